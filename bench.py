@@ -12,15 +12,25 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
     Either way every rank builds ITS slice of one global batch (per-env seeded: the slices concatenate to the
     same global batch for any N), envs are independent, and there is no collective on the data path
   * inputs are resident in HBM before the timed region; after the W warm-up steps the bench keeps stepping, untimed, for 0.25 s
-    (clock ramp of an idle box; the line's "warmup_extra_steps" says how many steps that was), then times R = --repeats (10)
-    BLOCKS of exactly K steps, each bracketed by barrier + synchronize, MAX over ranks per block.  value / ms_per_step are the
-    MEDIAN block ("median of >= 10 repeats"); "blocks" carries min / max / all of them
-  * rank 0 prints ONE JSON line (value = whole-job env-steps/s); for N > 1 the line also carries "other_scaling": the same
-    measurement in the other mode (so one scaling run holds the strong AND the weak row)
-  * "boundary": the same workload timed one level up, through the reference's autograd boundary -- ForwardWarp.apply(...) then
-    .backward() on tensors that require grad, workspace / output / gradient allocation included (N = 1 only)
+    (clock ramp of an idle box; the line's "warmup_extra_steps" says how many steps that was), then times R = --repeats BLOCKS of
+    exactly K steps, each bracketed by barrier + synchronize, MAX over ranks per block.  value / ms_per_step are the MEDIAN block;
+    "blocks" carries min / max / all of them.  A plain run times ONE block (R = 1): exactly K timed steps
+  * rank 0 prints ONE JSON line (value = whole-job env-steps/s)
+  * --dump-outputs DIR: right after the timed blocks, rank 0 writes what the last timed step computed -- the frame outputs of the
+    forward rollout (wp_pos, wp_vel, grf, jaf) and every gradient of the adjoint (grad_<input>) -- as DIR/<name>.npy, float32, with
+    the env axis explicit; above 60 MiB in all, the same seeded sample of envs is kept in every file.  The inputs are seeded: the
+    same arguments give the same inputs in every run, so two builds can be compared output for output
 
-Extra objects on the line:
+--full (off by default; a plain run does only setup, warm-up, the timed steps, the dump and the line) adds the measurements beside
+the headline, each run after the timed blocks (the dump is taken before them):
+  * R = 10 blocks by default ("median of >= 10 repeats")
+  * for N > 1 (or with --both) "other_scaling": the same measurement in the other mode (so one scaling run holds the strong AND
+    the weak row)
+  * "boundary": the same workload timed one level up, through the reference's autograd boundary -- ForwardWarp.apply(...) then
+    .backward() on tensors that require grad, workspace / output / gradient allocation included (N = 1 only; --no-boundary skips it)
+  * the per-kernel launch durations (per_rank[].fwd_kernel_ms / bwd_kernel_ms) and the objects below
+
+Extra objects on the --full line:
   roofline     dominant kernel (the adjoint rollout): algorithmic HBM bytes per launch / its average launch
                duration measured live with HIP events on the launch stream (pd_model_set_timing) on back-to-back
                launches in an extra un-timed pass; peak = 8 TB/s nominal (frac) and 6.3 TB/s achievable (frac_of_achievable);
@@ -28,7 +38,7 @@ Extra objects on the line:
                names it -- counters cannot be read inside this run); secondary = what actually bounds the kernel
                (waves per SIMD, VALU busy, LDS per workgroup) from the same profile + this run's launch geometry
   cpu_baseline the C oracle (oracle/ref_c, fp32, OpenMP over envs: "CPU restatement of the reference
-               algorithm, not Warp") timed on this host, rank 0, N = 1 only, on a bounded sample
+               algorithm, not Warp") timed on this host, rank 0, N = 1 only, on a bounded sample (--no-cpu-baseline skips it)
 """
 import argparse
 import json
@@ -187,22 +197,67 @@ def device_identity(dev):
     return ident
 
 
+DUMP_BUDGET_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, bufs, bs, nb, nq, nqd, nframes, nsteps):
+    """What one step of the timed path hands its caller -- rollout_forward's frame outputs and rollout_backward's gradients, read
+    from the reused buffers after the last timed step -- as out_dir/<name>.npy, float32, env axis explicit.  When all envs would
+    exceed DUMP_BUDGET_BYTES, the same envs of every array are kept: a sorted sample drawn with seed 0 (fixed for given arguments)."""
+    g = bufs["grads"]
+    arrays = {  # name -> (tensor viewed with its env axis, which axis that is)
+        "wp_pos": (bufs["wp_pos"].view(nframes, bs, nb, 7), 1),
+        "wp_vel": (bufs["wp_vel"].view(nframes, bs, nb, 6), 1),
+        "grf": (bufs["grf"].view(nframes, bs, nb, 6), 1),
+        "jaf": (bufs["jaf"].view(nframes, bs, nb, 6), 1),
+        "grad_q_init": (g["q_init"].view(bs, nq), 0),
+        "grad_qd_init": (g["qd_init"].view(bs, nqd), 0),
+        "grad_torques": (g["torques"].view(nsteps, bs, nqd), 1),
+        "grad_res_f": (g["res_f"].view(nsteps, bs, nb, 6), 1),
+        "grad_refs": (g["refs"].view(nsteps, bs, nqd), 1),
+        "grad_target_ke": (g["target_ke"].view(bs, nqd), 0),
+        "grad_target_kd": (g["target_kd"].view(bs, nqd), 0),
+        "grad_body_inv_mass": (g["body_inv_mass"].view(bs, nb), 0),
+        "grad_body_inertia": (g["body_inertia"].view(bs, nb, 3, 3), 0),
+        "grad_body_inv_inertia": (g["body_inv_inertia"].view(bs, nb, 3, 3), 0),
+    }
+    per_env = sum(t.numel() * t.element_size() for t, _ in arrays.values()) // bs
+    keep = min(bs, max(1, DUMP_BUDGET_BYTES // per_env))
+    idx = None
+    if keep < bs:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(bs, keep, replace=False))).to(bufs["wp_pos"].device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, axis) in arrays.items():
+        if idx is not None:
+            t = t.index_select(axis, idx)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=10, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median block is reported (default 1, or 10 with --full)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="weak: --bs envs per GPU; strong: --bs envs in total, sharded across the GPUs")
     ap.add_argument("--bs", type=int, default=GLOBAL_BS, help="envs per GPU (weak) / global batch (strong)")
     ap.add_argument("--T", type=int, default=100, help="sim steps per rollout")
     ap.add_argument("--robot", default="laikago")
     ap.add_argument("--segw", type=int, default=0, help="lanes per articulation (0 = default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-boundary", action="store_true", help="skip the autograd-boundary measurement")
-    ap.add_argument("--both", action="store_true", help="also measure the other scaling mode at N = 1 (always done for N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: kernel durations + roofline, the other scaling mode, the "
+                         "autograd-boundary number, the CPU baseline, 10 timed blocks by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32; rank 0's envs, a seeded sample "
+                         "of them when the whole would exceed 60 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-boundary", action="store_true", help="with --full: skip the autograd-boundary measurement")
+    ap.add_argument("--both", action="store_true", help="with --full: also measure the other scaling mode at N = 1 (always done for N > 1)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # typed as `python bench.py --gpus N`: start the N ranks ourselves, BEFORE anything in this process touches the GPU
@@ -282,7 +337,7 @@ def main():
             out = dm.rollout_forward(bs, T, inp["dt"], *fwd_args, frame2step=f2s, out=bufs)
             return dm.rollout_backward(bs, T, inp["dt"], *bwd_args, f2s, out[4], adj_pos, adj_vel, out=bufs)
 
-        return step, bs, gbs
+        return step, bs, gbs, bufs
 
     extra_warm = [0]
 
@@ -349,28 +404,32 @@ def main():
         return step
 
     local_blocks = []
-    step, bs, gbs = setup(args.scaling)
+    step, bs, gbs, bufs = setup(args.scaling)
     blocks, g = timed(step)
     local_ms = float(np.median(local_blocks)) / args.steps * 1e3
     elapsed = float(np.median(blocks))  # the median block: ms_per_step x steps = one real K-step block
     warm_extra = extra_warm[0]
     bad = int(torch.isnan(g["q_init"]).sum().item())
+    if args.dump_outputs and rank == 0:  # the buffers still hold the last timed step: nothing has run since
+        dump_outputs(args.dump_outputs, bufs, bs, dm.nb, dm.nq, dm.nqd, int(bufs["wp_pos"].shape[0]), T)
 
     # per-kernel device time (HIP events on the launch stream around each launch, pd_model_set_timing), in an extra pass outside
     # the timed region: batches of 10 steps enqueued back to back, as the timed region runs them, and the durations of the LAST
     # forward and adjoint launch of each batch are read (the read synchronises).  Bracketing every launch with a host
     # synchronisation instead reads 0.27 + 0.33 ms where the back-to-back pair takes 0.56 (clocks sag in the idle gaps);
-    # rocprofv3's per-dispatch durations of this same command (profiles/) are the quantity measured here.
-    dm.set_timing(True)
-    kf, kb = [], []
-    for _ in range(max(4, min(args.steps // 2, 10))):
-        for _ in range(10):
-            step()
-        torch.cuda.synchronize()
-        kf.append(dm.last_kernel_ms(0))
-        kb.append(dm.last_kernel_ms(1))
-    dm.set_timing(False)
-    fwd_ms, bwd_ms = float(np.mean(kf)), float(np.mean(kb))
+    # per-dispatch durations from a kernel trace of this same command (profiles/) are the quantity measured here.  --full only.
+    fwd_ms = bwd_ms = None
+    if args.full:
+        dm.set_timing(True)
+        kf, kb = [], []
+        for _ in range(max(4, min(args.steps // 2, 10))):
+            for _ in range(10):
+                step()
+            torch.cuda.synchronize()
+            kf.append(dm.last_kernel_ms(0))
+            kb.append(dm.last_kernel_ms(1))
+        dm.set_timing(False)
+        fwd_ms, bwd_ms = float(np.mean(kf)), float(np.mean(kb))
 
     # per rank: which kernel family ran the rank's shard and its OWN clock -- a scaling record can then tell a slow rank
     # from the latency floor of a small shard (512 envs per GPU at N = 8 take the quad-lane kernels)
@@ -382,8 +441,10 @@ def main():
         epw = 64 // max(1, dm.segment_width())                 # envs per wave of the lane-per-body kernels
         roles = waves * epw // envs                            # waves per env group
         return "lane per body: %d envs per wave, %d wave%s per env group" % (epw, roles, "" if roles == 1 else "s")
-    mine = {"rank": rank, "envs": bs, "ms_per_step": local_ms, "fwd_kernel_ms": fwd_ms, "bwd_kernel_ms": bwd_ms,
-            "fwd_family": family(0), "bwd_family": family(1), "segment_lanes": dm.segment_width()}
+    mine = {"rank": rank, "envs": bs, "ms_per_step": local_ms, "fwd_family": family(0), "bwd_family": family(1),
+            "segment_lanes": dm.segment_width()}
+    if args.full:
+        mine.update(fwd_kernel_ms=fwd_ms, bwd_kernel_ms=bwd_ms)
     per_rank = [mine]
     if world > 1:
         gathered = [None] * world
@@ -393,9 +454,9 @@ def main():
     # N > 1: the same measurement in the OTHER scaling mode, reported beside the main one (SURVEY section 8(d) writes C4 as
     # one 4096-env batch split over the GPUs = strong; the driver's contract quotes weak).  At N = 1 the two coincide.
     other = None
-    if world > 1 or args.both:
+    if args.full and (world > 1 or args.both):
         o_mode = "strong" if args.scaling == "weak" else "weak"
-        o_step, o_bs, o_gbs = setup(o_mode)
+        o_step, o_bs, o_gbs, _ = setup(o_mode)
         o_blocks, _ = timed(o_step)
         o_elapsed = float(np.median(o_blocks))
         other = {"scaling": o_mode, "value": o_gbs * T * args.steps / o_elapsed, "unit": "env-steps/s", "ms_per_step": o_elapsed / args.steps * 1e3,
@@ -403,7 +464,7 @@ def main():
                  "blocks": {"n": len(o_blocks), "min_value": o_gbs * T * args.steps / max(o_blocks), "max_value": o_gbs * T * args.steps / min(o_blocks)}}
 
     boundary = None
-    if world == 1 and not args.no_boundary:
+    if args.full and world == 1 and not args.no_boundary:
         b_blocks, gb = timed(boundary_step_factory())
         b_elapsed = float(np.median(b_blocks))
         boundary = {"value": gbs * T * args.steps / b_elapsed, "unit": "env-steps/s", "ms_per_step": b_elapsed / args.steps * 1e3,
@@ -412,7 +473,8 @@ def main():
                             "save_for_backward and the in-kernel remove_nan included; median of %d blocks of %d steps" % (len(b_blocks), args.steps),
                     "nan_grads": int(torch.isnan(gb["q_init"]).sum().item())}
 
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         nb, nqd = int(tpl["nb"]), int(tpl["nqd"])
         bf, bb = algorithmic_bytes(nb, nqd)
         ach_bwd = bs * T * bb / (bwd_ms * 1e-3)
@@ -469,6 +531,43 @@ def main():
                     "frac_of_vector_peak_note": "instructions x 64 lanes x 2 flop (every instruction priced as an FMA: an upper bound) / 157.3 TFLOP/s",
                     "insts_per_launch": n, "cycles_per_instruction": VALU_CYCLES_PER_INST, "clock_ghz_assumed": 2.4}
 
+        roofline = {
+            # what binds is fp32 VALU issue (roofline.valu); achieved / peak / unit / frac below stay the HBM figures the contract
+            # defines (algorithmic bytes / launch duration against 8 TB/s), repeated as hbm_frac
+            "bound": "valu-issue",
+            "hbm_frac": ach_bwd / HBM_PEAK_BYTES,
+            "limiter": "fp32 VALU issue: a SIMD issues one non-packed wave64 fp32 instruction per ~4.2 cycles whatever the waves or "
+                       "their ILP; the adjoint's two waves per SIMD keep it ~95 % busy (roofline.valu; the forward pass, three waves per SIMD -- "
+                       "body, contact, cull -- ~56 %: the step's chain crosses two hand-overs).  frac of HBM is what the contract asks for",
+            "valu": valu_roofline(pb, bwd_ms),
+            "kernel": "k_rollout_bwd",
+            "achieved": ach_bwd / 1e9,
+            "peak": HBM_PEAK_BYTES / 1e9,
+            "unit": "GB/s",
+            "frac": ach_bwd / HBM_PEAK_BYTES,
+            "frac_of_achievable": ach_bwd / HBM_ACHIEVABLE_BYTES,
+            "peak_achievable": HBM_ACHIEVABLE_BYTES / 1e9,
+            "traffic": pb.get("hbm_bytes_per_launch") if same_cfg else None,
+            "traffic_source": ("profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of `bench.py --steps 10`), NOT measured in "
+                               "this run; taken on library source %s = the one loaded here" % (prof.get("tag", "pmc_summary.json"), prof_hash)) if (same_cfg and pb)
+                              else ("the committed profile is of another build (library source %s, loaded %s): counter-derived fields are null"
+                                    % (prof_hash, lib_hash) if stale_profile else None),
+            "avg_launch_ms": bwd_ms,
+            # the event pass against the timed region: its forward + adjoint launch durations / the timed ms per step.  Above 1 = the
+            # event pass runs slower than the timed blocks (the event records sit between the launches), i.e. `frac` UNDERSTATES the
+            # kernel by about that factor; pair_frac_timed = the whole pair's algorithmic bytes / the TIMED step against 8 TB/s
+            "event_pass_over_timed": (fwd_ms + bwd_ms) / (elapsed / args.steps * 1e3),
+            "pair_frac_timed": bs * T * (bf + bb) / (elapsed / args.steps) / HBM_PEAK_BYTES,
+            "algorithmic_bytes_per_env_step": bb,
+            "secondary": secondary(geo_b, pb),
+            "fwd_kernel": {"kernel": "k_rollout_fwd", "achieved": ach_fwd / 1e9, "frac": ach_fwd / HBM_PEAK_BYTES,
+                           "frac_of_achievable": ach_fwd / HBM_ACHIEVABLE_BYTES, "avg_launch_ms": fwd_ms,
+                           "algorithmic_bytes_per_env_step": bf, "secondary": secondary(geo_f, pf), "valu": valu_roofline(pf, fwd_ms)},
+            "note": "VALU-issue bound (adjoint) / hand-over chain of three waves sharing a SIMD's issue slots (forward), not HBM-bound (roofline.valu, roofline.secondary, "
+                    "DESIGN.md section 4); launch durations are per dispatch, measured on launches enqueued back to back like the timed region",
+        }
+
+    if rank == 0:
         line = {
             "metric": "env-steps/sec (fwd+adjoint), Laikago 12-DoF, batch=4096, 1/2/4/8 MI355X",
             "value": gbs * T * args.steps / elapsed,
@@ -476,7 +575,7 @@ def main():
             "n_gpus": world,
             "collective_backend": backend,   # "nccl" (= RCCL) | "gloo" (RCCL could not come up) | null at N = 1: barrier + MAX only
             "ranks_seen": ranks_seen,        # all-reduced count of ranks behind that backend
-            "per_rank": per_rank,            # all-gathered: each rank's shard, kernel family, own ms_per_step and kernel durations
+            "per_rank": per_rank,            # all-gathered: each rank's shard, kernel family, own ms_per_step (+ kernel durations: --full)
             "devices_seen": devices_seen,    # all-gathered identity (UUID / PCI address) of each rank's GPU: N distinct unless PPR_BENCH_SHARE_GPU (a test hook)
             "devices_distinct": len({json.dumps({k: v for k, v in d.items() if k not in ("index", "name")} or d, sort_keys=True) for d in devices_seen}),
             "launcher": "self" if os.environ.get("PPR_BENCH_SELF_LAUNCHED") else ("torch.distributed.run" if world > 1 else "none"),
@@ -502,47 +601,14 @@ def main():
                 "segment_lanes": dm.segment_width(),
                 "nan_grads": bad,
             },
-            "roofline": {
-                # what binds is fp32 VALU issue (roofline.valu); achieved / peak / unit / frac below stay the HBM figures the contract
-                # defines (algorithmic bytes / launch duration against 8 TB/s), repeated as hbm_frac
-                "bound": "valu-issue",
-                "hbm_frac": ach_bwd / HBM_PEAK_BYTES,
-                "limiter": "fp32 VALU issue: a SIMD issues one non-packed wave64 fp32 instruction per ~4.2 cycles whatever the waves or "
-                           "their ILP; the adjoint's two waves per SIMD keep it ~95 % busy (roofline.valu; the forward pass, three waves per SIMD -- "
-                           "body, contact, cull -- ~56 %: the step's chain crosses two hand-overs).  frac of HBM is what the contract asks for",
-                "valu": valu_roofline(pb, bwd_ms),
-                "kernel": "k_rollout_bwd",
-                "achieved": ach_bwd / 1e9,
-                "peak": HBM_PEAK_BYTES / 1e9,
-                "unit": "GB/s",
-                "frac": ach_bwd / HBM_PEAK_BYTES,
-                "frac_of_achievable": ach_bwd / HBM_ACHIEVABLE_BYTES,
-                "peak_achievable": HBM_ACHIEVABLE_BYTES / 1e9,
-                "traffic": pb.get("hbm_bytes_per_launch") if same_cfg else None,
-                "traffic_source": ("profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of `bench.py --steps 10`), NOT measured in "
-                                   "this run; taken on library source %s = the one loaded here" % (prof.get("tag", "pmc_summary.json"), prof_hash)) if (same_cfg and pb)
-                                  else ("the committed profile is of another build (library source %s, loaded %s): counter-derived fields are null"
-                                        % (prof_hash, lib_hash) if stale_profile else None),
-                "avg_launch_ms": bwd_ms,
-                # the event pass against the timed region: its forward + adjoint launch durations / the timed ms per step.  Above 1 = the
-                # event pass runs slower than the timed blocks (the event records sit between the launches), i.e. `frac` UNDERSTATES the
-                # kernel by about that factor; pair_frac_timed = the whole pair's algorithmic bytes / the TIMED step against 8 TB/s
-                "event_pass_over_timed": (fwd_ms + bwd_ms) / (elapsed / args.steps * 1e3),
-                "pair_frac_timed": bs * T * (bf + bb) / (elapsed / args.steps) / HBM_PEAK_BYTES,
-                "algorithmic_bytes_per_env_step": bb,
-                "secondary": secondary(geo_b, pb),
-                "fwd_kernel": {"kernel": "k_rollout_fwd", "achieved": ach_fwd / 1e9, "frac": ach_fwd / HBM_PEAK_BYTES,
-                               "frac_of_achievable": ach_fwd / HBM_ACHIEVABLE_BYTES, "avg_launch_ms": fwd_ms,
-                               "algorithmic_bytes_per_env_step": bf, "secondary": secondary(geo_f, pf), "valu": valu_roofline(pf, fwd_ms)},
-                "note": "VALU-issue bound (adjoint) / hand-over chain of three waves sharing a SIMD's issue slots (forward), not HBM-bound (roofline.valu, roofline.secondary, "
-                        "DESIGN.md section 4); launch durations are per dispatch, measured on launches enqueued back to back like the timed region",
-            },
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if other is not None:
             line["other_scaling"] = other
         if boundary is not None:
             line["boundary"] = boundary
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(tpl, args.robot, T, seqs)
         print(json.dumps(line))
     if world > 1:

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_contract_and_consistency():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "3", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "3", "--full", "--no-cpu-baseline"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -76,7 +77,7 @@ def test_bench_self_launches_two_ranks():
     one_gpu = dict(os.environ, HIP_VISIBLE_DEVICES=first)
     one_gpu.pop("CUDA_VISIBLE_DEVICES", None)
     env = dict(one_gpu, PPR_BENCH_SHARE_GPU="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "3"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "3", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -95,3 +96,37 @@ def test_bench_self_launches_two_ranks():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "2"],
                          cwd=ROOT, capture_output=True, text=True, timeout=300, env=env2)
     assert out.returncode != 0 and "no GPU of its own" in out.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one block, prints the headline fields only, and with --dump-outputs
+    writes the last timed step's frame outputs and gradients as float32 .npy files within 64 MB.  The inputs are seeded, so a second
+    run with another step count dumps the same outputs."""
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / ("s%d" % steps)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["unit"] == "env-steps/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+        assert line["steps"] == steps and line["warmup"] == 1 and line["blocks"]["n"] == 1 and line["config"]["nan_grads"] == 0
+        assert abs(line["value"] - 4096 * 100 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        for k in ("roofline", "boundary", "cpu_baseline", "other_scaling"):
+            assert k not in line, k
+        files = sorted(os.listdir(str(d)))
+        assert "wp_pos.npy" in files and "grad_q_init.npy" in files and "grad_torques.npy" in files, files
+        assert sum(os.path.getsize(os.path.join(str(d), f)) for f in files) <= 64 * 10 ** 6
+        arrays = {f: np.load(os.path.join(str(d), f)) for f in files}
+        for f, a in arrays.items():
+            assert a.dtype == np.float32 and a.size > 0 and not np.isnan(a).any(), f
+        n_env = arrays["grad_q_init.npy"].shape[0]
+        assert arrays["wp_pos.npy"].shape == (4, n_env, 13, 7) and arrays["grad_torques.npy"].shape == (100, n_env, 18)
+        dumps.append(arrays)
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    for f in a:
+        assert a[f].shape == b[f].shape and np.allclose(a[f], b[f], rtol=1e-5, atol=1e-6 * (np.abs(b[f]).max() + 1e-30)), f
