@@ -72,10 +72,15 @@ int pd_abi_version(void);
 const char *pd_build_id(void);
 const char *pd_last_error(void);
 
+/* Placement of the contact tables (up to 65 535 candidates): the rollout kernels copy them into LDS once per workgroup, beside the
+ * envs' scratch, and the default segment width is the narrowest >= nb at which both fit 160 KiB.  A robot whose tables fit at NO
+ * width (more than ~7 000 mesh candidates) keeps them in global memory instead: then the default is the narrowest width at which
+ * its envs' scratch alone fits, and only a robot whose scratch fits at no width is refused ("model needs N B of LDS ..."). */
 int pd_model_create(const pd_model_desc *desc, pd_model **out);
 void pd_model_destroy(pd_model *m);
 /* Lanes of a 64-wide wavefront given to one articulation: 16, 32 or 64 (>= nb).  0 = default
- * (smallest that fits).  64 is the literal "one articulation per wavefront" mapping. */
+ * (smallest that fits).  64 is the literal "one articulation per wavefront" mapping.  The tables stay where pd_model_create put
+ * them: a model with tables in global memory accepts every width at which its envs' scratch fits. */
 int pd_model_set_segment_width(pd_model *m, int lanes);
 int pd_model_get_segment_width(const pd_model *m);
 
@@ -83,7 +88,8 @@ int pd_model_get_segment_width(const pd_model *m);
  * (Laikago) run the QUAD-LANE kernels (four lanes per body, one articulation per wavefront: a shorter instruction stream per step,
  * three times the lane-cycles per env) while the batch fits one workgroup per compute unit (<= 4 x CUs envs = 1 024 on MI355X) and the
  * lane-per-body kernels above that; 1: lane per body always; 2: quad-lane wherever the robot is eligible (tests, A/B timing).
- * pd_model_get_kernel_family returns the setting; *eligible (may be NULL) = 1 when the robot has quad-lane kernels at all. */
+ * pd_model_get_kernel_family returns the setting; *eligible (may be NULL) = 1 when the robot has quad-lane kernels at all (whether
+ * its contact tables live in LDS or, when they fit at no segment width, in global memory). */
 int pd_model_set_kernel_family(pd_model *m, int family);
 int pd_model_get_kernel_family(const pd_model *m, int *eligible);
 

@@ -47,6 +47,8 @@ struct PdDevModel {
   int env_lds_rec2;                                       // quad-lane adjoint (64-lane copy of an eligible model, else 0): PD_QGEN generations of cull vectors + records and of the state-only hand-over
   const float *X_p_env;                                   // [xp_envs][nb][7] per-env joint_X_p bound by the caller, or null (template X_p)
   int xp_envs;
+  int global_tables;                                      // 1: the contact tables stay in global memory (the rollout kernels' GT instantiations;
+                                                          // a model whose tables fit in LDS at no segment width, pd_host.hip build_device)
 };
 
 #define WAVE_SYNC()                                        \

@@ -121,7 +121,13 @@ static int jt_slot(int jt) { return jt == PD_JT_REVOLUTE ? 0 : (jt == PD_JT_COMP
 
 // Builds the device copy for segment width `segw` into temporaries and commits blob / dev / lds_* / segw / jt only when
 // every check has passed: a failed call leaves the model exactly as it was.
-static int build_device(pd_model *m, int segw) {
+// global_tables: the contact tables stay in global memory and only the per-env part of a workgroup's LDS has to fit -- for the
+// models whose tables fit at NO width (pd_model_create); every other model keeps them in LDS.  A -DPD_GLOBAL_TABLES build (checking
+// build: only the tables' address space differs, the bits must not) puts every model there.
+static int build_device(pd_model *m, int segw, bool global_tables) {
+#ifdef PD_GLOBAL_TABLES
+  global_tables = true;
+#endif
   const int nb = m->nb;
   if (segw == 0) segw = nb <= 16 ? 16 : (nb <= 32 ? 32 : 64);
   if (segw != 16 && segw != 32 && segw != 64) return fail("segment width must be 16, 32 or 64");
@@ -240,6 +246,7 @@ static int build_device(pd_model *m, int segw) {
   // the speculative cull's margin (pd_kernels.hip sink_margin): tight where candidates are many (mesh robots), generous where they are few
   d.spec_safety = nc > 512 ? 1.25f : 3.0f; d.spec_slack = nc > 512 ? 1.0e-4f : 1.0e-3f;
   d.X_p_env = m->xp_env; d.xp_envs = m->xp_envs;
+  d.global_tables = global_tables ? 1 : 0;
   // cull vectors (float4 per body, 16-B aligned) + records + wrench slots + adjoint slots + tile list + hit list (8*segw) + per-hit result slots (13*segw)
   d.env_lds_floats = ((nb * (4 + PD_REC + PD_W6 + 2 * PD_ADJ) + PD_ADJ + std::max(ntiles, 2 * nb) + 8 * segw + PD_ADJ * segw + 3) / 4) * 4 + 4;  // + PD_ADJ: the zero record
   // lanes (env e, body b) of one wave address base_e + f(b): an env stride of 16 mod 32 floats lets the envs of a wave
@@ -248,7 +255,10 @@ static int build_device(pd_model *m, int segw) {
   const int envs_per_block = PD_BWAVES * (64 / segw);
   const size_t lds_tables = (size_t)std::max(nc, 1) * 16 + (size_t)std::max(ntiles, 1) * 32 + (size_t)std::max(m->nmat, 1) * 16 +
                             (size_t)((std::max(ntiles, 1) + 3) & ~3) * 4 + (size_t)((nb + 1) & ~1) * 8 + (size_t)((std::max(nc, 1) + 15) & ~15);
-  const size_t lds_rollout = lds_tables + (size_t)envs_per_block * d.env_lds_floats * 4;
+  // (the kernels that copy the tables into LDS take them from global memory instead when global_tables is set: they need no LDS then.
+  // The cull wave's candidate and tile lists are part of env_lds_floats, so pd_fwd_cull_cap gives the same answer either way)
+  const size_t lds_tab = global_tables ? 0 : lds_tables;
+  const size_t lds_rollout = lds_tab + (size_t)envs_per_block * d.env_lds_floats * 4;
   {
     int dev_id = 0, cus = 0;
     if (hipGetDevice(&dev_id) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess) cus = 0;
@@ -266,9 +276,13 @@ static int build_device(pd_model *m, int segw) {
   // k_rollout_bwd3 with the contact tables in LDS (or the unsplit kernel, A/B only)
   const size_t lds_rollout_bwd = jt == PD_JT_REVOLUTE
                                      ? (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4
-                                     : lds_tables + (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats) * 4;
+                                     : lds_tab + (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats) * 4;
   // (the 160 KiB checks below are for PD_BWAVES env groups per workgroup, the most a launch uses)
   const size_t lds_fk = (size_t)envs_per_block * nb * (PD_REC + PD_ADJ) * 4;
+  if (global_tables) {  // (the tables are out of LDS already: what is left is the envs' own scratch)
+    if (lds_rollout_bwd > 160 * 1024 || lds_rollout > 160 * 1024)
+      return fail("model needs " + std::to_string(std::max(lds_rollout, lds_rollout_bwd)) + " B of LDS per workgroup for its envs' scratch alone, contact tables in global memory (> 160 KiB)");
+  }
   if (lds_rollout_bwd > 160 * 1024) return fail("model needs " + std::to_string(lds_rollout_bwd) + " B of LDS per workgroup (> 160 KiB); use a wider segment");
   if (lds_rollout > 160 * 1024) return fail("model needs " + std::to_string(lds_rollout) + " B of LDS per workgroup (> 160 KiB); use a wider segment");
   // (k_reduce_fk runs FK workgroups of PD_REDUCE_BLOCK / 64 body waves: that many times the 4-wave FK workgroup's records)
@@ -313,13 +327,14 @@ static int build_device(pd_model *m, int segw) {
 
 // The quad-lane kernels' device copy (64-lane mapping).  Eligible: revolute-only PLAIN models (pd_parented: what the specialised
 // instantiation assumes) with at most 16 bodies.  Not an error when the model is not eligible or the copy does not fit: the
-// lane-per-body kernels then serve every batch size.
+// lane-per-body kernels then serve every batch size.  The copy keeps its tables where the model keeps its own (global memory for a
+// model whose tables fit at no width).
 static void build_quad(pd_model *m) {
   free_quad(m);
   if (m->jt != PD_JT_REVOLUTE || m->nb > 16) return;
   pd_model tmp = *m;  // host arrays are copied, the device copy is built into the temporary and moved over
   tmp.blob = nullptr; tmp.quad = nullptr;
-  if (build_device(&tmp, 64) != 0 || tmp.jt != PD_JT_REVOLUTE) { if (tmp.blob) (void)hipFree(tmp.blob); return; }
+  if (build_device(&tmp, 64, m->dev.global_tables != 0) != 0 || tmp.jt != PD_JT_REVOLUTE) { if (tmp.blob) (void)hipFree(tmp.blob); return; }
   m->quad = new pd_model::Quad{tmp.blob, tmp.dev, tmp.lds_tables, tmp.jt};
 }
 
@@ -329,11 +344,15 @@ static int g_groups = 0;   // -DPD_STAMPS diagnostic builds only (pd_debug_set_g
 static PdLaunchCfg launch_cfg(const pd_model *m, int kind, int n_envs, bool loss = false) {
   const PdDevModel &d = m->dev;
   const int epw = 64 / m->segw, n_groups = (n_envs + epw - 1) / epw;
+  const size_t tab = d.global_tables ? 0 : m->lds_tables;  // contact tables in LDS, for the kernels that copy them there
   PdLaunchCfg c{};
   c.kernel = pd_kernel_variant(kind, m->jt, n_groups, d.cu_count);
   // the loss-evaluating forward exists wave-specialised only (round 6): its unsplit instantiation does not survive the register allocator in
   // the branch-free form the other forward kernels of plain models have, and an env must give the same bits whichever kernel runs it
   if (loss && c.kernel == PD_KV_FWD_UNSPLIT) c.kernel = PD_KV_FWD_SPLIT;
+  // ... and so does every forward of a model with its contact tables in global memory: the unsplit kernel has no such instantiation
+  // (its register allocation fails to compile with the table pointers in registers); both kernels give an env the same bits
+  if (d.global_tables && c.kernel == PD_KV_FWD_UNSPLIT) c.kernel = PD_KV_FWD_SPLIT;
   c.roles = pd_variant_roles(c.kernel);
 #ifndef PD_NO_CULLW
   // revolute-only robots: a third wave per env group runs the speculative contact cull (k_rollout_fwd CULLW)
@@ -345,10 +364,10 @@ static PdLaunchCfg launch_cfg(const pd_model *m, int kind, int n_envs, bool loss
   c.threads = c.roles * c.groups * 64;
   const size_t envs = (size_t)c.groups * epw;
   switch (c.kernel) {
-    case PD_KV_FWD_SPLIT: case PD_KV_FWD_UNSPLIT: case PD_KV_BWD_UNSPLIT: c.lds = m->lds_tables + envs * d.env_lds_floats * 4; break;
+    case PD_KV_FWD_SPLIT: case PD_KV_FWD_UNSPLIT: case PD_KV_BWD_UNSPLIT: c.lds = tab + envs * d.env_lds_floats * 4; break;
     case PD_KV_BWD_2ROLE: case PD_KV_BWD_2ROLE_EARLY: c.lds = envs * (d.env_lds_floats + 2 * d.env_lds_jc) * 4; break;
     case PD_KV_BWD_3ROLE: c.lds = envs * d.env_lds_bwd3 * 4; break;
-    case PD_KV_BWD3_2ROLE: c.lds = m->lds_tables + envs * d.env_lds_bwd3 * 4; break;
+    case PD_KV_BWD3_2ROLE: c.lds = tab + envs * d.env_lds_bwd3 * 4; break;
     default: c.lds = m->lds_fk; break;
   }
   return c;
@@ -377,7 +396,7 @@ static hipError_t launch(const pd_model *m, int kind, const void *args, int n_en
     if (kind == PD_K_ROLLOUT_BWD && c.groups > 2) c.groups = 2;   // (three roles: at most 384 threads, two waves per SIMD -- the body wave needs its 256 VGPRs)
     c.nblocks = (n_envs + c.groups - 1) / c.groups;
     c.threads = c.roles * c.groups * 64;
-    c.lds = kind == PD_K_ROLLOUT_FWD ? m->quad->lds_tables + (size_t)c.groups * d.env_lds_floats * 4   // contact tables in LDS
+    c.lds = kind == PD_K_ROLLOUT_FWD ? (d.global_tables ? 0 : m->quad->lds_tables) + (size_t)c.groups * d.env_lds_floats * 4   // contact tables in LDS (unless global)
                                      : (size_t)c.groups * (d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4;  // adjoint: + joint hand-over records + second generation of records
     if (c.nblocks == 0) return hipSuccess;
     int *ll = const_cast<pd_model *>(m)->last_launch[kind];
@@ -474,10 +493,13 @@ int pd_model_create(const pd_model_desc *d, pd_model **out) {
   for (int k = 0; k < d->nc; ++k)
     if (m->cbody[k] < 0 || m->cbody[k] >= d->nb) { delete m; return fail("contact_body out of range"); }
   // default segment width: the narrowest that holds the bodies AND whose workgroup (contact tables + 64/width envs per
-  // wave) fits the 160 KiB of LDS -- a robot with more contact candidates gets fewer envs per workgroup instead of an error
+  // wave) fits the 160 KiB of LDS -- a robot with more contact candidates gets fewer envs per workgroup instead of an error.
+  // A robot whose tables fit at NO width keeps them in global memory: then the narrowest width at which its envs' scratch fits.
   {
+    const int w0 = m->nb <= 16 ? 16 : (m->nb <= 32 ? 32 : 64);
     int rc = 1;
-    for (int w = m->nb <= 16 ? 16 : (m->nb <= 32 ? 32 : 64); w <= 64 && rc; w *= 2) rc = build_device(m, w);
+    for (int w = w0; w <= 64 && rc; w *= 2) rc = build_device(m, w, false);
+    for (int w = w0; w <= 64 && rc; w *= 2) rc = build_device(m, w, true);
     if (rc) { free_device(m); delete m; return 1; }
   }
   build_quad(m);
@@ -497,10 +519,11 @@ void pd_model_destroy(pd_model *m) {
 }
 
 // Setup-time call: the device copy is rebuilt (one synchronisation, because launches in flight may still read the old one).
+// The tables stay where pd_model_create put them: a model with tables in global memory accepts every width its envs' scratch fits.
 int pd_model_set_segment_width(pd_model *m, int lanes) {
   if (!m) return fail("null model");
   (void)hipDeviceSynchronize();
-  if (build_device(m, lanes)) return 1;
+  if (build_device(m, lanes, m->dev.global_tables != 0)) return 1;
   build_quad(m);
   return 0;
 }

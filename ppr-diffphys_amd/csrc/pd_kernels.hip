@@ -550,7 +550,9 @@ PD_DEV float *lds_setup(const PdDevModel &m, unsigned char *smem, SweepTables &T
 #define pair_wait(f, v) pair_wait_knock(f, v, knock_role)
 #endif
 // RUNSUM (with CULLW, lane per body): the hit pass sums per body in registers -- launched when four env groups fill the workgroup (see there)
-template <int SEGW, int JT, bool SPLIT, bool LOSS = false, bool QUAD = false, bool CULLW = false, bool RUNSUM = false>
+// GT (global tables): the contact tables stay in global memory (lds_setup<false>) -- instantiated for the models whose tables fit in LDS at
+// no segment width (pd_host.hip build_device); the sweeps read them through the same SweepTables pointers, the arithmetic is the same
+template <int SEGW, int JT, bool SPLIT, bool LOSS = false, bool QUAD = false, bool CULLW = false, bool RUNSUM = false, bool GT = false>
 __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK), CULLW ? 3 : 2) void k_rollout_fwd(PdDevModel m, RolloutArgs a) {
   static_assert(!RUNSUM || (CULLW && !QUAD), "run sums in the hit pass: the lane-per-body kernels with the cull wave");
   // TRAJC: the contact wave stores planes 0-2 of the trajectory out of the staged records (round 3 measured this a loss, when that wave's idle
@@ -577,7 +579,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
   const int nb = m.nb, N = a.bs * nb;
 
   SweepTables tabs;
-  float *scratch = lds_setup<true>(m, smem, tabs, wave * EPW + seg, m.env_lds_floats);
+  float *scratch = lds_setup<!GT>(m, smem, tabs, wave * EPW + seg, m.env_lds_floats);
   float4 *cull = (float4 *)scratch;
   // pcon: nb + 1 records, the last one stays zero and stands in for "no child" (the gather then needs no predicates)
   float *rec = scratch + 4 * nb, *facc = rec + nb * PD_REC, *pcon = facc + nb * PD_W6;
@@ -2270,7 +2272,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
 // ROLES = 3: I, C, J waves (<= 168 VGPRs each).  ROLES = 2: the integrate wave also replays the contacts (between its phase 2
 // and the wait for the joint wave) -- compound-joint robots, whose joint adjoint needs more than 168 registers but whose
 // box contacts are a handful of points: two waves per env group, <= 256 VGPRs each.
-template <int SEGW, int JT, int ROLES>
+template <int SEGW, int JT, int ROLES, bool GT = false>  // GT: contact tables in global memory, as k_rollout_fwd
 __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevModel m, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
@@ -2291,7 +2293,7 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
 
   SweepTables tabs;
   // ROLES == 2: the (small) contact tables are copied into LDS, the inline replay then has no exposed global loads
-  float *scratch = lds_setup<ROLES == 2>(m, smem, tabs, wave * EPW + seg, m.env_lds_bwd3);
+  float *scratch = lds_setup<ROLES == 2 && !GT>(m, smem, tabs, wave * EPW + seg, m.env_lds_bwd3);
   // staged records and cull vectors: TWO generations, by step parity -- the integrate wave stages step - 1 while the other
   // waves still work on step (the joint wave then starts the state-only half of step - 1 without waiting for anybody)
   float4 *const cull0 = (float4 *)scratch;
@@ -2863,7 +2865,9 @@ __global__ __launch_bounds__(PD_FK_BLOCK) void k_seeds_fk(PdDevModel m, SeedsFkA
 // workgroups pack twice as many body waves per SIMD (quad at 8192 envs: split +22 %), so the launcher picks per launch.
 
 // cfg: the host's choice for this launch (pd_args.h: pd_launch_cfg) -- kernel variant, workgroups, threads, LDS bytes
-template <int JT>
+// GT: the model keeps its contact tables in global memory (m.global_tables) -- the rollout kernels that copy them into LDS have a GT
+// instantiation, the rest (revolute-only adjoint kernels, FK) read no table from LDS and are the same kernels either way
+template <int JT, bool GT>
 static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, const PdLaunchCfg &cfg, hipStream_t st) {
   const dim3 g(cfg.nblocks), t(cfg.threads);
   const size_t lds = cfg.lds;
@@ -2873,11 +2877,11 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
         if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
           const bool loss = ((const RolloutArgs *)args)->loss_target != nullptr;
           if (cfg.roles == 3) {  // with the cull wave
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
           } else {
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
           }
           break;
         } else {
@@ -2888,11 +2892,11 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
         if constexpr (JT == PD_JT_REVOLUTE) {
           const bool loss = ((const RolloutArgs *)args)->loss_target != nullptr;
           if (cfg.groups >= PD_BWAVES) {  // full workgroups: per-body sums in registers (RUNSUM)
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
           } else {
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
+            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
           }
           break;
         } else {
@@ -2902,9 +2906,11 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
       // (unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation)
       if (((const RolloutArgs *)args)->loss_target) {  // trajectory loss at the frame states (pd_rollout_forward_traj_loss)
         if (cfg.kernel != PD_KV_FWD_SPLIT) return hipErrorInvalidValue;  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
-        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
+        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
       } else if (cfg.kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND)
-        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
+        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
+      else if constexpr (GT)  // (no unsplit instantiation with global tables -- it does not survive the register allocator: a model with its
+        return hipErrorInvalidValue;  // tables in global memory takes the split kernel at every batch size, pd_host.hip launch_cfg)
       else
         hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND>), g, t, lds, st, m, *(const RolloutArgs *)args);
       break;
@@ -2920,7 +2926,7 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
         }
         hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false>), g, t, lds, st, m, *(const RolloutArgs *)args);
       } else {
-        hipLaunchKernelGGL((k_rollout_bwd3<PD_SEGW, JT, 2>), g, t, lds, st, m, *(const RolloutArgs *)args);
+        hipLaunchKernelGGL((k_rollout_bwd3<PD_SEGW, JT, 2, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
       }
       break;
 #if PD_POLICY == 0  // (the host routes the FK kinds to these launchers whatever the model's policy)
@@ -2943,35 +2949,37 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
   return hipGetLastError();
 }
 
-template <int JT>
-static hipError_t set_lds_jt(int bytes) {
+template <int JT, bool GT>
+static hipError_t set_lds_gt(int bytes) {
   hipError_t e;
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if constexpr (!GT)
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   }
   if constexpr (JT == PD_JT_REVOLUTE) {  // ... with the cull wave
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     if constexpr (PD_SEGW == 64) {
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     }
   }
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   if constexpr (pd_split(JT)) {
     if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
       if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     }
   } else {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd3<PD_SEGW, JT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd3<PD_SEGW, JT, 2, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   }
 #if PD_POLICY == 0
+  if constexpr (GT) return hipSuccess;  // (the FK kernels are the same for both placements: set with GT = false)
   if ((e = hipFuncSetAttribute((const void *)k_fk<PD_SEGW, JT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   if ((e = hipFuncSetAttribute((const void *)k_reduce_fk<PD_SEGW, JT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   if ((e = hipFuncSetAttribute((const void *)k_seeds_fk<PD_SEGW, JT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
@@ -2981,11 +2989,22 @@ static hipError_t set_lds_jt(int bytes) {
 #endif
 }
 
+template <int JT>
+static hipError_t set_lds_jt(int bytes) {
+  const hipError_t e = set_lds_gt<JT, false>(bytes);
+  return e != hipSuccess ? e : set_lds_gt<JT, true>(bytes);
+}
+
 // jt: PD_JT_REVOLUTE only, PD_JT_COMPOUND only, anything else -> generic (all joint types)
 hipError_t PD_LAUNCH_NAME(PD_SEGW)(int kind, int jt, const PdDevModel &m, const void *args, const PdLaunchCfg &cfg, hipStream_t st) {
-  if (jt == PD_JT_REVOLUTE) return launch_jt<PD_JT_REVOLUTE>(kind, m, args, cfg, st);
-  if (jt == PD_JT_COMPOUND) return launch_jt<PD_JT_COMPOUND>(kind, m, args, cfg, st);
-  return launch_jt<PD_JT_REVOLUTE | PD_JT_COMPOUND | PD_JT_FIXED>(kind, m, args, cfg, st);
+  if (m.global_tables) {
+    if (jt == PD_JT_REVOLUTE) return launch_jt<PD_JT_REVOLUTE, true>(kind, m, args, cfg, st);
+    if (jt == PD_JT_COMPOUND) return launch_jt<PD_JT_COMPOUND, true>(kind, m, args, cfg, st);
+    return launch_jt<PD_JT_REVOLUTE | PD_JT_COMPOUND | PD_JT_FIXED, true>(kind, m, args, cfg, st);
+  }
+  if (jt == PD_JT_REVOLUTE) return launch_jt<PD_JT_REVOLUTE, false>(kind, m, args, cfg, st);
+  if (jt == PD_JT_COMPOUND) return launch_jt<PD_JT_COMPOUND, false>(kind, m, args, cfg, st);
+  return launch_jt<PD_JT_REVOLUTE | PD_JT_COMPOUND | PD_JT_FIXED, false>(kind, m, args, cfg, st);
 }
 hipError_t PD_SET_LDS_NAME(PD_SEGW)(int jt, int bytes) {
   if (jt == PD_JT_REVOLUTE) return set_lds_jt<PD_JT_REVOLUTE>(bytes);

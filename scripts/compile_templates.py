@@ -5,6 +5,12 @@ Run HERE (the container with /root/reference); outputs are committed:
   ppr-diffphys_amd/diffphys_amd/templates/{laikago,human,quad}.npz   articulation templates
   ppr-diffphys_amd/diffphys_amd/templates/mocap_laikago.npz          AMP frames of the 5 sequences
 
+Opt-in target (not written by a plain run, so the outputs above are never rewritten by it):
+  --laikago-toes   tests/golden/template_laikago_toes.npz: laikago_toes.urdf (full lower-leg collision mesh + toe spheres,
+                   ~11 000 contact candidates) with Laikago's constants -- the test model of a robot whose contact tables do
+                   not fit in LDS (tests/test_gpu_large_contact_sets.py).  robots.PRESETS has no such entry (the reference's
+                   phys_model offers no such preset): the preset lives here, for this one compilation.
+
 The npz files hold DATA only (flat arrays derived from the URDF / mesh / json
 data files under /root/reference/data, Laikago meshes: PyBullet/Unitree
 licence, see data/urdf_templates/laikago/license.txt there).  Nothing on the
@@ -21,18 +27,36 @@ sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
 from diffphys_amd import robots  # noqa: E402
 
 REF = os.environ.get("PPR_REFERENCE", "/root/reference")
+# laikago_toes.urdf with the constants of the reference's "laikago" branch (dp_model.py:83-91): the same tuple as PRESETS["laikago"]
+LAIKAGO_TOES = ("laikago/laikago_toes.urdf",) + robots.PRESETS["laikago"][1:]
+LAIKAGO_TOES_OUT = os.path.join(ROOT, "tests", "golden", "template_laikago_toes.npz")
+
+
+def _template(name, urdf_root):
+    env, art, info = robots.make_env(name, urdf_root, 1, device="cpu")
+    tpl = env.template()
+    tpl["body_names"] = np.asarray(info["body_names"])
+    tpl["kp"] = np.float32(info["kp"])
+    tpl["kd"] = np.float32(info["kd"])
+    tpl["mass_rule"] = np.asarray(info["mass_rule"])  # which reading of dp_model.py:185-191 produced body_mass (robots.MASS_RULES)
+    return tpl
+
+
+def compile_laikago_toes(ref=REF):
+    """The laikago_toes template as a dict of arrays (what --laikago-toes writes); robots.PRESETS is left as it was."""
+    saved = robots.PRESETS
+    robots.PRESETS = dict(saved, laikago_toes=LAIKAGO_TOES)
+    try:
+        return _template("laikago_toes", os.path.join(ref, "data/urdf_templates"))
+    finally:
+        robots.PRESETS = saved
 
 
 def main():
     out = robots.TEMPLATE_DIR
     os.makedirs(out, exist_ok=True)
     for name in ("laikago", "human", "quad"):
-        env, art, info = robots.make_env(name, os.path.join(REF, "data/urdf_templates"), 1, device="cpu")
-        tpl = env.template()
-        tpl["body_names"] = np.asarray(info["body_names"])
-        tpl["kp"] = np.float32(info["kp"])
-        tpl["kd"] = np.float32(info["kd"])
-        tpl["mass_rule"] = np.asarray(info["mass_rule"])  # which reading of dp_model.py:185-191 produced body_mass (robots.MASS_RULES)
+        tpl = _template(name, os.path.join(REF, "data/urdf_templates"))
         np.savez_compressed(os.path.join(out, name + ".npz"), **tpl)
         print(
             "%-8s nb=%d nq=%d nqd=%d Nc=%d mass=%s"
@@ -48,5 +72,12 @@ def main():
     np.savez_compressed(os.path.join(out, "mocap_laikago.npz"), **mocap)
 
 
+def main_laikago_toes():
+    tpl = compile_laikago_toes()
+    np.savez_compressed(LAIKAGO_TOES_OUT, **tpl)
+    print("laikago_toes nb=%d nq=%d nqd=%d Nc=%d -> %s (%d bytes)"
+          % (tpl["nb"], tpl["nq"], tpl["nqd"], len(tpl["contact_body"]), LAIKAGO_TOES_OUT, os.path.getsize(LAIKAGO_TOES_OUT)))
+
+
 if __name__ == "__main__":
-    main()
+    main_laikago_toes() if "--laikago-toes" in sys.argv[1:] else main()
