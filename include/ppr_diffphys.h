@@ -111,7 +111,7 @@ int pd_model_get_numeric_policy(const pd_model *m);
 /* Floats of caller-provided workspace that pd_rollout_forward fills and pd_rollout_backward reads:
  * per step the 13-float body state and the 6-float body wrench as five float4 planes [step][plane][bs*nb], followed
  * by the forward sweep's contact hit log (32 ints per env-step) that the adjoint replays.  The base must be 16-byte
- * aligned. */
+ * aligned.  A forward with no adjoint to follow needs none (NULL: forward-only, see pd_rollout_forward). */
 size_t pd_rollout_workspace_floats(const pd_model *m, int bs, int nsteps);
 
 /* Inspection of the saved trajectory (tests, diagnostics): the hit log behind the planes holds, per (step, env), 32 ints --
@@ -136,7 +136,13 @@ int pd_model_bind_joint_X_p(pd_model *m, const float *joint_X_p_dev, int n_envs)
  * it with one synchronous copy, later calls neither allocate nor synchronise (warm up before capturing a graph).
  * Sizes: bs = 0 and nsteps = 0 are legal (nothing / FK only).  Largest batch of ONE call: bs x bodies < 2^27 and bs < 2^24 (the kernels
  * add 32-bit lane offsets to 64-bit step bases; 10 M Laikago envs) -- a larger bs is refused (non-zero, "batch too large"), never
- * wrapped; the workspace and every tensor may lie past 4 GiB (tests: 1 048 576 envs x 8 steps, 9.8 GB of workspace). */
+ * wrapped; the workspace and every tensor may lie past 4 GiB (tests: 1 048 576 envs x 8 steps, 9.8 GB of workspace).
+ * Forward-only: workspace_dev == NULL with nsteps > 0 is accepted (here and in the two *_traj_loss forward entries).  Such a launch
+ * saves nothing for the adjoint -- no trajectory, no hit log, and on the loss entries no seeds: seed_pos_dev and seed_gt_dev must be
+ * NULL too (a non-NULL one is refused with a message) -- and writes only wp_pos / wp_vel / grf / jaf, plus, on the loss entries,
+ * loss_table / reduced / scale and the FK rows.  Those are bit-identical to a launch with a workspace.  No adjoint can follow it: the
+ * pd_rollout_backward* entries refuse a NULL workspace.  (Laikago: 456 bytes of inputs per env-step instead of 1 624 with the
+ * workspace.)  With nsteps == 0 there is no trajectory either way and NULL keeps meaning "no workspace needed". */
 int pd_rollout_forward(const pd_model *m, int bs, int nsteps, float dt,
                        const float *q_init_dev, const float *qd_init_dev, const float *torques_dev,
                        const float *res_f_dev, const float *refs_dev, const float *target_ke_dev,

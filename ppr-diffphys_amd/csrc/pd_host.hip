@@ -644,17 +644,22 @@ static int rollout_forward_impl(const pd_model *cm, int bs, int nsteps, float dt
     return 0;
   }
   if (!q_init || !qd_init || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia) return fail("null device pointer");
-  if (nsteps > 0 && (!torques || !res_f || !refs || !ws)) return fail("null device pointer");
+  if (nsteps > 0 && (!torques || !res_f || !refs)) return fail("null device pointer");
   if (nframes > 0 && (!wp_pos || !wp_vel)) return fail("null device pointer");
   if (m->xp_env && m->xp_envs != bs) return fail("joint_X_p is bound for " + std::to_string(m->xp_envs) + " envs, rollout has " + std::to_string(bs));
+  // ws == NULL with nsteps > 0: forward-only -- the kernels store no trajectory, hit log or loss seeds (k_rollout_fwd SAVE = false), and
+  // no adjoint can follow.  (A rollout of no steps has no trajectory: it keeps the saving kernel, which writes the seeds of frame 0.)
+  const bool save = ws != nullptr || nsteps == 0;
+  if (!save && tl && (tl->seed_pos || tl->seed_gt))
+    return fail("seed_pos / seed_gt given without a workspace: the seeds serve only an adjoint, which needs the saved trajectory (pass a workspace, or NULL seeds for a forward-only rollout)");
   RolloutArgs a{};
   a.bs = bs; a.nsteps = nsteps; a.nframes = nframes; a.dt = dt;
   a.q_init = q_init; a.qd_init = qd_init; a.torques = torques; a.res_f = res_f; a.refs = refs;
   a.target_ke = target_ke; a.target_kd = target_kd; a.inv_mass = inv_mass; a.inertia = inertia; a.inv_inertia = inv_inertia;
   a.frame_of_step = fos; a.ws = ws; a.wp_pos = wp_pos; a.wp_vel = wp_vel; a.grf = grf; a.jaf = jaf; a.dbg = g_dbg;
-  a.hitlog = (int *)(ws + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb);
+  a.hitlog = ws ? (int *)(ws + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb) : nullptr;
   if (tl) {
-    if (nframes > 0 && (!tl->target || !tl->seed_pos || !tl->table || !tl->reduced || !tl->scale)) return fail("null device pointer (trajectory loss)");
+    if (nframes > 0 && (!tl->target || (save && !tl->seed_pos) || !tl->table || !tl->reduced || !tl->scale)) return fail("null device pointer (trajectory loss)");
     a.loss_target = nframes > 0 ? tl->target : nullptr; a.loss_outseq = tl->outseq; a.loss_rot_ratio = tl->rot_ratio;
     a.loss_seed_pos = tl->seed_pos; a.loss_seed_gt = tl->seed_gt; a.loss_table = tl->table;
   }

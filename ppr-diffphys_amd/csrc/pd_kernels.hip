@@ -552,7 +552,11 @@ PD_DEV float *lds_setup(const PdDevModel &m, unsigned char *smem, SweepTables &T
 // RUNSUM (with CULLW, lane per body): the hit pass sums per body in registers -- launched when four env groups fill the workgroup (see there)
 // GT (global tables): the contact tables stay in global memory (lds_setup<false>) -- instantiated for the models whose tables fit in LDS at
 // no segment width (pd_host.hip build_device); the sweeps read them through the same SweepTables pointers, the arithmetic is the same
-template <int SEGW, int JT, bool SPLIT, bool LOSS = false, bool QUAD = false, bool CULLW = false, bool RUNSUM = false, bool GT = false>
+// SAVE = false (forward-only: a launch with no workspace, pd_rollout_forward* with workspace_dev == NULL): no global store to what only
+// the adjoint reads -- trajectory planes (a.ws), hit log (a.hitlog), loss seeds (a.loss_seed_pos / _gt).  Every LDS access, hand-over
+// and cull stays as it is, so the frame outputs and the loss table are those of the saving kernel, bit for bit.
+template <int SEGW, int JT, bool SPLIT, bool LOSS = false, bool QUAD = false, bool CULLW = false, bool RUNSUM = false, bool GT = false,
+          bool SAVE = true>
 __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK), CULLW ? 3 : 2) void k_rollout_fwd(PdDevModel m, RolloutArgs a) {
   static_assert(!RUNSUM || (CULLW && !QUAD), "run sums in the hit pass: the lane-per-body kernels with the cull wave");
   // TRAJC: the contact wave stores planes 0-2 of the trajectory out of the staged records (round 3 measured this a loss, when that wave's idle
@@ -752,14 +756,14 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
             }
           }
           const int s = seg_slot(tch, sm, log_n);
-          if (tch && env_ok && s < PD_HITLOG - 1) lg[1 + s] = e;
+          if (SAVE && tch && env_ok && s < PD_HITLOG - 1) lg[1 + s] = e;
         }
-        if (l == 0 && env_ok) lg[0] = log_n < PD_HITLOG ? log_n : -1;
+        if (SAVE && l == 0 && env_ok) lg[0] = log_n < PD_HITLOG ? log_n : -1;
         STAMP(11);
       }
       STAMP(12);
       pair_signal(sig + 1, step + 1);  // B: contact wrenches are complete
-      if constexpr (TRAJC) {
+      if constexpr (TRAJC && SAVE) {
         if (is_body) {
           float *tj = a.ws + (size_t)step * (PD_TRAJ_G * 4) * N;
           const unsigned boff16c = (unsigned)((size_t)ec * nb + b) * 16u;
@@ -772,15 +776,15 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
       if (!cull_now) __builtin_amdgcn_s_setprio(0);  // (the cull stays urgent: the next hit pass needs its candidates)
       // the adjoint's log is written off the critical path
       if (redo) {
-        write_hit_log<SEGW>(lg, hits, log_n, env_ok, l);
+        if constexpr (SAVE) write_hit_log<SEGW>(lg, hits, log_n, env_ok, l);
       } else if (lane_owns) {
         const int s = seg_slot(touching, sm, log_n);
-        if (touching && env_ok && s < PD_HITLOG - 1) lg[1 + s] = c_e;
+        if (SAVE && touching && env_ok && s < PD_HITLOG - 1) lg[1 + s] = c_e;
         if (two) {
           const int s2 = seg_slot(touching2, sm, log_n);
-          if (touching2 && env_ok && s2 < PD_HITLOG - 1) lg[1 + s2] = c_e2;
+          if (SAVE && touching2 && env_ok && s2 < PD_HITLOG - 1) lg[1 + s2] = c_e2;
         }
-        if (l == 0 && env_ok) lg[0] = log_n < PD_HITLOG ? log_n : -1;
+        if (SAVE && l == 0 && env_ok) lg[0] = log_n < PD_HITLOG ? log_n : -1;
       }
       if (redo) lane_owns = false;
       if (CULLW && step % PD_SPEC_K == 1 && step + 1 < a.nsteps) {
@@ -948,7 +952,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
         lb = pd_se3::se3_loss_eval<7>(pose, tg, a.loss_rot_ratio, true, gp, gg);
         const float gp_v = qc == 0 ? gp[0] : (qc == 1 ? gp[1] : gp[2]), gp_q = qc == 0 ? gp[3] : (qc == 1 ? gp[4] : (qc == 2 ? gp[5] : gp[6]));
         const float gg_v = qc == 0 ? gg[0] : (qc == 1 ? gg[1] : gg[2]), gg_q = qc == 0 ? gg[3] : (qc == 1 ? gg[4] : (qc == 2 ? gg[5] : gg[6]));
-        if (qbody) {
+        if (SAVE && qbody) {
           float *o = a.loss_seed_pos + ((size_t)cfr * N + qidx) * 7;
           o[3 + qc] = gp_q;
           if (k.isv) o[qc] = gp_v;
@@ -1009,7 +1013,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
       // (every DPP read happens with the whole quad active: values are formed first, selected after, stored under the body mask last)
       const float vx_all = Q_BC0(s.v), vy_all = Q_BC1(s.v);
       const float pl1 = k.isv ? s.w : vx_all, pl2 = k.isv ? s.p : vy_all;
-      {
+      if constexpr (SAVE) {
         float *tj = a.ws + (size_t)step * (PD_TRAJ_G * 4) * N;
         stg(tj, boff_tj, s.r);
         stg(tj + (size_t)4 * N, boff_tj, pl1);
@@ -1072,7 +1076,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
       STAMP(5);
     }
     STAMP_FLUSH(a);
-    if (a.nsteps > 0 && qbody) {
+    if (SAVE && a.nsteps > 0 && qbody) {
       float *tp = a.ws + (size_t)(a.nsteps - 1) * (PD_TRAJ_G * 4) * N;
       stg(tp + (size_t)12 * N, boff_tj, o_p3); stg(tp + (size_t)16 * N, boff_tj, o_p4);
     }
@@ -1204,7 +1208,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
     //                    inside the divergent region the forced scalar does not compile)
     float *tj = a.ws + oj;
     if (!gw) return;
-    if constexpr (!TRAJC) {  // (TRAJC: the contact wave stores these three planes)
+    if constexpr (!TRAJC && SAVE) {  // (TRAJC: the contact wave stores these three planes)
       stg4(tj, boff16, make_float4(cs.r.x, cs.r.y, cs.r.z, cs.r.w));
       stg4(tj + (size_t)4 * N, boff16, make_float4(cs.w.x, cs.w.y, cs.w.z, cs.v.x));
       stg4(tj + (size_t)8 * N, boff16, make_float4(cs.p.x, cs.p.y, cs.p.z, cs.v.y));
@@ -1226,12 +1230,14 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
 #pragma unroll
         for (int k = 0; k < 7; ++k) tg[k] = a.loss_target[ot + k];
         lb = pd_se3::se3_loss_eval<7>(pose, tg, a.loss_rot_ratio, true, gp, gg);
-        float *o = a.loss_seed_pos + ((size_t)cfr * N + idx) * 7;
+        if constexpr (SAVE) {
+          float *o = a.loss_seed_pos + ((size_t)cfr * N + idx) * 7;
 #pragma unroll
-        for (int k = 0; k < 7; ++k) o[k] = gp[k];
-        if (a.loss_seed_gt) {
+          for (int k = 0; k < 7; ++k) o[k] = gp[k];
+          if (a.loss_seed_gt) {
 #pragma unroll
-          for (int k = 0; k < 7; ++k) a.loss_seed_gt[ot + k] = gg[k];
+            for (int k = 0; k < 7; ++k) a.loss_seed_gt[ot + k] = gg[k];
+          }
         }
       }
       // mean over the env's bodies (dp_model.py:777 .mean(-1)): butterfly over the segment's lanes, idle lanes carry 0
@@ -1244,7 +1250,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
     }
   };
   auto spill_wrench_at = [&](float *tj) {  // what the o_* registers hold for a step, to planes 3-4 of that step at tj
-    if (!gw) return;
+    if (!SAVE || !gw) return;
     stg4(tj, boff16, make_float4(o_vz, o_ft.x, o_ft.y, o_ft.z));
     stg4(tj + (size_t)4 * N, boff16, make_float4(o_ff.x, o_ff.y, o_ff.z, __uint_as_float(o_mask)));
   };
@@ -1300,7 +1306,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
         int log_n;
         sweep_contacts<SEGW, 6, PD_W6, true>(m, tabs, c, is_body ? cull[b] : make_float4(0.f, 0.f, 1.f, 0.f), rec, cull, list, hits, slot, facc,
                                              is_body, env_ok, seg, l, nullptr, PD_NO_REPLAY, log_n, contact_hit STAMP_PASS);
-        write_hit_log<SEGW>(lg, hits, log_n, env_ok, l);
+        if constexpr (SAVE) write_hit_log<SEGW>(lg, hits, log_n, env_ok, l);
       } else {
         const SegMask usm = seg_mask<SEGW>(seg);
         int log_n = 0;
@@ -1315,7 +1321,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
             }
           }
           const int sl = seg_slot(tch, usm, log_n);
-          if (tch && env_ok && sl < PD_HITLOG - 1) lg[1 + sl] = u_e;
+          if (SAVE && tch && env_ok && sl < PD_HITLOG - 1) lg[1 + sl] = u_e;
         } else {  // more candidates than lanes: batches out of the LDS list
           for (int j0 = 0; __ballot(j0 < u_nh) != 0ull; j0 += SEGW) {
             const int j = j0 + l;
@@ -1331,10 +1337,10 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
               }
             }
             const int sl = seg_slot(tch, usm, log_n);
-            if (tch && env_ok && sl < PD_HITLOG - 1) lg[1 + sl] = e;
+            if (SAVE && tch && env_ok && sl < PD_HITLOG - 1) lg[1 + sl] = e;
           }
         }
-        if (l == 0 && env_ok) lg[0] = log_n < PD_HITLOG ? log_n : -1;
+        if (SAVE && l == 0 && env_ok) lg[0] = log_n < PD_HITLOG ? log_n : -1;
       }
     }
     STAMP(1);
@@ -2867,53 +2873,63 @@ __global__ __launch_bounds__(PD_FK_BLOCK) void k_seeds_fk(PdDevModel m, SeedsFkA
 // cfg: the host's choice for this launch (pd_args.h: pd_launch_cfg) -- kernel variant, workgroups, threads, LDS bytes
 // GT: the model keeps its contact tables in global memory (m.global_tables) -- the rollout kernels that copy them into LDS have a GT
 // instantiation, the rest (revolute-only adjoint kernels, FK) read no table from LDS and are the same kernels either way
+// The forward variants, each with (SAVE) and without (forward-only) the stores of the trajectory the adjoint reads
+template <int JT, bool GT, bool SAVE>
+static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
+  const dim3 g(cfg.nblocks), t(cfg.threads);
+  const size_t lds = cfg.lds;
+  const bool loss = a.loss_target != nullptr;
+  if (cfg.kernel == PD_KV_FWD_QUAD) {
+    if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
+      if (cfg.roles == 3) {  // with the cull wave
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE>), g, t, lds, st, m, a);
+      } else {
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE>), g, t, lds, st, m, a);
+      }
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }
+  if (cfg.roles == 3) {  // wave-specialised forward with the cull wave (revolute-only robots)
+    if constexpr (JT == PD_JT_REVOLUTE) {
+      if (cfg.groups >= PD_BWAVES) {  // full workgroups: per-body sums in registers (RUNSUM)
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE>), g, t, lds, st, m, a);
+      } else {
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE>), g, t, lds, st, m, a);
+      }
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }
+  // (unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation)
+  if (loss) {  // trajectory loss at the frame states (pd_rollout_forward_traj_loss)
+    if (cfg.kernel != PD_KV_FWD_SPLIT) return hipErrorInvalidValue;  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
+    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE>), g, t, lds, st, m, a);
+  } else if (cfg.kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND)
+    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE>), g, t, lds, st, m, a);
+  else if constexpr (GT)  // (no unsplit instantiation with global tables -- it does not survive the register allocator: a model with its
+    return hipErrorInvalidValue;  // tables in global memory takes the split kernel at every batch size, pd_host.hip launch_cfg)
+  else
+    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE>), g, t, lds, st, m, a);
+  return hipGetLastError();
+}
+
 template <int JT, bool GT>
 static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, const PdLaunchCfg &cfg, hipStream_t st) {
   const dim3 g(cfg.nblocks), t(cfg.threads);
   const size_t lds = cfg.lds;
   switch (kind) {
-    case PD_K_ROLLOUT_FWD:
-      if (cfg.kernel == PD_KV_FWD_QUAD) {
-        if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-          const bool loss = ((const RolloutArgs *)args)->loss_target != nullptr;
-          if (cfg.roles == 3) {  // with the cull wave
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-          } else {
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-          }
-          break;
-        } else {
-          return hipErrorInvalidValue;
-        }
-      }
-      if (cfg.roles == 3) {  // wave-specialised forward with the cull wave (revolute-only robots)
-        if constexpr (JT == PD_JT_REVOLUTE) {
-          const bool loss = ((const RolloutArgs *)args)->loss_target != nullptr;
-          if (cfg.groups >= PD_BWAVES) {  // full workgroups: per-body sums in registers (RUNSUM)
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-          } else {
-            if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-          }
-          break;
-        } else {
-          return hipErrorInvalidValue;
-        }
-      }
-      // (unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation)
-      if (((const RolloutArgs *)args)->loss_target) {  // trajectory loss at the frame states (pd_rollout_forward_traj_loss)
-        if (cfg.kernel != PD_KV_FWD_SPLIT) return hipErrorInvalidValue;  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
-        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-      } else if (cfg.kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND)
-        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-      else if constexpr (GT)  // (no unsplit instantiation with global tables -- it does not survive the register allocator: a model with its
-        return hipErrorInvalidValue;  // tables in global memory takes the split kernel at every batch size, pd_host.hip launch_cfg)
-      else
-        hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND>), g, t, lds, st, m, *(const RolloutArgs *)args);
-      break;
+    case PD_K_ROLLOUT_FWD: {
+      // no workspace: the forward-only kernels (a rollout of no steps saves nothing either way and keeps the saving kernel: pd_host.hip)
+      const RolloutArgs &a = *(const RolloutArgs *)args;
+      return a.ws || a.nsteps == 0 ? launch_fwd<JT, GT, true>(m, a, cfg, st) : launch_fwd<JT, GT, false>(m, a, cfg, st);
+    }
     case PD_K_ROLLOUT_BWD:
       if constexpr (pd_split(JT)) {
         if (cfg.kernel == PD_KV_BWD_QUAD) {
@@ -2949,27 +2965,34 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
   return hipGetLastError();
 }
 
+template <int JT, bool GT, bool SAVE>
+static hipError_t set_lds_fwd(int bytes) {
+  hipError_t e;
+  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if constexpr (!GT)
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  }
+  if constexpr (JT == PD_JT_REVOLUTE) {  // ... with the cull wave
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if constexpr (PD_SEGW == 64) {
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    }
+  }
+  return hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
 template <int JT, bool GT>
 static hipError_t set_lds_gt(int bytes) {
   hipError_t e;
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  if constexpr (!GT)
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  }
-  if constexpr (JT == PD_JT_REVOLUTE) {  // ... with the cull wave
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if constexpr (PD_SEGW == 64) {
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    }
-  }
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if ((e = set_lds_fwd<JT, GT, true>(bytes))) return e;
+  if ((e = set_lds_fwd<JT, GT, false>(bytes))) return e;  // (the forward-only twins)
   if constexpr (pd_split(JT)) {
     if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {

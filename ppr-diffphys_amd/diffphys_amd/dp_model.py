@@ -56,6 +56,13 @@ def _f32c(t):
     return t if (t.dtype is torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
 
 
+def _save_kw(ctx):
+    """Nothing to differentiate (torch.no_grad(), or no input needs a gradient): the rollout runs forward-only -- no trajectory, no
+    loss seeds are saved, the outputs are the same bits.  Otherwise the saving call, unchanged (no extra keyword: a backend object that
+    predates the forward-only mode keeps working on the differentiable path)."""
+    return {} if any(ctx.needs_input_grad) else {"save_trajectory": False}
+
+
 class ForwardKinematics(torch.autograd.Function):
     """rj_q [T,bs,nq], rj_qd [T,bs,nqd], env -> body_q [bs,T,nb,7], body_qd [bs,T,nb,6], body_q_numpy."""
 
@@ -114,7 +121,7 @@ class ForwardWarp(torch.autograd.Function):
         inp = [c(t) for t in (q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass, body_inertia,
                               body_inv_inertia)]
         frame2step = [int(s) for s in frame2step]
-        wp_pos, wp_vel, grf, jaf, ws = dm.rollout_forward(bs, nsteps, self.dt, *inp, frame2step=frame2step)
+        wp_pos, wp_vel, grf, jaf, ws = dm.rollout_forward(bs, nsteps, self.dt, *inp, frame2step=frame2step, **_save_kw(ctx))
         ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
         ctx.save_for_backward(ws, *inp)
         ctx.mass_shape = body_mass.shape
@@ -204,7 +211,7 @@ def _traj_loss_forward(ctx, rollout_inputs, target_position, outseq_idx, self, q
     need_gt = target_position.requires_grad
     fk = None if queried is None else (c(queried[0]), c(queried[1]))
     wp_pos, wp_vel, grf, jaf, ws, tl = dm.rollout_forward_traj_loss(bs, nsteps, self.dt, *inp, frame2step=frame2step, target_pos=tgt,
-                                                                    outseq=outseq, rot_ratio=0.1, want_seed_gt=need_gt, fk=fk)
+                                                                    outseq=outseq, rot_ratio=0.1, want_seed_gt=need_gt, fk=fk, **_save_kw(ctx))
     # What the backward needs of tl -- WITHOUT the Function's outputs: an output kept on ctx closes the cycle ctx -> tensor -> grad_fn ->
     # ctx through C++ references that Python's collector cannot see, and every iteration would then pin its buffers for good (ADVICE r4:
     # ~30 MB per iteration at 4096 envs).  The FK outputs' shapes are all the backward wants of them.

@@ -254,12 +254,12 @@ class DeviceModel:
         return dict(workgroups=out[0], threads_per_wg=out[1], lds_bytes_per_wg=out[2], envs_per_wg=out[3])
 
     # -- rollout ----------------------------------------------------------------
-    def alloc_rollout(self, bs, nsteps, nframes, device, want_forces=True, backward=True):
+    def alloc_rollout(self, bs, nsteps, nframes, device, want_forces=True, backward=True, save_trajectory=True):
         """Workspace, frame outputs and gradient buffers of one (bs, nsteps, nframes) rollout, for callers that reuse them
-        across iterations (pass as ``out=`` to rollout_forward / rollout_backward)."""
+        across iterations (pass as ``out=`` to rollout_forward / rollout_backward).  save_trajectory=False: no workspace (ws None)."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
-        o = dict(ws=e(self.workspace_floats(bs, nsteps)), wp_pos=e(nframes, bs * nb, 7), wp_vel=e(nframes, bs * nb, 6))
+        o = dict(ws=e(self.workspace_floats(bs, nsteps)) if save_trajectory else None, wp_pos=e(nframes, bs * nb, 7), wp_vel=e(nframes, bs * nb, 6))
         if want_forces:
             o.update(grf=e(nframes, bs * nb, 6), jaf=e(nframes, bs * nb, 6))
         if backward:
@@ -279,17 +279,19 @@ class DeviceModel:
         return (ctypes.c_int * max(len(f), 1))(*f), len(f)
 
     def rollout_forward(self, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass,
-                        body_inertia, body_inv_inertia, frame2step, want_forces=True, out=None):
+                        body_inertia, body_inv_inertia, frame2step, want_forces=True, out=None, save_trajectory=True):
         """-> wp_pos [F, bs*nb, 7], wp_vel [F, bs*nb, 6], grf, jaf [F, bs*nb, 6] (or None), workspace.
-        frame2step: host sequence of F distinct ints in 0..nsteps (validated by the library before the launch)."""
+        frame2step: host sequence of F distinct ints in 0..nsteps (validated by the library before the launch).
+        save_trajectory=False: forward-only -- no workspace is allocated or written (workspace None), the outputs are the same bits;
+        no rollout_backward can follow."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         dev = q_init.device
         f2s, nframes = self._f2s(frame2step)
         if out is None:
-            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False)
-        ws, wp_pos, wp_vel = out["ws"], out["wp_pos"], out["wp_vel"]
+            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False, save_trajectory=save_trajectory)
+        ws, wp_pos, wp_vel = out["ws"] if save_trajectory else None, out["wp_pos"], out["wp_vel"]
         grf, jaf = (out["grf"], out["jaf"]) if want_forces else (None, None)
-        p = lambda t, name, n: _dev(t, name, n) if t.numel() else None  # empty tensors have a null data_ptr: the library accepts it
+        p = lambda t, name, n: _dev(t, name, n) if (t is not None and t.numel()) else None  # empty tensors have a null data_ptr: the library accepts it
         _check(lib().pd_rollout_forward(
             self.h, bs, nsteps, float(dt), p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd),
             p(torques, "torques", nsteps * bs * nqd), p(res_f, "res_f", nsteps * bs * nb * 6),
@@ -304,23 +306,26 @@ class DeviceModel:
     # -- rollout with the trajectory loss evaluated at the frame states (C ABI v5) ------------
     def rollout_forward_traj_loss(self, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass,
                                   body_inertia, body_inv_inertia, frame2step, target_pos, outseq=None, rot_ratio=0.1, want_forces=True,
-                                  want_seed_gt=True, out=None, fk=None):
+                                  want_seed_gt=True, out=None, fk=None, save_trajectory=True):
         """``pd_rollout_forward_traj_loss``: rollout_forward plus, in the same rollout launch, se3_loss of every frame pose against
         target_pos [bs, F, nb, 7] and reduce_loss(clip=True) of the per-frame means.  -> (wp_pos, wp_vel, grf, jaf, ws, tl) with tl a dict:
         reduced [4] = (loss_traj, clip threshold, positive entries left, clipped envs), table [bs, F], scale [bs, F], seed_pos
         [F, bs*nb, 7], seed_gt [bs, F, nb, 7] or None.  outseq: bool / uint8 [bs, F] (entries the loss ignores) or None.
         fk = (joint_q [Ff, bs_f, nq], joint_qd [Ff, bs_f, nqd]): the FK of the control reference rides on the reduce_loss launch
-        (``pd_rollout_forward_traj_loss_fk``); tl then also holds fk_body_q [bs_f, Ff, nb, 7] and fk_body_qd [bs_f, Ff, nb, 6]."""
+        (``pd_rollout_forward_traj_loss_fk``); tl then also holds fk_body_q [bs_f, Ff, nb, 7] and fk_body_qd [bs_f, Ff, nb, 6].
+        save_trajectory=False: forward-only -- no workspace and no seeds (ws, seed_pos and seed_gt None; a rollout of no steps keeps its
+        seeds, it has no trajectory to drop), the same bits everywhere else; no rollout_backward_traj_loss can follow."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         dev = q_init.device
         f2s, nframes = self._f2s(frame2step)
         if out is None:
-            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False)
-        ws, wp_pos, wp_vel = out["ws"], out["wp_pos"], out["wp_vel"]
+            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False, save_trajectory=save_trajectory)
+        ws, wp_pos, wp_vel = out["ws"] if save_trajectory else None, out["wp_pos"], out["wp_vel"]
         grf, jaf = (out["grf"], out["jaf"]) if want_forces else (None, None)
         e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
-        tl = dict(reduced=e(4), table=e(bs, nframes), scale=e(bs, nframes), seed_pos=e(nframes, bs * nb, 7),
-                  seed_gt=e(bs, nframes, nb, 7) if want_seed_gt else None)
+        seeds = save_trajectory or nsteps == 0
+        tl = dict(reduced=e(4), table=e(bs, nframes), scale=e(bs, nframes), seed_pos=e(nframes, bs * nb, 7) if seeds else None,
+                  seed_gt=e(bs, nframes, nb, 7) if (want_seed_gt and seeds) else None)
         if outseq is not None:
             if not (outseq.is_cuda and outseq.dtype in (torch.bool, torch.uint8) and outseq.is_contiguous() and outseq.numel() == bs * nframes):
                 raise ValueError("outseq must be a contiguous bool / uint8 GPU tensor of bs * nframes entries")
