@@ -142,7 +142,18 @@ int pd_model_bind_joint_X_p(pd_model *m, const float *joint_X_p_dev, int n_envs)
  * NULL too (a non-NULL one is refused with a message) -- and writes only wp_pos / wp_vel / grf / jaf, plus, on the loss entries,
  * loss_table / reduced / scale and the FK rows.  Those are bit-identical to a launch with a workspace.  No adjoint can follow it: the
  * pd_rollout_backward* entries refuse a NULL workspace.  (Laikago: 456 bytes of inputs per env-step instead of 1 624 with the
- * workspace.)  With nsteps == 0 there is no trajectory either way and NULL keeps meaning "no workspace needed". */
+ * workspace.)  With nsteps == 0 there is no trajectory either way and NULL keeps meaning "no workspace needed".
+ * Resumed: qd_init_dev == NULL (with bs > 0 and q_init_dev non-NULL) starts the rollout from a BODY state instead of joint
+ * coordinates.  q_init_dev is then [bs*nb][13] = (p[3], q[4] xyzw, w[3], v[3]) per body: the body-origin pose and the twist, exactly
+ * the numbers of a wp_pos row followed by a wp_vel row.  The 13 floats are used as they are -- no FK, the quaternion is not
+ * re-normalised -- so the rows of an earlier rollout's frame at its state nsteps continue that rollout bit for bit; a frame at step
+ * 0 returns the state bit for bit.  Frames, workspace or none, forces: as before.  pd_rollout_forward / pd_rollout_backward only: the
+ * *_traj_loss entries refuse a NULL qd_init_dev with a message.  The adjoint of such a rollout: pd_rollout_backward with
+ * qd_init_dev == NULL and the same state in q_init_dev; g_q_init_dev then receives the gradient of the body state, [bs*nb][13], and
+ * g_qd_init_dev must be NULL (a non-NULL one is refused with a message, nothing is written).  That state gradient is stored RAW, without
+ * the remove_nan every other gradient gets: it is the adjoint that flows on into the rollout that produced the state -- as the seed
+ * (adj_pos / adj_vel rows) of that rollout's frame at its state nsteps -- and a single launch does not scrub it between steps either.
+ * These argument combinations were refused ("null device pointer") before; no symbol or signature changed, the version stays 9. */
 int pd_rollout_forward(const pd_model *m, int bs, int nsteps, float dt,
                        const float *q_init_dev, const float *qd_init_dev, const float *torques_dev,
                        const float *res_f_dev, const float *refs_dev, const float *target_ke_dev,

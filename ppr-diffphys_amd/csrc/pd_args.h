@@ -75,6 +75,11 @@ struct RolloutArgs {
   int bs, nsteps, nframes;
   float dt;
   const float *q_init, *qd_init, *torques, *res_f, *refs, *target_ke, *target_kd, *inv_mass, *inertia, *inv_inertia;
+  // resumed rollout (pd_rollout_forward / pd_rollout_backward with qd_init == NULL): state 0 is the body state state0 [bs*nb][13] =
+  // (p, q xyzw, w, v) instead of eval_fk(q_init, qd_init), which are then null; the adjoint stores the gradient of that state to
+  // g_state0, raw, instead of running the FK adjoint (g_q_init / g_qd_init are then null)
+  const float *state0;
+  float *g_state0;
   const int *frame_of_step;
   float *ws;                           // workspace: saved trajectory [T][5 planes][N] float4, N = bs*nb, then the hit log
   float *wp_pos, *wp_vel, *grf, *jaf;  // forward outputs (grf/jaf may be null)

@@ -215,6 +215,15 @@ PD_DEV void stage_record(float *rec, int b, const BodyState &s, v3 com) {  // FK
   r[13] = rc.x; r[14] = rc.y; r[15] = rc.z;
 }
 
+// State 0 of a resumed rollout: row i of a body-state tensor [bs*nb][13] = (p, q xyzw, w, v), the numbers of a frame's wp_pos row
+// followed by its wp_vel row, taken as they are.
+PD_DEV BodyState load_state0(const float *state0, size_t i) {
+  const float *r = state0 + i * PD_ADJ;
+  BodyState s;
+  s.p = ld3(r); s.r = ld4(r + 3); s.w = ld3(r + 7); s.v = ld3(r + 10);
+  return s;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Forward kinematics of one joint (warp.sim.articulation.eval_fk).
 // jq / jqd point at this joint's coordinates; parent state comes from the LDS record.

@@ -643,7 +643,11 @@ static int rollout_forward_impl(const pd_model *cm, int bs, int nsteps, float dt
     if (tl && tl->reduced) return reduce_launch(m, 0, nframes, tl->table, tl->reduced, tl->scale, fk, (hipStream_t)stream);
     return 0;
   }
-  if (!q_init || !qd_init || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia) return fail("null device pointer");
+  // qd_init == NULL: resumed rollout -- q_init is then the body state [bs*nb][13] that state 0 is taken from (k_rollout_fwd: a.state0)
+  const bool resumed = q_init && !qd_init;
+  if (resumed && tl)
+    return fail("qd_init is NULL: a rollout resumed from a body state is pd_rollout_forward's alone, the trajectory-loss entries start from (q_init, qd_init)");
+  if (!q_init || (!qd_init && !resumed) || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia) return fail("null device pointer");
   if (nsteps > 0 && (!torques || !res_f || !refs)) return fail("null device pointer");
   if (nframes > 0 && (!wp_pos || !wp_vel)) return fail("null device pointer");
   if (m->xp_env && m->xp_envs != bs) return fail("joint_X_p is bound for " + std::to_string(m->xp_envs) + " envs, rollout has " + std::to_string(bs));
@@ -654,7 +658,8 @@ static int rollout_forward_impl(const pd_model *cm, int bs, int nsteps, float dt
     return fail("seed_pos / seed_gt given without a workspace: the seeds serve only an adjoint, which needs the saved trajectory (pass a workspace, or NULL seeds for a forward-only rollout)");
   RolloutArgs a{};
   a.bs = bs; a.nsteps = nsteps; a.nframes = nframes; a.dt = dt;
-  a.q_init = q_init; a.qd_init = qd_init; a.torques = torques; a.res_f = res_f; a.refs = refs;
+  a.q_init = resumed ? nullptr : q_init; a.qd_init = qd_init; a.state0 = resumed ? q_init : nullptr;
+  a.torques = torques; a.res_f = res_f; a.refs = refs;
   a.target_ke = target_ke; a.target_kd = target_kd; a.inv_mass = inv_mass; a.inertia = inertia; a.inv_inertia = inv_inertia;
   a.frame_of_step = fos; a.ws = ws; a.wp_pos = wp_pos; a.wp_vel = wp_vel; a.grf = grf; a.jaf = jaf; a.dbg = g_dbg;
   a.hitlog = ws ? (int *)(ws + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb) : nullptr;
@@ -724,8 +729,15 @@ static int rollout_backward_impl(const pd_model *cm, int bs, int nsteps, float d
     }
     return 0;
   }
-  if (!q_init || !qd_init || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia || !g_q_init || !g_qd_init || !g_ke ||
-      !g_kd || !g_inv_mass || !g_inertia || !g_inv_inertia)
+  // qd_init == NULL: adjoint of a resumed rollout -- q_init is the body state [bs*nb][13], g_q_init receives its gradient (raw: it is
+  // the adjoint that flows on into the rollout before), and there is no g_qd_init
+  const bool resumed = q_init && !qd_init;
+  if (resumed && (tl || fk))
+    return fail("qd_init is NULL: a rollout resumed from a body state is pd_rollout_backward's alone, the trajectory-loss entries start from (q_init, qd_init)");
+  if (resumed && g_qd_init)
+    return fail("g_qd_init given with a NULL qd_init: a resumed rollout has one state gradient, g_q_init [bs*nb][13] (pass a NULL g_qd_init)");
+  if (!q_init || (!qd_init && !resumed) || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia || !g_q_init ||
+      (!g_qd_init && !resumed) || !g_ke || !g_kd || !g_inv_mass || !g_inertia || !g_inv_inertia)
     return fail("null device pointer");
   if (nsteps > 0 && (!torques || !refs || !ws || !g_torques || !g_res_f || !g_refs)) return fail("null device pointer");
   if (!tl && nframes > 0 && (!adj_pos || !adj_vel)) return fail("null device pointer");
@@ -747,10 +759,12 @@ static int rollout_backward_impl(const pd_model *cm, int bs, int nsteps, float d
     if (pd_traj_seeds_launch(bs, m->nb, nframes, tl->seed_pos, tl->scale, tl->gain, adj_pos, adj_vel, tl->work, (hipStream_t)stream)) return fail("seed launch failed");
     adj_pos = tl->work; adj_vel = tl->work + (size_t)nframes * bs * m->nb * 7;
   }
-  a.q_init = q_init; a.qd_init = qd_init; a.torques = torques; a.refs = refs;
+  a.q_init = resumed ? nullptr : q_init; a.qd_init = qd_init; a.state0 = resumed ? q_init : nullptr;
+  a.torques = torques; a.refs = refs;
   a.target_ke = target_ke; a.target_kd = target_kd; a.inv_mass = inv_mass; a.inertia = inertia; a.inv_inertia = inv_inertia;
   a.frame_of_step = fos; a.ws = const_cast<float *>(ws); a.adj_pos = adj_pos; a.adj_vel = adj_vel;
-  a.g_q_init = g_q_init; a.g_qd_init = g_qd_init; a.g_torques = g_torques; a.g_res_f = g_res_f; a.g_refs = g_refs;
+  a.g_q_init = resumed ? nullptr : g_q_init; a.g_qd_init = g_qd_init; a.g_state0 = resumed ? g_q_init : nullptr;
+  a.g_torques = g_torques; a.g_res_f = g_res_f; a.g_refs = g_refs;
   a.g_ke = g_ke; a.g_kd = g_kd; a.g_inv_mass = g_inv_mass; a.g_inertia = g_inertia; a.g_inv_inertia = g_inv_inertia; a.dbg = g_dbg;
   a.hitlog = (int *)(const_cast<float *>(ws) + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb);
   hipStream_t st = (hipStream_t)stream;

@@ -877,6 +877,15 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
     }
     // ---- eval_fk (dp_model.py:1204) in the lane-per-body layout (lanes 0 .. nb-1), once; the records it stages are then read back
     // component-wise
+    if (a.state0) {  // resumed rollout: state 0 is given as a body state, used as it is (no FK, the quaternion is not re-normalised)
+      if (is_body) {
+        const BodyState s0 = load_state0(a.state0, (size_t)ec * nb + b);
+        float Rm0[9];
+        rotm(s0.r, Rm0);
+        stage_record(rec, cull, b, s0, mat_vec(Rm0, c.com), Rm0);
+      }
+      WAVE_SYNC();
+    } else
     for (int d = 0; d <= m.max_depth; ++d) {
       if (is_body && c.depth == d) {
         BodyState s0 = fk_joint<JT>(c, a.q_init + (size_t)ec * m.nq + c.qstart, a.qd_init + (size_t)ec * m.nqd + c.qdstart, rec);
@@ -1150,9 +1159,12 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
   // bound and sum run beside its predecessor's for one step: (margin98, sunk) is the pair in use, (margin98_n, sunk_n) the one staged
   constexpr int SPEC_STEPS = CULLW ? PD_SPEC_K + 1 : PD_SPEC_K;
   [[maybe_unused]] float margin98_n = __builtin_inff(), sunk_n = 0.f;
-  for (int d = 0; d <= m.max_depth; ++d) {
-    if (wr && c.depth == d) {
-      s = fk_joint<JT>(c, a.q_init + (size_t)ec * m.nq + c.qstart, a.qd_init + (size_t)ec * m.nqd + c.qdstart, rec);
+  // (resumed rollout, a.state0: state 0 is given as a body state and used as it is -- every body is then its own level, one pass)
+  const int fk_levels = a.state0 ? 0 : m.max_depth;
+  for (int d = 0; d <= fk_levels; ++d) {
+    if (wr && (a.state0 || c.depth == d)) {
+      if (a.state0) s = load_state0(a.state0, idx);
+      else s = fk_joint<JT>(c, a.q_init + (size_t)ec * m.nq + c.qstart, a.qd_init + (size_t)ec * m.nqd + c.qdstart, rec);
       rotm(s.r, Rm);
       rc = mat_vec(Rm, c.com);
       float4 cv = stage_record(rec, cull, b, s, rc, Rm);
@@ -1985,12 +1997,14 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     float *const rec0 = qgen + 4 * nb;
     WAVE_SYNC();
     if (qbody) {
-      float *d = cacc + bb * PD_ADJ;
+      // (resumed rollout: the adjoint of the given state 0 goes out RAW -- it flows on into the rollout that produced the state -- and
+      // there is no FK to differentiate)
+      float *d = a.g_state0 ? a.g_state0 + qidx * PD_ADJ : cacc + bb * PD_ADJ;
       d[3 + qc] = gn.r;
       if (k.isv) { d[qc] = gn.p; d[7 + qc] = gn.w; d[10 + qc] = gn.v; }
     }
     WAVE_SYNC();
-    {
+    if (!a.g_state0) {
       BodyAdj gs = adj_zero();
       if (is_body) adj_add_from(gs, cacc + b * PD_ADJ);
       if (a.nsteps == 0) {
@@ -2224,8 +2238,12 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     }
   }
   // ---- adjoint of eval_fk: rec holds state 0 (staged in the last loop iteration)
+  // (resumed rollout: the adjoint of the given state 0 goes out RAW -- it flows on into the rollout that produced the state -- and there
+  // is no FK to differentiate)
+  if (a.g_state0 && is_body) adj_store(a.g_state0 + idx * PD_ADJ, gn);
+  const int fk_levels = a.g_state0 ? -1 : m.max_depth;
   if (a.nsteps == 0) {
-    for (int d = 0; d <= m.max_depth; ++d) {  // nothing staged yet: rebuild state 0
+    for (int d = 0; d <= fk_levels; ++d) {  // nothing staged yet: rebuild state 0
       if (is_body && c.depth == d) {
         s = fk_joint<JT>(c, a.q_init + (size_t)ec * m.nq + c.qstart, a.qd_init + (size_t)ec * m.nqd + c.qdstart, rec);
         stage_record(rec, b, s, c.com);
@@ -2233,7 +2251,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
       WAVE_SYNC();
     }
   }
-  for (int d = m.max_depth; d >= 0; --d) {
+  for (int d = fk_levels; d >= 0; --d) {
     if (is_body && c.depth == d) {
       for (int k = 0; k < m.max_children; ++k) {
         int cid = (int)((c.children >> (8 * k)) & 0xffull);
@@ -2744,9 +2762,12 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
     }
   }
   // ---- adjoint of eval_fk: rec holds state 0 (staged in the last loop iteration); the J wave is past its last use of cslot
+  // (resumed rollout: the adjoint of the given state 0 goes out RAW, and there is no FK to differentiate -- see k_rollout_bwd)
+  if (a.g_state0 && is_body) adj_store(a.g_state0 + idx * PD_ADJ, gn);
+  const int fk_levels = a.g_state0 ? -1 : m.max_depth;
   c = load_body_const(m, b, ec);
   if (a.nsteps == 0) {
-    for (int d = 0; d <= m.max_depth; ++d) {  // nothing staged yet: rebuild state 0
+    for (int d = 0; d <= fk_levels; ++d) {  // nothing staged yet: rebuild state 0
       if (is_body && c.depth == d) {
         s = fk_joint<JT>(c, a.q_init + (size_t)ec * m.nq + c.qstart, a.qd_init + (size_t)ec * m.nqd + c.qdstart, rec);
         stage_record(rec, b, s, c.com);
@@ -2755,7 +2776,7 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
     }
   }
   WAVE_SYNC();
-  for (int d = m.max_depth; d >= 0; --d) {
+  for (int d = fk_levels; d >= 0; --d) {
     if (is_body && c.depth == d) {
       for (int k = 0; k < m.max_children; ++k) {
         int cid = (int)((c.children >> (8 * k)) & 0xffull);

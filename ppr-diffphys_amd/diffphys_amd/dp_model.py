@@ -101,12 +101,135 @@ class ForwardKinematics(torch.autograd.Function):
         return post(gq, dm.nq), post(gqd, dm.nqd), None
 
 
+def checkpoint_plan(nsteps, frame2step, K):
+    """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
+    divide nsteps).  Pure; -> (launch_frames, segments).
+
+    launch_frames: the frame list of the ONE forward-only launch -- the caller's ``frame2step`` in its order, then the boundary steps
+    K, 2K, ... (< nsteps) that are not frames already: no step twice, so the library's validation passes.
+
+    segments: one (start, end, local_frame2step, caller_indices, has_carry) per segment, first to last; the backward walks it in reverse.
+    The segment is the rollout of steps [start, end) from state ``start``.  ``caller_indices`` are the positions in ``frame2step`` of the
+    frames it seeds -- those with start <= step < end, and step == nsteps in the last segment -- and ``local_frame2step`` their steps
+    relative to ``start``, in the caller's order; with ``has_carry`` (every segment but the last) one more local frame follows, at
+    state end - start, whose seed is the state adjoint handed back by the segment after.  A caller frame ON a boundary step belongs to
+    the later segment, as its state 0: it is seeded once.  K >= nsteps gives one segment, the caller's own call."""
+    nsteps, K = int(nsteps), int(K)
+    frames = [int(s) for s in frame2step]
+    if K < 1:
+        raise ValueError("checkpoint_plan: K = %d, a segment has at least one step" % K)
+    if nsteps < 0 or any(s < 0 or s > nsteps for s in frames) or len(set(frames)) != len(frames):
+        raise ValueError("checkpoint_plan: frame2step must hold distinct steps in 0..%d" % nsteps)
+    have = set(frames)
+    launch_frames = frames + [b for b in range(K, nsteps, K) if b not in have]
+    segments = []
+    for start in range(0, max(nsteps, 1), K):
+        end = min(start + K, nsteps)
+        has_carry = end < nsteps
+        idx = [i for i, s in enumerate(frames) if start <= s < end or (not has_carry and s == end)]
+        local = [frames[i] - start for i in idx] + ([end - start] if has_carry else [])
+        segments.append((start, end, local, idx, has_carry))
+    return launch_frames, segments
+
+
+def checkpoint_steps_for(nsteps, bytes_per_step, bytes_per_boundary, budget_bytes):
+    """The largest segment length K in 1..nsteps whose checkpointed adjoint fits ``budget_bytes``: a K-step workspace
+    (K x bytes_per_step; ``4 * dm.workspace_floats(bs, 1)``) plus ceil(nsteps / K) boundary states (bytes_per_boundary each;
+    ``4 * 13 * bs * nb``).  Pure.  ValueError, naming the shortfall, when no K fits -- K = 1 included."""
+    nsteps = int(nsteps)
+    if nsteps < 1:
+        raise ValueError("checkpoint_steps_for: nsteps = %d, nothing to segment" % nsteps)
+    need = lambda K: K * int(bytes_per_step) + -(-nsteps // K) * int(bytes_per_boundary)
+    for K in range(nsteps, 0, -1):
+        if need(K) <= budget_bytes:
+            return K
+    best = min(range(1, nsteps + 1), key=need)
+    raise ValueError("checkpoint_steps_for: %d bytes short -- K = 1 needs %d bytes, the cheapest segment length (K = %d) needs %d, the budget is %d"
+                     % (need(best) - budget_bytes, need(1), best, need(best), budget_bytes))
+
+
+def _remove_nan(g):
+    """remove_nan of the boundary (NaN -> 0, +-inf kept) as a torch op: for the one gradient the adjoint kernel hands back raw."""
+    return torch.where(g != g, torch.zeros_like(g), g)
+
+
+_SUMMED = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")  # gradients that are sums over the steps
+
+
+def _checkpoint_forward(dm, bs, nsteps, dt, inp, frame2step, K):
+    """Forward of the checkpointed ForwardWarp: ONE forward-only launch whose frames are the caller's plus the segment boundaries.
+    -> the caller's (wp_pos, wp_vel, grf, jaf), and the boundary states [segments - 1, bs*nb, 13] kept for the backward."""
+    launch_frames, segments = checkpoint_plan(nsteps, frame2step, K)
+    F = len(frame2step)
+    pos, vel, grf, jaf, _ = dm.rollout_forward(bs, nsteps, dt, *inp, frame2step=launch_frames, save_trajectory=False)
+    row = {s: f for f, s in enumerate(launch_frames)}
+    states = torch.empty(len(segments) - 1, bs * dm.nb, 13, dtype=torch.float32, device=pos.device)
+    for j, seg in enumerate(segments[1:]):
+        states[j, :, :7] = pos[row[seg[0]]]
+        states[j, :, 7:] = vel[row[seg[0]]]
+    if len(launch_frames) > F:  # the caller's frames as tensors of their own: the boundary rows are not kept alive behind them
+        pos, vel, grf, jaf = pos[:F].clone(), vel[:F].clone(), grf[:F].clone(), jaf[:F].clone()
+    return pos, vel, grf, jaf, states
+
+
+def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos, adj_vel):
+    """Backward of the checkpointed ForwardWarp -> the gradient dict of DeviceModel.rollout_backward.  Segments last to first: a saving
+    forward of the segment from its boundary state into the one K-step workspace, then its adjoint, seeded with the caller's seeds
+    inside the segment and the state adjoint carried from the segment after (raw).  No host synchronisation."""
+    q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = inp
+    _, segments = checkpoint_plan(nsteps, frame2step, K)
+    dev, N = torques.device, bs * dm.nb
+    g = dm._alloc_grads(bs, nsteps, dev)
+    tmp = {k: torch.empty_like(g[k]) for k in _SUMMED}
+    ws = torch.empty(dm.workspace_floats(bs, min(K, nsteps)), dtype=torch.float32, device=dev)
+    carry = torch.empty(N, 13, dtype=torch.float32, device=dev) if len(segments) > 1 else None
+    none7, none6 = torch.empty(0, N, 7, dtype=torch.float32, device=dev), torch.empty(0, N, 6, dtype=torch.float32, device=dev)
+    for i in range(len(segments) - 1, -1, -1):
+        start, end, local, idx, has_carry = segments[i]
+        n = end - start
+        seg_ws = ws[: dm.workspace_floats(bs, n)]
+        ctl = (torques[start:end], res_f[start:end], refs[start:end])
+        init = dict(state0=states[i - 1]) if i > 0 else {}
+        q0 = (None, None) if i > 0 else (q_init, qd_init)
+        dm.rollout_forward(bs, n, dt, *q0, *ctl, ke, kd, inv_m, inertia, inv_inertia, frame2step=[], want_forces=False,
+                           out=dict(ws=seg_ws, wp_pos=none7, wp_vel=none6), **init)
+        contiguous = idx == list(range(idx[0], idx[0] + len(idx))) if idx else True
+        if not has_carry and contiguous:
+            sp, sv = (adj_pos[idx[0]: idx[0] + len(idx)], adj_vel[idx[0]: idx[0] + len(idx)]) if idx else (none7, none6)
+        else:
+            sp = torch.cat([adj_pos[j: j + 1] for j in idx] + ([carry[None, :, :7]] if has_carry else []))
+            sv = torch.cat([adj_vel[j: j + 1] for j in idx] + ([carry[None, :, 7:]] if has_carry else []))
+        first = i == len(segments) - 1  # the first segment processed writes the sums' accumulators themselves
+        gs = {k: (g[k] if first else tmp[k]) for k in _SUMMED}
+        gs.update(torques=g["torques"][start:end], res_f=g["res_f"][start:end], refs=g["refs"][start:end])
+        if i > 0:
+            gs["state0"] = carry
+        else:
+            gs.update(q_init=g["q_init"], qd_init=g["qd_init"])
+        dm.rollout_backward(bs, n, dt, *q0, ctl[0], ctl[2], ke, kd, inv_m, inertia, inv_inertia, local, seg_ws, sp, sv,
+                            out=dict(grads=gs), **init)
+        if not first:
+            for k in _SUMMED:
+                g[k].add_(tmp[k])
+    return g
+
+
 class ForwardWarp(torch.autograd.Function):
     """ForwardWarp.apply(q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_mass,
     body_inv_mass, body_inertia, body_inv_inertia, self) -> (wp_pos [F,bs*nb,7], wp_vel [F,bs*nb,6]).
 
-    Read from ``self``: ``env``, ``steps_idx``, ``frame2step``, ``dt``, ``num_envs``.
-    Written to ``self``: ``grfs``, ``jafs`` (lists of F tensors [bs*nb,6]), ``sim_trajs`` (F numpy [nb,7], env 0)."""
+    Read from ``self``: ``env``, ``steps_idx``, ``frame2step``, ``dt``, ``num_envs``; optionally ``checkpoint_steps``.
+    Written to ``self``: ``grfs``, ``jafs`` (lists of F tensors [bs*nb,6]), ``sim_trajs`` (F numpy [nb,7], env 0).
+
+    ``self.checkpoint_steps = K`` (absent, None, 0 or K >= nsteps: the single-launch path, unchanged) selects the CHECKPOINTED adjoint
+    when a gradient is wanted: the forward is one forward-only launch that also emits the states at steps K, 2K, ...; the backward
+    re-runs one K-step segment at a time, last to first, into one K-step workspace and carries the state adjoint from segment to segment
+    (:func:`checkpoint_plan`).  Memory: K instead of nsteps steps of workspace, plus 52 bytes per body per boundary.  Outputs, per-step
+    gradients (torques, res_f, refs) and the q_init / qd_init gradients are the single launch's bits; the five gradients that are sums
+    over the steps (target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia) are added up per segment, last segment first,
+    in fp32 -- a re-associated sum.  NaN policy, a stated difference: each segment scrubs what it stores (NaN -> 0) and the carried
+    adjoint is raw, so an env whose adjoint turns NaN gets zero per-step gradients in every earlier segment, as in the single launch;
+    but what the segments processed BEFORE the NaN arose added to the five sums stays there, where the single launch returns 0."""
 
     @staticmethod
     def forward(ctx, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_mass, body_inv_mass, body_inertia,
@@ -121,7 +244,12 @@ class ForwardWarp(torch.autograd.Function):
         inp = [c(t) for t in (q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass, body_inertia,
                               body_inv_inertia)]
         frame2step = [int(s) for s in frame2step]
-        wp_pos, wp_vel, grf, jaf, ws = dm.rollout_forward(bs, nsteps, self.dt, *inp, frame2step=frame2step, **_save_kw(ctx))
+        K = int(getattr(self, "checkpoint_steps", None) or 0)
+        ctx.checkpoint = K if (0 < K < nsteps and any(ctx.needs_input_grad)) else 0
+        if ctx.checkpoint:
+            wp_pos, wp_vel, grf, jaf, ws = _checkpoint_forward(dm, bs, nsteps, float(self.dt), inp, frame2step, K)  # (ws: the boundary states)
+        else:
+            wp_pos, wp_vel, grf, jaf, ws = dm.rollout_forward(bs, nsteps, self.dt, *inp, frame2step=frame2step, **_save_kw(ctx))
         ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
         ctx.save_for_backward(ws, *inp)
         ctx.mass_shape = body_mass.shape
@@ -137,14 +265,64 @@ class ForwardWarp(torch.autograd.Function):
     def backward(ctx, adj_body_qs, adj_body_qd):
         ws, q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = ctx.saved_tensors
         bs, nsteps, dt, frame2step = ctx.meta
-        g = ctx.dm.rollout_backward(bs, nsteps, dt, q_init, qd_init, torques, refs, ke, kd, inv_m, inertia, inv_inertia,
-                                    frame2step, ws, adj_body_qs.to(torch.float32).contiguous(),
-                                    adj_body_qd.to(torch.float32).contiguous())
+        if ctx.checkpoint:
+            g = _checkpoint_backward(ctx.dm, bs, nsteps, dt, (q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia),
+                                     frame2step, ctx.checkpoint, ws, adj_body_qs.to(torch.float32).contiguous(),
+                                     adj_body_qd.to(torch.float32).contiguous())
+        else:
+            g = ctx.dm.rollout_backward(bs, nsteps, dt, q_init, qd_init, torques, refs, ke, kd, inv_m, inertia, inv_inertia,
+                                        frame2step, ws, adj_body_qs.to(torch.float32).contiguous(),
+                                        adj_body_qd.to(torch.float32).contiguous())
         # remove_nan (dp_model.py:1294-1384: NaN -> 0 on every returned gradient, inf kept) is applied by the adjoint kernel where it
         # stores the gradients (pd_rollout_backward): no pass over the tensors here
         return (g["q_init"], g["qd_init"], g["torques"].view_as(torques), g["res_f"].view_as(res_f),
                 g["refs"].view_as(refs), g["target_ke"], g["target_kd"],
-                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=ws.device), g["body_inv_mass"],
+                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=torques.device), g["body_inv_mass"],
+                g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
+
+
+class ForwardWarpState(torch.autograd.Function):
+    """ForwardWarp started from a BODY state instead of joint coordinates:
+
+        wp_pos, wp_vel = ForwardWarpState.apply(body_q0 [bs*nb,7], body_qd0 [bs*nb,6], torques, res_f, refs, target_ke, target_kd,
+                                                body_mass, body_inv_mass, body_inertia, body_inv_inertia, self)
+
+    State 0 is (body_q0, body_qd0) as given -- the rows of a frame's wp_pos / wp_vel; no FK, no re-normalisation -- so a window whose
+    inputs are the ``wp_pos[-1]`` / ``wp_vel[-1]`` of the window before (its frame at state nsteps) continues that rollout bit for
+    bit, and ordinary autograd chains the windows' adjoints.  Reads and writes ``self`` as ForwardWarp (``checkpoint_steps`` is not
+    read); forward-only when nothing needs a gradient.  The gradients of body_q0 / body_qd0 leave the kernel raw and get the
+    boundary's remove_nan (NaN -> 0, +-inf kept) here, by a torch op on those two small tensors."""
+
+    @staticmethod
+    def forward(ctx, body_q0, body_qd0, torques, res_f, refs, target_ke, target_kd, body_mass, body_inv_mass, body_inertia,
+                body_inv_inertia, self):
+        dm = hip_backend.device_model(self.env)
+        bs, nsteps = int(self.num_envs), len(self.steps_idx)
+        frame2step = [int(s) for s in self.frame2step]
+        c = _f32c
+        state0 = torch.cat([c(body_q0).reshape(-1, 7), c(body_qd0).reshape(-1, 6)], dim=1)
+        inp = [c(t) for t in (torques, res_f, refs, target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia)]
+        wp_pos, wp_vel, grf, jaf, ws = dm.rollout_forward(bs, nsteps, self.dt, None, None, *inp, frame2step=frame2step, state0=state0,
+                                                          **_save_kw(ctx))
+        ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
+        ctx.save_for_backward(ws, state0, *inp)
+        ctx.mass_shape, ctx.q0_shape, ctx.qd0_shape = body_mass.shape, body_q0.shape, body_qd0.shape
+        has_f = [f for f, s in enumerate(frame2step) if s < nsteps]
+        self.grfs = [grf[f] for f in has_f]
+        self.jafs = [jaf[f] for f in has_f]
+        self.sim_trajs = HostFrames(wp_pos[:, : dm.nb])
+        return wp_pos, wp_vel
+
+    @staticmethod
+    def backward(ctx, adj_body_qs, adj_body_qd):
+        ws, state0, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = ctx.saved_tensors
+        bs, nsteps, dt, frame2step = ctx.meta
+        g = ctx.dm.rollout_backward(bs, nsteps, dt, None, None, torques, refs, ke, kd, inv_m, inertia, inv_inertia, frame2step, ws,
+                                    adj_body_qs.to(torch.float32).contiguous(), adj_body_qd.to(torch.float32).contiguous(), state0=state0)
+        g0 = _remove_nan(g["state0"])
+        return (g0[:, :7].reshape(ctx.q0_shape), g0[:, 7:].reshape(ctx.qd0_shape), g["torques"].view_as(torques), g["res_f"].view_as(res_f),
+                g["refs"].view_as(refs), g["target_ke"], g["target_kd"],
+                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=torques.device), g["body_inv_mass"],
                 g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
 
 

@@ -266,12 +266,24 @@ class DeviceModel:
             o["grads"] = self._alloc_grads(bs, nsteps, device)
         return o
 
-    def _alloc_grads(self, bs, nsteps, device):
+    def _alloc_grads(self, bs, nsteps, device, resumed=False):
+        """resumed: the gradient buffers of a rollout that started from a body state -- ``state0`` [bs*nb, 13] in place of q_init / qd_init."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
-        return dict(q_init=e(bs * nq), qd_init=e(bs * nqd), torques=e(nsteps, bs * nqd), res_f=e(nsteps, bs * nb, 6),
-                    refs=e(nsteps, bs * nqd), target_ke=e(bs * nqd), target_kd=e(bs * nqd), body_inv_mass=e(bs * nb),
-                    body_inertia=e(bs * nb, 3, 3), body_inv_inertia=e(bs * nb, 3, 3))
+        g = dict(state0=e(bs * nb, 13)) if resumed else dict(q_init=e(bs * nq), qd_init=e(bs * nqd))
+        g.update(torques=e(nsteps, bs * nqd), res_f=e(nsteps, bs * nb, 6),
+                 refs=e(nsteps, bs * nqd), target_ke=e(bs * nqd), target_kd=e(bs * nqd), body_inv_mass=e(bs * nb),
+                 body_inertia=e(bs * nb, 3, 3), body_inv_inertia=e(bs * nb, 3, 3))
+        return g
+
+    @staticmethod
+    def _state0(state0):
+        """A body state as ONE [bs*nb, 13] tensor: given so, or as the pair (body_q [bs*nb, 7], body_qd [bs*nb, 6]) -- a frame's wp_pos and
+        wp_vel rows -- which is concatenated."""
+        if isinstance(state0, (tuple, list)):
+            body_q, body_qd = state0
+            state0 = torch.cat([body_q.reshape(-1, 7), body_qd.reshape(-1, 6)], dim=1)
+        return state0
 
     @staticmethod
     def _f2s(frame2step):
@@ -279,13 +291,23 @@ class DeviceModel:
         return (ctypes.c_int * max(len(f), 1))(*f), len(f)
 
     def rollout_forward(self, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass,
-                        body_inertia, body_inv_inertia, frame2step, want_forces=True, out=None, save_trajectory=True):
+                        body_inertia, body_inv_inertia, frame2step, want_forces=True, out=None, save_trajectory=True, state0=None):
         """-> wp_pos [F, bs*nb, 7], wp_vel [F, bs*nb, 6], grf, jaf [F, bs*nb, 6] (or None), workspace.
         frame2step: host sequence of F distinct ints in 0..nsteps (validated by the library before the launch).
         save_trajectory=False: forward-only -- no workspace is allocated or written (workspace None), the outputs are the same bits;
-        no rollout_backward can follow."""
+        no rollout_backward can follow.
+        state0= (q_init and qd_init None): a RESUMED rollout -- state 0 is the body state state0, [bs*nb, 13] = (p, q xyzw, w, v) or the
+        pair (body_q [bs*nb, 7], body_qd [bs*nb, 6]), e.g. the rows of an earlier rollout's frame at its last state, taken as they are
+        (no FK, no re-normalisation): the rollout continues that one bit for bit."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
-        dev = q_init.device
+        if state0 is not None:
+            if q_init is not None or qd_init is not None:
+                raise ValueError("rollout_forward: state0 takes the place of q_init / qd_init (pass None for both)")
+            state0 = self._state0(state0)
+            init = (_dev(state0, "state0", bs * nb * 13) if state0.numel() else None, None)
+        else:
+            init = None
+        dev = q_init.device if state0 is None else state0.device
         f2s, nframes = self._f2s(frame2step)
         if out is None:
             out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False, save_trajectory=save_trajectory)
@@ -293,7 +315,7 @@ class DeviceModel:
         grf, jaf = (out["grf"], out["jaf"]) if want_forces else (None, None)
         p = lambda t, name, n: _dev(t, name, n) if (t is not None and t.numel()) else None  # empty tensors have a null data_ptr: the library accepts it
         _check(lib().pd_rollout_forward(
-            self.h, bs, nsteps, float(dt), p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd),
+            self.h, bs, nsteps, float(dt), *(init or (p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd))),
             p(torques, "torques", nsteps * bs * nqd), p(res_f, "res_f", nsteps * bs * nb * 6),
             p(refs, "refs", nsteps * bs * nqd), p(target_ke, "target_ke", bs * nqd),
             p(target_kd, "target_kd", bs * nqd), p(body_inv_mass, "body_inv_mass", bs * nb),
@@ -432,20 +454,35 @@ class DeviceModel:
         return out
 
     def rollout_backward(self, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, body_inv_mass,
-                         body_inertia, body_inv_inertia, frame2step, ws, adj_pos, adj_vel, out=None):
+                         body_inertia, body_inv_inertia, frame2step, ws, adj_pos, adj_vel, out=None, state0=None):
+        """The adjoint of rollout_forward -> dict of gradients.  state0= (q_init and qd_init None): the adjoint of a resumed rollout; the
+        dict then holds ``state0`` [bs*nb, 13], the gradient of the body state, in place of q_init / qd_init.  It is stored RAW -- no
+        remove_nan, unlike every other gradient: it is the adjoint that flows on into the rollout that produced the state, as the seed
+        of that rollout's frame at its last state, and the single launch does not scrub it between steps either."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
-        dev = q_init.device
+        resumed = state0 is not None
+        if resumed:
+            if q_init is not None or qd_init is not None:
+                raise ValueError("rollout_backward: state0 takes the place of q_init / qd_init (pass None for both)")
+            state0 = self._state0(state0)
+        dev = state0.device if resumed else q_init.device
         f2s, nframes = self._f2s(frame2step)
-        g = out["grads"] if out is not None else self._alloc_grads(bs, nsteps, dev)
+        g = out["grads"] if out is not None else self._alloc_grads(bs, nsteps, dev, resumed=resumed)
         p = lambda t, name, n=None: _dev(t, name, n) if t.numel() else None
+        if resumed:
+            init = (p(state0, "state0", bs * nb * 13), None)
+            g_init = (p(g["state0"], "g state0", bs * nb * 13), None)
+        else:
+            init = (p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd))
+            g_init = (p(g["q_init"], "g"), p(g["qd_init"], "g"))
         _check(lib().pd_rollout_backward(
-            self.h, bs, nsteps, float(dt), p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd),
+            self.h, bs, nsteps, float(dt), *init,
             p(torques, "torques", nsteps * bs * nqd), p(refs, "refs", nsteps * bs * nqd),
             p(target_ke, "target_ke", bs * nqd), p(target_kd, "target_kd", bs * nqd),
             p(body_inv_mass, "body_inv_mass", bs * nb), p(body_inertia, "body_inertia", bs * nb * 9),
             p(body_inv_inertia, "body_inv_inertia", bs * nb * 9), nframes, f2s,
             p(ws, "workspace", self.workspace_floats(bs, nsteps)), p(adj_pos, "adj_pos", nframes * bs * nb * 7),
-            p(adj_vel, "adj_vel", nframes * bs * nb * 6), p(g["q_init"], "g"), p(g["qd_init"], "g"),
+            p(adj_vel, "adj_vel", nframes * bs * nb * 6), *g_init,
             p(g["torques"], "g"), p(g["res_f"], "g"), p(g["refs"], "g"), p(g["target_ke"], "g"),
             p(g["target_kd"], "g"), p(g["body_inv_mass"], "g"), p(g["body_inertia"], "g"),
             p(g["body_inv_inertia"], "g"), _stream()))
