@@ -166,7 +166,17 @@ int pd_rollout_forward(const pd_model *m, int bs, int nsteps, float dt,
  * direct gradient (integrator_euler.py:43 loads it, nothing uses it), so there is no g_body_mass.
  * Every stored gradient has been through the boundary's remove_nan (diffphys/dp_model.py:1294-1384 with
  * diffphys/dp_utils.py:43-57, clip=False): NaN -> 0, +-inf kept -- applied by the kernel at its stores (ABI v4; up to v3
- * the caller had to scrub). */
+ * the caller had to scrub).
+ * Selective: each of g_torques_dev, g_res_f_dev and g_refs_dev -- the three gradients with a row PER STEP, [T][bs*nqd], [T][bs*nb][6],
+ * [T][bs*nqd]: 456 bytes per Laikago env-step together -- may be NULL, here and in the two *_traj_loss backward entries, alone or in
+ * any combination (all three NULL included).  NULL means "not wanted": the launch computes nothing for that gradient and stores
+ * nothing for it, and the caller allocates nothing.  Every gradient that IS asked for -- the remaining per-step ones, g_q_init /
+ * g_qd_init, the state gradient of a resumed rollout, the five summed ones, the FK ride's -- is bit-identical to what the launch with
+ * all three pointers stores.  Such a launch runs a selective instantiation of the adjoint kernel (its per-step stores behind
+ * wave-uniform tests of the pointers); with all three given the kernel is the one it always was.  Composes with Resumed
+ * (qd_init_dev == NULL); neither allocates nor synchronises, so it may be captured.  The INPUTS torques_dev / refs_dev and the
+ * workspace stay required with nsteps > 0, and every other g_*_dev stays required.  These argument combinations were refused ("null
+ * device pointer") before; no symbol or signature changed, the version stays 9. */
 int pd_rollout_backward(const pd_model *m, int bs, int nsteps, float dt,
                         const float *q_init_dev, const float *qd_init_dev, const float *torques_dev,
                         const float *refs_dev, const float *target_ke_dev, const float *target_kd_dev,

@@ -739,7 +739,9 @@ static int rollout_backward_impl(const pd_model *cm, int bs, int nsteps, float d
   if (!q_init || (!qd_init && !resumed) || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia || !g_q_init ||
       (!g_qd_init && !resumed) || !g_ke || !g_kd || !g_inv_mass || !g_inertia || !g_inv_inertia)
     return fail("null device pointer");
-  if (nsteps > 0 && (!torques || !refs || !ws || !g_torques || !g_res_f || !g_refs)) return fail("null device pointer");
+  // g_torques / g_res_f / g_refs may each be NULL: that per-step gradient is not wanted -- the launch then takes the adjoint kernel's
+  // selective instantiation (pd_kernels.hip SEL), which computes and stores nothing for it; the inputs and the workspace stay required
+  if (nsteps > 0 && (!torques || !refs || !ws)) return fail("null device pointer");
   if (!tl && nframes > 0 && (!adj_pos || !adj_vel)) return fail("null device pointer");
   if (tl && ((adj_pos == nullptr) != (adj_vel == nullptr))) return fail("adj_pos and adj_vel come together (both, or neither)");
   if (tl && nframes > 0 && (!tl->seed_pos || !tl->scale || !tl->gain || !tl->work)) return fail("null device pointer (trajectory loss)");

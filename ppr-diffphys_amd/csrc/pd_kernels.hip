@@ -1506,7 +1506,19 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
 #endif
 #endif
 // QUAD: the body wave in the four-lanes-per-body form (pd_quad.h), one env per wave, 64-lane mapping -- see k_rollout_fwd.
-template <int SEGW, int JT, bool SPLIT, bool EARLY = false, bool QUAD = false>
+// SEL (adjoint kernels): the SELECTIVE instantiation, launched when the caller declined at least one of the per-step gradients
+// g_torques / g_res_f / g_refs (a NULL pointer: pd_rollout_backward).  Each of their store groups then sits behind a wave-uniform test
+// of its pointer -- a kernel argument, so a scalar compare and branch -- and nothing is stored, and no remove_nan select is made, for
+// an absent one.  Everything else is the same source: no sum changes its order and no surviving value its expression, so every
+// gradient that IS asked for has the all-three launch's bits.  SEL = false folds the tests to `true` at compile time: the launch with
+// all three pointers runs the code it ran before the flag existed.
+template <bool SEL>
+__device__ __forceinline__ bool grad_wanted(const float *g) {
+  if constexpr (SEL) return g != nullptr;
+  else return true;
+}
+
+template <int SEGW, int JT, bool SPLIT, bool EARLY = false, bool QUAD = false, bool SEL = false>
 __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
@@ -1898,7 +1910,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
       adjf[bb * PD_W6 + (k.isv ? qc : 6)] = adj_t0; adjf[bb * PD_W6 + (k.isv ? 3 + qc : 6)] = adj_f0;  // (lane 3: the slot's pad float)
       pair_signal(sig, a.nsteps - step);  // A: records (staged one step ago) + wrench adjoints
       STAMP(1);
-      if (k.isv) {
+      if (grad_wanted<SEL>(a.g_res_f) && k.isv) {
         float *o = a.g_res_f + (size_t)step * N * 6;  // adjoint of wp_add
         stg(o, boff_rf, NZ(adj_t0)); stg(o + 3, boff_rf, NZ(adj_f0));
       }
@@ -1937,13 +1949,20 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
       {
         *cs_r = par.r; *cs_p = par.p; *cs_w = par.w; *cs_v = par.v;
         if (qc == 0) {
-          if (B.type == PD_JOINT_REVOLUTE) { stg(a.g_refs + oc, boff_qd, NZ(a_tgt)); stg(a.g_torques + oc, boff_qd, NZ(a_act)); }
+          if (B.type == PD_JOINT_REVOLUTE) {
+            if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc, boff_qd, NZ(a_tgt));
+            if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc, boff_qd, NZ(a_act));
+          }
         }
         // the root's six dof columns are zero (a FREE joint reads no dof, integrator_euler.py:382): lanes 0-5 of the root's quad
         // and its neighbour write one each
         if (B.type == PD_JOINT_FREE) {
-          stg(a.g_refs + oc + qc, boff_qd, 0.f); stg(a.g_torques + oc + qc, boff_qd, 0.f);
-          if (qc < 2) { stg(a.g_refs + oc + 4 + qc, boff_qd, 0.f); stg(a.g_torques + oc + 4 + qc, boff_qd, 0.f); }
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + qc, boff_qd, 0.f);
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + qc, boff_qd, 0.f);
+          if (qc < 2) {
+            if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + 4 + qc, boff_qd, 0.f);
+            if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + 4 + qc, boff_qd, 0.f);
+          }
         }
       }
       g_ke += a_ke; g_kd += a_kd;
@@ -2134,7 +2153,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
         }
         pair_signal(sig, a.nsteps - step);  // A: records + wrench adjoints are staged
       });
-      if (is_body) {
+      if (grad_wanted<SEL>(a.g_res_f) && is_body) {
         float *o = a.g_res_f + (size_t)step * N * 6;  // adjoint of wp_add
         stg2(o, boff * 6u, make_float2(NZ(adj_t0.x), NZ(adj_t0.y))); stg2(o + 2, boff * 6u, make_float2(NZ(adj_t0.z), NZ(adj_f0.x)));
         stg2(o + 4, boff * 6u, make_float2(NZ(adj_f0.y), NZ(adj_f0.z)));
@@ -2152,7 +2171,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     // this wave does ahead of the signal delays it: with the remove_nan selects and the g_res_f stores before the signal the
     // adjoint took 0.324 ms, behind it 0.312 (same-box A/B) -- then the stores, then take its joint hand-over records
     if (SPLIT) pair_signal(sig, a.nsteps - step);
-    if (is_body) {
+    if (grad_wanted<SEL>(a.g_res_f) && is_body) {
       float *o = a.g_res_f + (size_t)step * N * 6;  // adjoint of wp_add
       stg2(o, boff * 6u, make_float2(NZ(adj_t0.x), NZ(adj_t0.y))); stg2(o + 2, boff * 6u, make_float2(NZ(adj_t0.z), NZ(adj_f0.x)));
       stg2(o + 4, boff * 6u, make_float2(NZ(adj_f0.y), NZ(adj_f0.z)));
@@ -2184,17 +2203,26 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
       adj_store(cslot + b * PD_ADJ, par);
 #pragma unroll
       for (int k = 0; k < ND; ++k) {
-        if (k < ndof) { stg(a.g_refs + oc + k, boff_qd, NZ(a_tgt[k])); stg(a.g_torques + oc + k, boff_qd, NZ(a_act[k])); }
+        if (k < ndof) {
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + k, boff_qd, NZ(a_tgt[k]));
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + k, boff_qd, NZ(a_act[k]));
+        }
         g_ke[k] += a_ke[k]; g_kd[k] += a_kd[k];
       }
       // the root's six dof columns are zero (a FREE joint reads no dof, integrator_euler.py:382).  Lanes 1..6 write one each
       // beside their own entry -- two vector-memory instructions per array and step instead of seven: with eight waves
       // on a CU it is the NUMBER of such instructions (one per ~27 cycles across the CU), not their bytes, that the loop feels
       if (zero_by_lanes) {
-        if (b >= 1 && b <= 6) { stg(a.g_refs + oc, boff_zero, 0.f); stg(a.g_torques + oc, boff_zero, 0.f); }
+        if (b >= 1 && b <= 6) {
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc, boff_zero, 0.f);
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc, boff_zero, 0.f);
+        }
       } else if (c.type == PD_JOINT_FREE) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) { stg(a.g_refs + oc + k, boff_qd, 0.f); stg(a.g_torques + oc + k, boff_qd, 0.f); }
+        for (int k = 0; k < 6; ++k) {
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + k, boff_qd, 0.f);
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + k, boff_qd, 0.f);
+        }
       }
     }
     STAMP(2);
@@ -2296,7 +2324,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
 // ROLES = 3: I, C, J waves (<= 168 VGPRs each).  ROLES = 2: the integrate wave also replays the contacts (between its phase 2
 // and the wait for the joint wave) -- compound-joint robots, whose joint adjoint needs more than 168 registers but whose
 // box contacts are a handful of points: two waves per env group, <= 256 VGPRs each.
-template <int SEGW, int JT, int ROLES, bool GT = false>  // GT: contact tables in global memory, as k_rollout_fwd
+template <int SEGW, int JT, int ROLES, bool GT = false, bool SEL = false>  // GT: contact tables in global memory, as k_rollout_fwd; SEL: see k_rollout_bwd
 __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevModel m, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
@@ -2460,22 +2488,34 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
       if constexpr (CLONE3) {  // every non-FREE joint has ND dofs: one region for the six stores
         if (gw && ndof > 0) {
 #pragma unroll
-          for (int k = 0; k < ND; ++k) { stg(a.g_refs + oc + k, boff_qd, NZ(a_tgt[k])); stg(a.g_torques + oc + k, boff_qd, NZ(a_act[k])); }
+          for (int k = 0; k < ND; ++k) {
+            if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + k, boff_qd, NZ(a_tgt[k]));
+            if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + k, boff_qd, NZ(a_act[k]));
+          }
         }
 #pragma unroll
         for (int k = 0; k < ND; ++k) { g_ke[k] += a_ke[k]; g_kd[k] += a_kd[k]; }
       } else {
 #pragma unroll
       for (int k = 0; k < ND; ++k) {
-        if (is_body && k < ndof) { stg(a.g_refs + oc + k, boff_qd, NZ(a_tgt[k])); stg(a.g_torques + oc + k, boff_qd, NZ(a_act[k])); }
+        if (is_body && k < ndof) {
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + k, boff_qd, NZ(a_tgt[k]));
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + k, boff_qd, NZ(a_act[k]));
+        }
         g_ke[k] += a_ke[k]; g_kd[k] += a_kd[k];
       }
       }
       if (zero_by_lanes) {
-        if (gw && b >= 1 && b <= 6 && l < nb) { stg(a.g_refs + oc, boff_zero, 0.f); stg(a.g_torques + oc, boff_zero, 0.f); }
+        if (gw && b >= 1 && b <= 6 && l < nb) {
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc, boff_zero, 0.f);
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc, boff_zero, 0.f);
+        }
       } else if (is_body && c.type == PD_JOINT_FREE) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) { stg(a.g_refs + oc + k, boff_qd, 0.f); stg(a.g_torques + oc + k, boff_qd, 0.f); }
+        for (int k = 0; k < 6; ++k) {
+          if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + k, boff_qd, 0.f);
+          if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc + k, boff_qd, 0.f);
+        }
       }
     };
     if constexpr (JT == PD_JT_REVOLUTE) {
@@ -2711,7 +2751,7 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
       if (pre_ok) load_log(step - 1, cnt_n, e_n);
     });
     rotm_adj(s.r, aR, ga.r);
-    if (gw) {
+    if (grad_wanted<SEL>(a.g_res_f) && gw) {
       float *o = a.g_res_f + (size_t)__builtin_amdgcn_readfirstlane(step) * N * 6;  // adjoint of wp_add
       stg2(o, boff * 6u, make_float2(NZ(adj_t0.x), NZ(adj_t0.y))); stg2(o + 2, boff * 6u, make_float2(NZ(adj_t0.z), NZ(adj_f0.x)));
       stg2(o + 4, boff * 6u, make_float2(NZ(adj_f0.y), NZ(adj_f0.z)));
@@ -2941,31 +2981,41 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
   return hipGetLastError();
 }
 
-template <int JT, bool GT>
-static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, const PdLaunchCfg &cfg, hipStream_t st) {
+template <int JT, bool GT, bool SEL>
+static hipError_t launch_bwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
   const dim3 g(cfg.nblocks), t(cfg.threads);
   const size_t lds = cfg.lds;
+  if constexpr (pd_split(JT)) {
+    if (cfg.kernel == PD_KV_BWD_QUAD) {
+      if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
+        hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false, true, SEL>), g, t, lds, st, m, a);
+        return hipGetLastError();
+      } else {
+        return hipErrorInvalidValue;
+      }
+    }
+    hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false, false, SEL>), g, t, lds, st, m, a);
+  } else {
+    hipLaunchKernelGGL((k_rollout_bwd3<PD_SEGW, JT, 2, GT, SEL>), g, t, lds, st, m, a);
+  }
+  return hipGetLastError();
+}
+
+template <int JT, bool GT>
+static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, const PdLaunchCfg &cfg, hipStream_t st) {
+  [[maybe_unused]] const dim3 g(cfg.nblocks), t(cfg.threads);  // (the FK kinds' geometry: the literal objects launch no FK kernel)
+  [[maybe_unused]] const size_t lds = cfg.lds;
   switch (kind) {
     case PD_K_ROLLOUT_FWD: {
       // no workspace: the forward-only kernels (a rollout of no steps saves nothing either way and keeps the saving kernel: pd_host.hip)
       const RolloutArgs &a = *(const RolloutArgs *)args;
       return a.ws || a.nsteps == 0 ? launch_fwd<JT, GT, true>(m, a, cfg, st) : launch_fwd<JT, GT, false>(m, a, cfg, st);
     }
-    case PD_K_ROLLOUT_BWD:
-      if constexpr (pd_split(JT)) {
-        if (cfg.kernel == PD_KV_BWD_QUAD) {
-          if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-            hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false, true>), g, t, lds, st, m, *(const RolloutArgs *)args);
-            break;
-          } else {
-            return hipErrorInvalidValue;
-          }
-        }
-        hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false>), g, t, lds, st, m, *(const RolloutArgs *)args);
-      } else {
-        hipLaunchKernelGGL((k_rollout_bwd3<PD_SEGW, JT, 2, GT>), g, t, lds, st, m, *(const RolloutArgs *)args);
-      }
-      break;
+    case PD_K_ROLLOUT_BWD: {
+      // a per-step gradient declined (NULL g_torques / g_res_f / g_refs): the selective twin (SEL); all three given, the kernel as ever
+      const RolloutArgs &a = *(const RolloutArgs *)args;
+      return a.nsteps > 0 && (!a.g_torques || !a.g_res_f || !a.g_refs) ? launch_bwd<JT, GT, true>(m, a, cfg, st) : launch_bwd<JT, GT, false>(m, a, cfg, st);
+    }
 #if PD_POLICY == 0  // (the host routes the FK kinds to these launchers whatever the model's policy)
     case PD_K_FK_FWD:
       hipLaunchKernelGGL((k_fk<PD_SEGW, JT, false>), g, t, lds, st, m, *(const FkArgs *)args);
@@ -3009,19 +3059,27 @@ static hipError_t set_lds_fwd(int bytes) {
   return hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+template <int JT, bool GT, bool SEL>
+static hipError_t set_lds_bwd(int bytes) {
+  hipError_t e;
+  if constexpr (pd_split(JT)) {
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false, false, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false, true, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    }
+  } else {
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd3<PD_SEGW, JT, 2, GT, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  }
+  return hipSuccess;
+}
+
 template <int JT, bool GT>
 static hipError_t set_lds_gt(int bytes) {
   hipError_t e;
   if ((e = set_lds_fwd<JT, GT, true>(bytes))) return e;
   if ((e = set_lds_fwd<JT, GT, false>(bytes))) return e;  // (the forward-only twins)
-  if constexpr (pd_split(JT)) {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    }
-  } else {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd3<PD_SEGW, JT, 2, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  }
+  if ((e = set_lds_bwd<JT, GT, false>(bytes))) return e;
+  if ((e = set_lds_bwd<JT, GT, true>(bytes))) return e;  // (the selective twins)
 #if PD_POLICY == 0
   if constexpr (GT) return hipSuccess;  // (the FK kernels are the same for both placements: set with GT = false)
   if ((e = hipFuncSetAttribute((const void *)k_fk<PD_SEGW, JT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;

@@ -153,6 +153,25 @@ def _remove_nan(g):
     return torch.where(g != g, torch.zeros_like(g), g)
 
 
+def grads_wanted(needs_input_grad):
+    """The ``want=`` of the adjoint launch from an autograd ctx's ``needs_input_grad``: of the per-step gradients (torques, res_f, refs --
+    inputs 2, 3, 4 of ForwardWarp, ForwardWarpState, ForwardWarpTrajLoss and ForwardWarpTrajLossFK alike) those whose input needs one.
+    The rest are neither allocated nor computed, and the Function returns None for them."""
+    return tuple(n for n, i in (("torques", 2), ("res_f", 3), ("refs", 4)) if needs_input_grad[i])
+
+
+def _want_kw(ctx):
+    """The ``want=`` keyword of the adjoint call -- absent when all three per-step gradients are needed: the call is then the one it
+    always was (as _save_kw: a backend object that predates the selective adjoint keeps working where every input needs a gradient)."""
+    want = grads_wanted(ctx.needs_input_grad)
+    return {} if len(want) == len(hip_backend.GRAD_NAMES) else {"want": want}
+
+
+def _view(g, name, like):
+    """a per-step gradient shaped as its input, or None when it was not asked for"""
+    return g[name].view_as(like) if name in g else None
+
+
 _SUMMED = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")  # gradients that are sums over the steps
 
 
@@ -172,14 +191,16 @@ def _checkpoint_forward(dm, bs, nsteps, dt, inp, frame2step, K):
     return pos, vel, grf, jaf, states
 
 
-def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos, adj_vel):
+def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos, adj_vel, want=hip_backend.GRAD_NAMES):
     """Backward of the checkpointed ForwardWarp -> the gradient dict of DeviceModel.rollout_backward.  Segments last to first: a saving
     forward of the segment from its boundary state into the one K-step workspace, then its adjoint, seeded with the caller's seeds
-    inside the segment and the state adjoint carried from the segment after (raw).  No host synchronisation."""
+    inside the segment and the state adjoint carried from the segment after (raw).  No host synchronisation.  want: the per-step
+    gradients to compute -- only they get their full [T] tensor, whose step slices the segments' selective launches fill."""
     q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = inp
     _, segments = checkpoint_plan(nsteps, frame2step, K)
     dev, N = torques.device, bs * dm.nb
-    g = dm._alloc_grads(bs, nsteps, dev)
+    want = hip_backend.grad_want(want)
+    g = dm._alloc_grads(bs, nsteps, dev, want=want)
     tmp = {k: torch.empty_like(g[k]) for k in _SUMMED}
     ws = torch.empty(dm.workspace_floats(bs, min(K, nsteps)), dtype=torch.float32, device=dev)
     carry = torch.empty(N, 13, dtype=torch.float32, device=dev) if len(segments) > 1 else None
@@ -201,13 +222,13 @@ def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos
             sv = torch.cat([adj_vel[j: j + 1] for j in idx] + ([carry[None, :, 7:]] if has_carry else []))
         first = i == len(segments) - 1  # the first segment processed writes the sums' accumulators themselves
         gs = {k: (g[k] if first else tmp[k]) for k in _SUMMED}
-        gs.update(torques=g["torques"][start:end], res_f=g["res_f"][start:end], refs=g["refs"][start:end])
+        gs.update({k: g[k][start:end] for k in want})
         if i > 0:
             gs["state0"] = carry
         else:
             gs.update(q_init=g["q_init"], qd_init=g["qd_init"])
         dm.rollout_backward(bs, n, dt, *q0, ctl[0], ctl[2], ke, kd, inv_m, inertia, inv_inertia, local, seg_ws, sp, sv,
-                            out=dict(grads=gs), **init)
+                            out=dict(grads=gs), want=want, **init)
         if not first:
             for k in _SUMMED:
                 g[k].add_(tmp[k])
@@ -265,18 +286,19 @@ class ForwardWarp(torch.autograd.Function):
     def backward(ctx, adj_body_qs, adj_body_qd):
         ws, q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = ctx.saved_tensors
         bs, nsteps, dt, frame2step = ctx.meta
+        want = _want_kw(ctx)  # per-step gradients nobody asked for are not allocated, computed or stored
         if ctx.checkpoint:
             g = _checkpoint_backward(ctx.dm, bs, nsteps, dt, (q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia),
                                      frame2step, ctx.checkpoint, ws, adj_body_qs.to(torch.float32).contiguous(),
-                                     adj_body_qd.to(torch.float32).contiguous())
+                                     adj_body_qd.to(torch.float32).contiguous(), **want)
         else:
             g = ctx.dm.rollout_backward(bs, nsteps, dt, q_init, qd_init, torques, refs, ke, kd, inv_m, inertia, inv_inertia,
                                         frame2step, ws, adj_body_qs.to(torch.float32).contiguous(),
-                                        adj_body_qd.to(torch.float32).contiguous())
+                                        adj_body_qd.to(torch.float32).contiguous(), **want)
         # remove_nan (dp_model.py:1294-1384: NaN -> 0 on every returned gradient, inf kept) is applied by the adjoint kernel where it
         # stores the gradients (pd_rollout_backward): no pass over the tensors here
-        return (g["q_init"], g["qd_init"], g["torques"].view_as(torques), g["res_f"].view_as(res_f),
-                g["refs"].view_as(refs), g["target_ke"], g["target_kd"],
+        return (g["q_init"], g["qd_init"], _view(g, "torques", torques), _view(g, "res_f", res_f),
+                _view(g, "refs", refs), g["target_ke"], g["target_kd"],
                 torch.zeros(ctx.mass_shape, dtype=torch.float32, device=torques.device), g["body_inv_mass"],
                 g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
 
@@ -318,10 +340,11 @@ class ForwardWarpState(torch.autograd.Function):
         ws, state0, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = ctx.saved_tensors
         bs, nsteps, dt, frame2step = ctx.meta
         g = ctx.dm.rollout_backward(bs, nsteps, dt, None, None, torques, refs, ke, kd, inv_m, inertia, inv_inertia, frame2step, ws,
-                                    adj_body_qs.to(torch.float32).contiguous(), adj_body_qd.to(torch.float32).contiguous(), state0=state0)
+                                    adj_body_qs.to(torch.float32).contiguous(), adj_body_qd.to(torch.float32).contiguous(), state0=state0,
+                                    **_want_kw(ctx))
         g0 = _remove_nan(g["state0"])
-        return (g0[:, :7].reshape(ctx.q0_shape), g0[:, 7:].reshape(ctx.qd0_shape), g["torques"].view_as(torques), g["res_f"].view_as(res_f),
-                g["refs"].view_as(refs), g["target_ke"], g["target_kd"],
+        return (g0[:, :7].reshape(ctx.q0_shape), g0[:, 7:].reshape(ctx.qd0_shape), _view(g, "torques", torques), _view(g, "res_f", res_f),
+                _view(g, "refs", refs), g["target_ke"], g["target_kd"],
                 torch.zeros(ctx.mass_shape, dtype=torch.float32, device=torques.device), g["body_inv_mass"],
                 g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
 
@@ -424,14 +447,14 @@ def _traj_loss_backward(ctx, g_loss, g_queried):
         aqd = z(ctx.fk_shapes[1]) if g_queried[1] is None else g_queried[1].to(torch.float32).contiguous()
         fk = (jq, jqd, aq, aqd)
     g = ctx.dm.rollout_backward_traj_loss(bs, nsteps, dt, q_init, qd_init, torques, refs, ke, kd, inv_m, inertia, inv_inertia,
-                                          frame2step, ws, tl, gl, fk=fk)
+                                          frame2step, ws, tl, gl, fk=fk, **_want_kw(ctx))
     g_tgt = None
     if ctx.needs_input_grad[11] and tl["seed_gt"] is not None:  # d loss_traj / d target pose = g x share / nb x d se3 / d gt
         # a zero share is an ASSIGNMENT in the reference (loss_seq[i, idx:] = 0, loss_traj[outseq_idx] = 0): nothing flows there, not 0 * inf
         k = (tl["scale"] * (gl / ctx.dm.nb))[:, :, None, None]
         g_tgt = torch.where(k != 0, tl["seed_gt"] * k, torch.zeros_like(tl["seed_gt"])).view(ctx.tgt_shape)
-    out = (g["q_init"], g["qd_init"], g["torques"].view_as(torques), g["res_f"].view_as(res_f),
-           g["refs"].view_as(refs), g["target_ke"], g["target_kd"],
+    out = (g["q_init"], g["qd_init"], _view(g, "torques", torques), _view(g, "res_f", res_f),
+           _view(g, "refs", refs), g["target_ke"], g["target_kd"],
            torch.zeros(ctx.mass_shape, dtype=torch.float32, device=ws.device), g["body_inv_mass"],
            g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), g_tgt, None)
     if g_queried is not None:

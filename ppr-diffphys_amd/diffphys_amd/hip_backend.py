@@ -20,6 +20,41 @@ ABI_VERSION = 9  # PD_ABI_VERSION of include/ppr_diffphys.h this binding was wri
 _fp = ctypes.POINTER(ctypes.c_float)
 _ip = ctypes.POINTER(ctypes.c_int)
 
+# The gradients the adjoint stores PER STEP -- [T, bs*nqd], [T, bs*nb, 6], [T, bs*nqd] -- and the only ones a caller may decline
+# (``want=`` of rollout_backward / rollout_backward_traj_loss): the library takes a NULL pointer for each as "not wanted".
+GRAD_NAMES = ("torques", "res_f", "refs")
+
+
+def grad_want(want):
+    """``want`` as a tuple in GRAD_NAMES order.  Any iterable of names (or one name); the empty tuple asks for no per-step gradient.
+    An unknown name raises: a typo must not silently drop a gradient."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for n in want:
+        if n not in GRAD_NAMES:
+            raise ValueError("want: unknown per-step gradient %r (known: %s)" % (n, ", ".join(GRAD_NAMES)))
+    return tuple(n for n in GRAD_NAMES if n in want)
+
+
+def alloc_grads(nb, nq, nqd, bs, nsteps, device, resumed=False, want=GRAD_NAMES):
+    """The gradient buffers of one adjoint rollout (DeviceModel._alloc_grads).  Of the per-step gradients only those in ``want`` are
+    allocated, and only they are keys of the result."""
+    want = grad_want(want)
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
+    g = dict(state0=e(bs * nb, 13)) if resumed else dict(q_init=e(bs * nq), qd_init=e(bs * nqd))
+    step = dict(torques=(nsteps, bs * nqd), res_f=(nsteps, bs * nb, 6), refs=(nsteps, bs * nqd))
+    g.update({n: e(*step[n]) for n in GRAD_NAMES if n in want})
+    g.update(target_ke=e(bs * nqd), target_kd=e(bs * nqd), body_inv_mass=e(bs * nb),
+             body_inertia=e(bs * nb, 3, 3), body_inv_inertia=e(bs * nb, 3, 3))
+    return g
+
+
+def _select_grads(g, want):
+    """The dict a selective adjoint returns: ``g`` without the per-step gradients that were not asked for (g itself when all were)."""
+    for n in want:
+        if n not in g:
+            raise KeyError("out['grads'] has no buffer for the wanted gradient %r" % n)
+    return g if len(want) == len(GRAD_NAMES) else {k: v for k, v in g.items() if k not in GRAD_NAMES or k in want}
+
 
 class _Desc(ctypes.Structure):
     _fields_ = [
@@ -266,15 +301,10 @@ class DeviceModel:
             o["grads"] = self._alloc_grads(bs, nsteps, device)
         return o
 
-    def _alloc_grads(self, bs, nsteps, device, resumed=False):
-        """resumed: the gradient buffers of a rollout that started from a body state -- ``state0`` [bs*nb, 13] in place of q_init / qd_init."""
-        nb, nq, nqd = self.nb, self.nq, self.nqd
-        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
-        g = dict(state0=e(bs * nb, 13)) if resumed else dict(q_init=e(bs * nq), qd_init=e(bs * nqd))
-        g.update(torques=e(nsteps, bs * nqd), res_f=e(nsteps, bs * nb, 6),
-                 refs=e(nsteps, bs * nqd), target_ke=e(bs * nqd), target_kd=e(bs * nqd), body_inv_mass=e(bs * nb),
-                 body_inertia=e(bs * nb, 3, 3), body_inv_inertia=e(bs * nb, 3, 3))
-        return g
+    def _alloc_grads(self, bs, nsteps, device, resumed=False, want=GRAD_NAMES):
+        """resumed: the gradient buffers of a rollout that started from a body state -- ``state0`` [bs*nb, 13] in place of q_init / qd_init.
+        want: the per-step gradients to allocate (GRAD_NAMES; the rest are left out of the dict)."""
+        return alloc_grads(self.nb, self.nq, self.nqd, bs, nsteps, device, resumed=resumed, want=want)
 
     @staticmethod
     def _state0(state0):
@@ -377,16 +407,19 @@ class DeviceModel:
         return wp_pos, wp_vel, grf, jaf, ws, tl
 
     def rollout_backward_traj_loss(self, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, body_inv_mass,
-                                   body_inertia, body_inv_inertia, frame2step, ws, tl, g_loss, adj_pos=None, adj_vel=None, out=None, fk=None):
+                                   body_inertia, body_inv_inertia, frame2step, ws, tl, g_loss, adj_pos=None, adj_vel=None, out=None, fk=None,
+                                   want=GRAD_NAMES):
         """``pd_rollout_backward_traj_loss``: the adjoint rollout seeded with g_loss (a 0-dim / 1-element GPU tensor: the upstream
         gradient of loss_traj) x scale / nb x seed_pos, plus adj_pos / adj_vel when given.
         fk = (joint_q [Ff, bs_f, nq], joint_qd [Ff, bs_f, nqd], adj_body_q [bs_f, Ff, nb, 7], adj_body_qd [bs_f, Ff, nb, 6]): the FK
         adjoint rides on the seeds launch (``pd_rollout_backward_traj_loss_fk``); g then also holds fk_joint_q [Ff, bs_f, nq] and
-        fk_joint_qd [Ff, bs_f, nqd] (with ForwardKinematics.backward's post-processing)."""
+        fk_joint_qd [Ff, bs_f, nqd] (with ForwardKinematics.backward's post-processing).
+        want: as rollout_backward."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         dev = q_init.device
         f2s, nframes = self._f2s(frame2step)
-        g = out["grads"] if out is not None else self._alloc_grads(bs, nsteps, dev)
+        want = grad_want(want)
+        g = _select_grads(out["grads"], want) if out is not None else self._alloc_grads(bs, nsteps, dev, want=want)
         work = tl.get("work")
         if work is None:  # scratch for the seeds of this sweep (adj_pos / adj_vel layout), kept with the forward's outputs
             work = tl["work"] = torch.empty(nframes * bs * nb * 13, dtype=torch.float32, device=dev)
@@ -412,7 +445,7 @@ class DeviceModel:
             p(adj_vel, "adj_vel", nframes * bs * nb * 6), p(tl["seed_pos"], "seed_pos", nframes * bs * nb * 7),
             p(tl["scale"], "scale", bs * nframes), _dev(g_loss, "g_loss", 1), p(work, "seed_work", nframes * bs * nb * 13),
             p(g["q_init"], "g"), p(g["qd_init"], "g"),
-            p(g["torques"], "g"), p(g["res_f"], "g"), p(g["refs"], "g"), p(g["target_ke"], "g"),
+            p(g.get("torques"), "g"), p(g.get("res_f"), "g"), p(g.get("refs"), "g"), p(g["target_ke"], "g"),
             p(g["target_kd"], "g"), p(g["body_inv_mass"], "g"), p(g["body_inertia"], "g"),
             p(g["body_inv_inertia"], "g"), *(() if ride is None else (ctypes.byref(ride),)), _stream()))
         return g
@@ -454,12 +487,16 @@ class DeviceModel:
         return out
 
     def rollout_backward(self, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, body_inv_mass,
-                         body_inertia, body_inv_inertia, frame2step, ws, adj_pos, adj_vel, out=None, state0=None):
+                         body_inertia, body_inv_inertia, frame2step, ws, adj_pos, adj_vel, out=None, state0=None, want=GRAD_NAMES):
         """The adjoint of rollout_forward -> dict of gradients.  state0= (q_init and qd_init None): the adjoint of a resumed rollout; the
         dict then holds ``state0`` [bs*nb, 13], the gradient of the body state, in place of q_init / qd_init.  It is stored RAW -- no
         remove_nan, unlike every other gradient: it is the adjoint that flows on into the rollout that produced the state, as the seed
-        of that rollout's frame at its last state, and the single launch does not scrub it between steps either."""
+        of that rollout's frame at its last state, and the single launch does not scrub it between steps either.
+        want: which of the per-step gradients GRAD_NAMES = ("torques", "res_f", "refs") to compute (default: all three).  One that is
+        not named is neither allocated nor computed -- the library gets a NULL pointer and runs its selective adjoint kernel, which
+        stores nothing for it -- and is not a key of the returned dict; every other gradient is the all-three launch's, bit for bit."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
+        want = grad_want(want)
         resumed = state0 is not None
         if resumed:
             if q_init is not None or qd_init is not None:
@@ -467,8 +504,8 @@ class DeviceModel:
             state0 = self._state0(state0)
         dev = state0.device if resumed else q_init.device
         f2s, nframes = self._f2s(frame2step)
-        g = out["grads"] if out is not None else self._alloc_grads(bs, nsteps, dev, resumed=resumed)
-        p = lambda t, name, n=None: _dev(t, name, n) if t.numel() else None
+        g = _select_grads(out["grads"], want) if out is not None else self._alloc_grads(bs, nsteps, dev, resumed=resumed, want=want)
+        p = lambda t, name, n=None: _dev(t, name, n) if (t is not None and t.numel()) else None
         if resumed:
             init = (p(state0, "state0", bs * nb * 13), None)
             g_init = (p(g["state0"], "g state0", bs * nb * 13), None)
@@ -483,7 +520,7 @@ class DeviceModel:
             p(body_inv_inertia, "body_inv_inertia", bs * nb * 9), nframes, f2s,
             p(ws, "workspace", self.workspace_floats(bs, nsteps)), p(adj_pos, "adj_pos", nframes * bs * nb * 7),
             p(adj_vel, "adj_vel", nframes * bs * nb * 6), *g_init,
-            p(g["torques"], "g"), p(g["res_f"], "g"), p(g["refs"], "g"), p(g["target_ke"], "g"),
+            p(g.get("torques"), "g"), p(g.get("res_f"), "g"), p(g.get("refs"), "g"), p(g["target_ke"], "g"),
             p(g["target_kd"], "g"), p(g["body_inv_mass"], "g"), p(g["body_inertia"], "g"),
             p(g["body_inv_inertia"], "g"), _stream()))
         return g
