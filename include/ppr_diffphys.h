@@ -153,6 +153,17 @@ int pd_model_bind_joint_X_p(pd_model *m, const float *joint_X_p_dev, int n_envs)
  * g_qd_init_dev must be NULL (a non-NULL one is refused with a message, nothing is written).  That state gradient is stored RAW, without
  * the remove_nan every other gradient gets: it is the adjoint that flows on into the rollout that produced the state -- as the seed
  * (adj_pos / adj_vel rows) of that rollout's frame at its state nsteps -- and a single launch does not scrub it between steps either.
+ * Zero controls: torques_dev and res_f_dev may each be NULL with nsteps > 0, alone or together, here and in the two *_traj_loss forward
+ * entries.  NULL means "all zeros" -- what the reference feeds the rollout after multiplying both MLP outputs by zero
+ * (diffphys/dp_model.py:526-536): nothing is read for that input and the caller allocates nothing for it (Laikago: 384 of the 456 bytes of
+ * inputs per env-step).  Every output -- wp_pos / wp_vel / grf / jaf, the workspace with its hit log, and on the loss entries seeds, loss
+ * table, reduced, scale and the FK rows -- is bit-identical to the launch that is given zero-filled tensors.  Such a launch runs a
+ * zero-controls instantiation of the forward kernel (the loads of the two inputs behind wave-uniform tests of their pointers, an absent
+ * one yielding 0.0f into the same arithmetic); with both given the kernel is the one it always was.  Composes with Forward-only
+ * (NULL workspace) and Resumed (NULL qd_init_dev), both numeric policies, both kernel families, every segment width and both table
+ * placements; neither allocates nor synchronises, so it may be captured.  refs_dev stays required with nsteps > 0 -- a PD target of zero
+ * is a pose, not an absence: a NULL one is refused by name ("null device pointer: refs_dev ...") and nothing is written -- as does
+ * every other input.  The adjoint of such a rollout: see pd_rollout_backward, Zero controls.
  * These argument combinations were refused ("null device pointer") before; no symbol or signature changed, the version stays 9. */
 int pd_rollout_forward(const pd_model *m, int bs, int nsteps, float dt,
                        const float *q_init_dev, const float *qd_init_dev, const float *torques_dev,
@@ -174,9 +185,16 @@ int pd_rollout_forward(const pd_model *m, int bs, int nsteps, float dt,
  * g_qd_init, the state gradient of a resumed rollout, the five summed ones, the FK ride's -- is bit-identical to what the launch with
  * all three pointers stores.  Such a launch runs a selective instantiation of the adjoint kernel (its per-step stores behind
  * wave-uniform tests of the pointers); with all three given the kernel is the one it always was.  Composes with Resumed
- * (qd_init_dev == NULL); neither allocates nor synchronises, so it may be captured.  The INPUTS torques_dev / refs_dev and the
- * workspace stay required with nsteps > 0, and every other g_*_dev stays required.  These argument combinations were refused ("null
- * device pointer") before; no symbol or signature changed, the version stays 9. */
+ * (qd_init_dev == NULL); neither allocates nor synchronises, so it may be captured.  The INPUT refs_dev and the
+ * workspace stay required with nsteps > 0, and every other g_*_dev stays required.
+ * Zero controls: torques_dev may be NULL with nsteps > 0 ("all zeros"), here and in the two *_traj_loss backward entries; res_f is not
+ * an input of the adjoint.  CONTRACT: the adjoint's torques_dev is NULL exactly when the forward's was (or, equally, the forward was given
+ * zeros).  A mismatch cannot be detected -- the workspace does not record it -- and is the caller's error, like a numeric-policy mismatch:
+ * the gradients are then those of another rollout.  g_torques_dev and g_res_f_dev are independent of this: the gradient with respect to
+ * an absent, zero input is well defined, it is computed when its pointer is given, and it equals the zero-tensor launch's bit for bit, as
+ * does every other gradient.  A NULL torques_dev takes the selective instantiation too (the load behind a test of the pointer), whatever
+ * the g_*_dev are; composes with Selective and Resumed.  A NULL refs_dev is refused by name, nothing is written.
+ * These argument combinations were refused ("null device pointer") before; no symbol or signature changed, the version stays 9. */
 int pd_rollout_backward(const pd_model *m, int bs, int nsteps, float dt,
                         const float *q_init_dev, const float *qd_init_dev, const float *torques_dev,
                         const float *refs_dev, const float *target_ke_dev, const float *target_kd_dev,

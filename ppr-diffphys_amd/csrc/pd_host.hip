@@ -648,7 +648,9 @@ static int rollout_forward_impl(const pd_model *cm, int bs, int nsteps, float dt
   if (resumed && tl)
     return fail("qd_init is NULL: a rollout resumed from a body state is pd_rollout_forward's alone, the trajectory-loss entries start from (q_init, qd_init)");
   if (!q_init || (!qd_init && !resumed) || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia) return fail("null device pointer");
-  if (nsteps > 0 && (!torques || !res_f || !refs)) return fail("null device pointer");
+  // torques / res_f may each be NULL: "all zeros" -- nothing is read for it, the launch takes the forward kernels' zero-controls twins
+  // (pd_kernels.hip ZC), whose outputs are those of the launch with explicit zero tensors bit for bit; refs stays required
+  if (nsteps > 0 && !refs) return fail("null device pointer: refs_dev (the PD targets are required; only torques_dev and res_f_dev may be NULL, meaning all zeros)");
   if (nframes > 0 && (!wp_pos || !wp_vel)) return fail("null device pointer");
   if (m->xp_env && m->xp_envs != bs) return fail("joint_X_p is bound for " + std::to_string(m->xp_envs) + " envs, rollout has " + std::to_string(bs));
   // ws == NULL with nsteps > 0: forward-only -- the kernels store no trajectory, hit log or loss seeds (k_rollout_fwd SAVE = false), and
@@ -741,7 +743,9 @@ static int rollout_backward_impl(const pd_model *cm, int bs, int nsteps, float d
     return fail("null device pointer");
   // g_torques / g_res_f / g_refs may each be NULL: that per-step gradient is not wanted -- the launch then takes the adjoint kernel's
   // selective instantiation (pd_kernels.hip SEL), which computes and stores nothing for it; the inputs and the workspace stay required
-  if (nsteps > 0 && (!torques || !refs || !ws)) return fail("null device pointer");
+  // torques may be NULL ("all zeros", exactly when the forward's was): the same twin, with the load of torques behind a test as well
+  if (nsteps > 0 && !refs) return fail("null device pointer: refs_dev (the PD targets are required; only torques_dev may be NULL, meaning all zeros)");
+  if (nsteps > 0 && !ws) return fail("null device pointer");
   if (!tl && nframes > 0 && (!adj_pos || !adj_vel)) return fail("null device pointer");
   if (tl && ((adj_pos == nullptr) != (adj_vel == nullptr))) return fail("adj_pos and adj_vel come together (both, or neither)");
   if (tl && nframes > 0 && (!tl->seed_pos || !tl->scale || !tl->gain || !tl->work)) return fail("null device pointer (trajectory loss)");

@@ -71,6 +71,14 @@ PD_DEV float4 ldg4(const float *ubase, unsigned boff) { return *(const float4 *)
 PD_DEV void stg4(float *ubase, unsigned boff, float4 v) { *(float4 *)((char *)ubase + boff) = v; }
 PD_DEV float2 ldg2(const float *ubase, unsigned boff) { return *(const float2 *)((const char *)ubase + boff); }
 PD_DEV void stg2(float *ubase, unsigned boff, float2 v) { *(float2 *)((char *)ubase + boff) = v; }
+// An optional input (NULL torques / res_f: "all zeros", pd_rollout_forward): in the instantiations that accept one (ON: k_rollout_fwd ZC,
+// the adjoint kernels' SEL) a wave-uniform test of the pointer -- a kernel argument, so a scalar compare -- in all others the constant
+// `true`, which folds away.  Written INTO each load site: `ptr_given<ON>(p) ? ldg(p + ..) : 0.f`, address arithmetic included.
+template <bool ON>
+PD_DEV bool ptr_given(const float *p) {
+  if constexpr (ON) return p != nullptr;
+  else return true;
+}
 
 // Saved trajectory (workspace): per step PD_TRAJ_G planes of float4, [step][plane][bs*nb]; consecutive lanes touch consecutive
 // 16-byte words, and a step costs 5 vector-memory instructions per lane instead of 19 (their issue rate, not the bytes,
@@ -555,8 +563,13 @@ PD_DEV float *lds_setup(const PdDevModel &m, unsigned char *smem, SweepTables &T
 // SAVE = false (forward-only: a launch with no workspace, pd_rollout_forward* with workspace_dev == NULL): no global store to what only
 // the adjoint reads -- trajectory planes (a.ws), hit log (a.hitlog), loss seeds (a.loss_seed_pos / _gt).  Every LDS access, hand-over
 // and cull stays as it is, so the frame outputs and the loss table are those of the saving kernel, bit for bit.
+// ZC (zero controls: a launch with a NULL torques and / or res_f, pd_rollout_forward): the prefetch of each of the two -- the dof entries of
+// torques, the six res_f floats of a body -- sits behind a wave-uniform test of its pointer, and an absent one yields 0.0f into the same
+// variables.  No use is removed at compile time: every product and sum is the expression it is with loaded zeros, so the multiplies
+// that fuse are the same and the outputs are those of the launch with explicit zero tensors, bit for bit.  ZC = false folds the tests
+// to `true`: the launch with both pointers runs the code it ran before the flag existed.
 template <int SEGW, int JT, bool SPLIT, bool LOSS = false, bool QUAD = false, bool CULLW = false, bool RUNSUM = false, bool GT = false,
-          bool SAVE = true>
+          bool SAVE = true, bool ZC = false>
 __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK), CULLW ? 3 : 2) void k_rollout_fwd(PdDevModel m, RolloutArgs a) {
   static_assert(!RUNSUM || (CULLW && !QUAD), "run sums in the hit pass: the lane-per-body kernels with the cull wave");
   // TRAJC: the contact wave stores planes 0-2 of the trajectory out of the staged records (round 3 measured this a loss, when that wave's idle
@@ -936,9 +949,11 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
       n_fr = ld_uniform(a.frame_of_step, sc);
       const size_t o = (size_t)sc * a.bs * m.nqd;
       n_tgt = ldg(a.refs + o, boff_qd);   // (unconditional: the root reads the first of its own six dofs, its joint result is dropped)
-      n_act = ldg(a.torques + o, boff_qd);
-      const float *rf = a.res_f + (size_t)sc * N * 6;
-      n_rft = ldg(rf, boff_rf); n_rff = ldg(rf + 3, boff_rf);
+      // (ZC: an absent control has no base to offset -- the bases are hoisted behind the test, the old statements without the flag)
+      const float *tb = ptr_given<ZC>(a.torques) ? a.torques + o : nullptr;
+      n_act = ptr_given<ZC>(a.torques) ? ldg(tb, boff_qd) : 0.f;
+      const float *rf = ptr_given<ZC>(a.res_f) ? a.res_f + (size_t)sc * N * 6 : nullptr;
+      n_rft = ptr_given<ZC>(a.res_f) ? ldg(rf, boff_rf) : 0.f; n_rff = ptr_given<ZC>(a.res_f) ? ldg(rf + 3, boff_rf) : 0.f;
     };
     auto q_frame_out = [&](int cfr, const QState &x) {  // frame gather (dp_model.py:1231-1248)
       if (qbody) {
@@ -1193,17 +1208,19 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
     // torques: the saddr form costs more scalar instructions per array than the vector adds it saves, and running offsets instead of the
     // step x stride products overflow the scalar register file into v_readlane / v_writelane inside the loop: both built and counted)
     const size_t o = (size_t)sc * a.bs * m.nqd;
-    const float *rb = a.refs + o, *tb = a.torques + o, *rf = a.res_f + (size_t)sc * N * 6;
+    // (ZC: an absent control has no base to offset -- the arithmetic sits behind the test as well; without the flag the test is `true`)
+    const float *rb = a.refs + o, *tb = ptr_given<ZC>(a.torques) ? a.torques + o : nullptr;
+    const float *rf = ptr_given<ZC>(a.res_f) ? a.res_f + (size_t)sc * N * 6 : nullptr;
 #pragma unroll
     for (int k = 0; k < ND; ++k) {
       // (CLONE: unconditional -- the FREE root reads the first ND of its own six dofs, valid addresses, and its joint result is dropped)
       bool on = LEANA || k < ndof;
       n_tgt[k] = on ? ldg(rb + k, boff_qd) : 0.f;
-      n_act[k] = on ? ldg(tb + k, boff_qd) : 0.f;
+      n_act[k] = on && ptr_given<ZC>(a.torques) ? ldg(tb + k, boff_qd) : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const float2 v = ldg2(rf + 2 * k, boff24);
+      const float2 v = ptr_given<ZC>(a.res_f) ? ldg2(rf + 2 * k, boff24) : make_float2(0.f, 0.f);
       n_rf[2 * k] = v.x; n_rf[2 * k + 1] = v.y;
     }
   };
@@ -1607,7 +1624,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     };
     auto load_ctrl = [&](int step, float &tgt, float &act) {
       const size_t o = (size_t)__builtin_amdgcn_readfirstlane(step > 0 ? step : 0) * a.bs * m.nqd;
-      tgt = rev ? ldg(a.refs + o, boff_qd) : 0.f; act = rev ? ldg(a.torques + o, boff_qd) : 0.f;
+      tgt = rev ? ldg(a.refs + o, boff_qd) : 0.f; act = rev && ptr_given<SEL>(a.torques) ? ldg(a.torques + o, boff_qd) : 0.f;
     };
     auto fetch_point = [&](int cnt, int &e, float4 &P, float4 &M) {  // entries past the count are uninitialised memory
       if (!(env_ok && l < cnt && l < PD_HITLOG - 1)) e = 0;
@@ -2108,7 +2125,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     for (int k = 0; k < ND; ++k) {
       bool on = k < ndof;
       n_tgt[k] = on ? ldg(a.refs + o + k, boff_qd) : 0.f;
-      n_act[k] = on ? ldg(a.torques + o + k, boff_qd) : 0.f;
+      n_act[k] = on && ptr_given<SEL>(a.torques) ? ldg(a.torques + o + k, boff_qd) : 0.f;
     }
   };
   if (a.nsteps > 0) load_step(a.nsteps - 1);
@@ -2533,7 +2550,7 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
           pose[0] = ldg4(tj, boff * 4u); pose[1] = ldg4(tj + (size_t)4 * N, boff * 4u);
           pose[2] = ldg4(tj, boff_p * 4u); pose[3] = ldg4(tj + (size_t)4 * N, boff_p * 4u); pose[4] = ldg4(tj + (size_t)8 * N, boff_p * 4u);
           const size_t o = (size_t)sc * a.bs * m.nqd;
-          tgt_n = ldg(a.refs + o, boff_qd); act_n = ldg(a.torques + o, boff_qd);
+          tgt_n = ldg(a.refs + o, boff_qd); act_n = ptr_given<SEL>(a.torques) ? ldg(a.torques + o, boff_qd) : 0.f;
         }
       };
       if (a.nsteps > 0) load_next(a.nsteps - 1);
@@ -2582,7 +2599,7 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
         for (int k = 0; k < ND; ++k) {
           const bool on = CLONE3 || (is_body && k < ndof);  // (CLONE3: unconditional; the root reads the first of its own dofs and never uses them)
           n_tgt[k] = on ? ldg(a.refs + o + k, boff_qd) : 0.f;
-          n_act[k] = on ? ldg(a.torques + o + k, boff_qd) : 0.f;
+          n_act[k] = on && ptr_given<SEL>(a.torques) ? ldg(a.torques + o + k, boff_qd) : 0.f;
         }
       };
       if (a.nsteps > 0) load_next(a.nsteps - 1);  // (a zero-step rollout has no controls: null pointers)
@@ -2934,8 +2951,9 @@ __global__ __launch_bounds__(PD_FK_BLOCK) void k_seeds_fk(PdDevModel m, SeedsFkA
 // cfg: the host's choice for this launch (pd_args.h: pd_launch_cfg) -- kernel variant, workgroups, threads, LDS bytes
 // GT: the model keeps its contact tables in global memory (m.global_tables) -- the rollout kernels that copy them into LDS have a GT
 // instantiation, the rest (revolute-only adjoint kernels, FK) read no table from LDS and are the same kernels either way
-// The forward variants, each with (SAVE) and without (forward-only) the stores of the trajectory the adjoint reads
-template <int JT, bool GT, bool SAVE>
+// The forward variants, each with (SAVE) and without (forward-only) the stores of the trajectory the adjoint reads, and each of those
+// with the loads of torques / res_f as ever and behind tests of their pointers (ZC: a launch with a NULL one)
+template <int JT, bool GT, bool SAVE, bool ZC>
 static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
   const dim3 g(cfg.nblocks), t(cfg.threads);
   const size_t lds = cfg.lds;
@@ -2943,11 +2961,11 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
   if (cfg.kernel == PD_KV_FWD_QUAD) {
     if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
       if (cfg.roles == 3) {  // with the cull wave
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE>), g, t, lds, st, m, a);
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
       } else {
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE>), g, t, lds, st, m, a);
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
       }
       return hipGetLastError();
     } else {
@@ -2957,11 +2975,11 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
   if (cfg.roles == 3) {  // wave-specialised forward with the cull wave (revolute-only robots)
     if constexpr (JT == PD_JT_REVOLUTE) {
       if (cfg.groups >= PD_BWAVES) {  // full workgroups: per-body sums in registers (RUNSUM)
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE>), g, t, lds, st, m, a);
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE, ZC>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE, ZC>), g, t, lds, st, m, a);
       } else {
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE>), g, t, lds, st, m, a);
+        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
+        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
       }
       return hipGetLastError();
     } else {
@@ -2971,13 +2989,13 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
   // (unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation)
   if (loss) {  // trajectory loss at the frame states (pd_rollout_forward_traj_loss)
     if (cfg.kernel != PD_KV_FWD_SPLIT) return hipErrorInvalidValue;  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
-    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE>), g, t, lds, st, m, a);
+    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
   } else if (cfg.kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND)
-    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE>), g, t, lds, st, m, a);
+    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
   else if constexpr (GT)  // (no unsplit instantiation with global tables -- it does not survive the register allocator: a model with its
     return hipErrorInvalidValue;  // tables in global memory takes the split kernel at every batch size, pd_host.hip launch_cfg)
   else
-    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE>), g, t, lds, st, m, a);
+    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE, ZC>), g, t, lds, st, m, a);
   return hipGetLastError();
 }
 
@@ -3009,12 +3027,16 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
     case PD_K_ROLLOUT_FWD: {
       // no workspace: the forward-only kernels (a rollout of no steps saves nothing either way and keeps the saving kernel: pd_host.hip)
       const RolloutArgs &a = *(const RolloutArgs *)args;
-      return a.ws || a.nsteps == 0 ? launch_fwd<JT, GT, true>(m, a, cfg, st) : launch_fwd<JT, GT, false>(m, a, cfg, st);
+      // a NULL torques / res_f ("all zeros") with steps to run: the ZC twins; both given, the kernels as ever
+      if (a.nsteps > 0 && (!a.torques || !a.res_f))
+        return a.ws ? launch_fwd<JT, GT, true, true>(m, a, cfg, st) : launch_fwd<JT, GT, false, true>(m, a, cfg, st);
+      return a.ws || a.nsteps == 0 ? launch_fwd<JT, GT, true, false>(m, a, cfg, st) : launch_fwd<JT, GT, false, false>(m, a, cfg, st);
     }
     case PD_K_ROLLOUT_BWD: {
-      // a per-step gradient declined (NULL g_torques / g_res_f / g_refs): the selective twin (SEL); all three given, the kernel as ever
+      // a per-step gradient declined (NULL g_torques / g_res_f / g_refs) or an absent torques (NULL: all zeros): the selective twin (SEL),
+      // which carries the run-time pointer tests; all four given, the kernel as ever
       const RolloutArgs &a = *(const RolloutArgs *)args;
-      return a.nsteps > 0 && (!a.g_torques || !a.g_res_f || !a.g_refs) ? launch_bwd<JT, GT, true>(m, a, cfg, st) : launch_bwd<JT, GT, false>(m, a, cfg, st);
+      return a.nsteps > 0 && (!a.g_torques || !a.g_res_f || !a.g_refs || !a.torques) ? launch_bwd<JT, GT, true>(m, a, cfg, st) : launch_bwd<JT, GT, false>(m, a, cfg, st);
     }
 #if PD_POLICY == 0  // (the host routes the FK kinds to these launchers whatever the model's policy)
     case PD_K_FK_FWD:
@@ -3036,27 +3058,27 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
   return hipGetLastError();
 }
 
-template <int JT, bool GT, bool SAVE>
+template <int JT, bool GT, bool SAVE, bool ZC>
 static hipError_t set_lds_fwd(int bytes) {
   hipError_t e;
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   if constexpr (!GT)
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
   }
   if constexpr (JT == PD_JT_REVOLUTE) {  // ... with the cull wave
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     if constexpr (PD_SEGW == 64) {
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
+      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
     }
   }
-  return hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 template <int JT, bool GT, bool SEL>
@@ -3076,8 +3098,10 @@ static hipError_t set_lds_bwd(int bytes) {
 template <int JT, bool GT>
 static hipError_t set_lds_gt(int bytes) {
   hipError_t e;
-  if ((e = set_lds_fwd<JT, GT, true>(bytes))) return e;
-  if ((e = set_lds_fwd<JT, GT, false>(bytes))) return e;  // (the forward-only twins)
+  if ((e = set_lds_fwd<JT, GT, true, false>(bytes))) return e;
+  if ((e = set_lds_fwd<JT, GT, false, false>(bytes))) return e;  // (the forward-only twins)
+  if ((e = set_lds_fwd<JT, GT, true, true>(bytes))) return e;    // (the zero-controls twins of both)
+  if ((e = set_lds_fwd<JT, GT, false, true>(bytes))) return e;
   if ((e = set_lds_bwd<JT, GT, false>(bytes))) return e;
   if ((e = set_lds_bwd<JT, GT, true>(bytes))) return e;  // (the selective twins)
 #if PD_POLICY == 0

@@ -51,7 +51,10 @@ class HostFrames:
 
 
 def _f32c(t):
-    """detached, float32, contiguous -- without touching a tensor that already is (the usual case; three tensor ops saved per input)"""
+    """detached, float32, contiguous -- without touching a tensor that already is (the usual case; three tensor ops saved per input).
+    None stays None: an absent ``torques`` / ``res_f`` (all zeros; the library gets a NULL pointer and reads nothing for it)."""
+    if t is None:
+        return None
     t = t.detach()
     return t if (t.dtype is torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
 
@@ -198,7 +201,7 @@ def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos
     gradients to compute -- only they get their full [T] tensor, whose step slices the segments' selective launches fill."""
     q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = inp
     _, segments = checkpoint_plan(nsteps, frame2step, K)
-    dev, N = torques.device, bs * dm.nb
+    dev, N = refs.device, bs * dm.nb
     want = hip_backend.grad_want(want)
     g = dm._alloc_grads(bs, nsteps, dev, want=want)
     tmp = {k: torch.empty_like(g[k]) for k in _SUMMED}
@@ -209,7 +212,7 @@ def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos
         start, end, local, idx, has_carry = segments[i]
         n = end - start
         seg_ws = ws[: dm.workspace_floats(bs, n)]
-        ctl = (torques[start:end], res_f[start:end], refs[start:end])
+        ctl = tuple(None if t is None else t[start:end] for t in (torques, res_f, refs))  # (an absent control: nothing to slice)
         init = dict(state0=states[i - 1]) if i > 0 else {}
         q0 = (None, None) if i > 0 else (q_init, qd_init)
         dm.rollout_forward(bs, n, dt, *q0, *ctl, ke, kd, inv_m, inertia, inv_inertia, frame2step=[], want_forces=False,
@@ -238,6 +241,10 @@ def _checkpoint_backward(dm, bs, nsteps, dt, inp, frame2step, K, states, adj_pos
 class ForwardWarp(torch.autograd.Function):
     """ForwardWarp.apply(q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_mass,
     body_inv_mass, body_inertia, body_inv_inertia, self) -> (wp_pos [F,bs*nb,7], wp_vel [F,bs*nb,6]).
+
+    ``torques`` and ``res_f`` may each be None -- "all zeros", here and in ForwardWarpState / ForwardWarpTrajLoss / ForwardWarpTrajLossFK:
+    nothing is allocated or read for an absent one, outputs and gradients are those of the call with zero tensors bit for bit, and the
+    gradient returned for its position is None.
 
     Read from ``self``: ``env``, ``steps_idx``, ``frame2step``, ``dt``, ``num_envs``; optionally ``checkpoint_steps``.
     Written to ``self``: ``grfs``, ``jafs`` (lists of F tensors [bs*nb,6]), ``sim_trajs`` (F numpy [nb,7], env 0).
@@ -299,7 +306,7 @@ class ForwardWarp(torch.autograd.Function):
         # stores the gradients (pd_rollout_backward): no pass over the tensors here
         return (g["q_init"], g["qd_init"], _view(g, "torques", torques), _view(g, "res_f", res_f),
                 _view(g, "refs", refs), g["target_ke"], g["target_kd"],
-                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=torques.device), g["body_inv_mass"],
+                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=refs.device), g["body_inv_mass"],
                 g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
 
 
@@ -345,7 +352,7 @@ class ForwardWarpState(torch.autograd.Function):
         g0 = _remove_nan(g["state0"])
         return (g0[:, :7].reshape(ctx.q0_shape), g0[:, 7:].reshape(ctx.qd0_shape), _view(g, "torques", torques), _view(g, "res_f", res_f),
                 _view(g, "refs", refs), g["target_ke"], g["target_kd"],
-                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=torques.device), g["body_inv_mass"],
+                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=refs.device), g["body_inv_mass"],
                 g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
 
 

@@ -328,7 +328,9 @@ class DeviceModel:
         no rollout_backward can follow.
         state0= (q_init and qd_init None): a RESUMED rollout -- state 0 is the body state state0, [bs*nb, 13] = (p, q xyzw, w, v) or the
         pair (body_q [bs*nb, 7], body_qd [bs*nb, 6]), e.g. the rows of an earlier rollout's frame at its last state, taken as they are
-        (no FK, no re-normalisation): the rollout continues that one bit for bit."""
+        (no FK, no re-normalisation): the rollout continues that one bit for bit.
+        torques, res_f: each may be None = all zeros -- the library gets NULL, nothing is allocated or read for it, every output is the
+        bits of the launch with a zero tensor; its size is then not checked at all, the step count is checked on refs alone."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         if state0 is not None:
             if q_init is not None or qd_init is not None:
@@ -366,7 +368,8 @@ class DeviceModel:
         fk = (joint_q [Ff, bs_f, nq], joint_qd [Ff, bs_f, nqd]): the FK of the control reference rides on the reduce_loss launch
         (``pd_rollout_forward_traj_loss_fk``); tl then also holds fk_body_q [bs_f, Ff, nb, 7] and fk_body_qd [bs_f, Ff, nb, 6].
         save_trajectory=False: forward-only -- no workspace and no seeds (ws, seed_pos and seed_gt None; a rollout of no steps keeps its
-        seeds, it has no trajectory to drop), the same bits everywhere else; no rollout_backward_traj_loss can follow."""
+        seeds, it has no trajectory to drop), the same bits everywhere else; no rollout_backward_traj_loss can follow.
+        torques, res_f: each may be None = all zeros, as in rollout_forward (sizes then checked on refs alone)."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         dev = q_init.device
         f2s, nframes = self._f2s(frame2step)
@@ -414,7 +417,7 @@ class DeviceModel:
         fk = (joint_q [Ff, bs_f, nq], joint_qd [Ff, bs_f, nqd], adj_body_q [bs_f, Ff, nb, 7], adj_body_qd [bs_f, Ff, nb, 6]): the FK
         adjoint rides on the seeds launch (``pd_rollout_backward_traj_loss_fk``); g then also holds fk_joint_q [Ff, bs_f, nq] and
         fk_joint_qd [Ff, bs_f, nqd] (with ForwardKinematics.backward's post-processing).
-        want: as rollout_backward."""
+        want: as rollout_backward.  torques: None exactly when the forward's was, as in rollout_backward."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         dev = q_init.device
         f2s, nframes = self._f2s(frame2step)
@@ -494,7 +497,10 @@ class DeviceModel:
         of that rollout's frame at its last state, and the single launch does not scrub it between steps either.
         want: which of the per-step gradients GRAD_NAMES = ("torques", "res_f", "refs") to compute (default: all three).  One that is
         not named is neither allocated nor computed -- the library gets a NULL pointer and runs its selective adjoint kernel, which
-        stores nothing for it -- and is not a key of the returned dict; every other gradient is the all-three launch's, bit for bit."""
+        stores nothing for it -- and is not a key of the returned dict; every other gradient is the all-three launch's, bit for bit.
+        torques: None = all zeros, EXACTLY when the forward's was (a mismatch cannot be detected; the step count is then checked on refs
+        alone).  The gradients stay independent of it: g["torques"] / g["res_f"] of an absent input are computed when wanted, the bits of
+        the launch with zero tensors."""
         nb, nq, nqd = self.nb, self.nq, self.nqd
         want = grad_want(want)
         resumed = state0 is not None

@@ -79,6 +79,8 @@ class phys_model(nn.Module):
         if name not in robots.PRESETS:
             raise NotImplementedError(name)
         self.in_bullet = False
+        # True: with skip_zeroed_mlps the all-zero torques / res_f are not made at all -- get_net_pred hands the rollout None (off by default)
+        self.absent_zero_controls = False
         # articulation template: compiled from the URDF when its directory is given, else the committed npz
         if urdf_root is not None:
             env, _, info = robots.make_env(name, urdf_root, 1, device="cpu")
@@ -320,8 +322,15 @@ class phys_model(nn.Module):
             # only applies its weight decay to them).  Same values without the two MLPs' forward and backward -- 2 of the 5 time-MLPs,
             # ~40 % of an iteration's GEMMs: zeros here, zero gradients attached in backward() / iteration() (_attach_zero_grads).
             # skip_zeroed_mlps = False evaluates them as the reference does (tests compare the two bit for bit).
-            torques = torch.zeros(bs, nstep, 6 + self.n_dof, dtype=torch.float32, device=steps_fr.device)
-            res_f = torch.zeros(bs, nstep, 6 * self.n_links, dtype=torch.float32, device=steps_fr.device)
+            # absent_zero_controls = True: the zeros themselves are not made either -- None: the rollout takes an absent torques / res_f as
+            # all zeros (a NULL pointer in the C ABI: nothing allocated, nothing read, the bits of the launch with zero tensors), and
+            # forward() gives the two regularisers their value, 0 (tests compare the two settings bit for bit).  Off by default: callers
+            # that hook the rollout launch to read its ten input tensors (tests/test_gpu_workload.py does) keep finding ten tensors.
+            if self.absent_zero_controls:
+                torques = res_f = None
+            else:
+                torques = torch.zeros(bs, nstep, 6 + self.n_dof, dtype=torch.float32, device=steps_fr.device)
+                res_f = torch.zeros(bs, nstep, 6 * self.n_links, dtype=torch.float32, device=steps_fr.device)
         else:
             shared = {}
             torques = self.torque_mlp(t, shared)
@@ -361,7 +370,9 @@ class phys_model(nn.Module):
         queried_q = torch.cat([queried_q, queried_ja], -1).permute(1, 0, 2).reshape(nstep, -1)
         queried_qd = queried_qd.permute(1, 0, 2).reshape(nstep, -1)
         ref_ja = torch.cat([torch.zeros_like(queried_ja[..., :1].repeat(1, 1, 6)), queried_ja], -1).permute(1, 0, 2).reshape(nstep, -1)
-        return ref_ja, queried_q, queried_qd, torques.reshape(nstep, -1), res_f.reshape(nstep, -1, 6)  # quirk (ii)
+        # (None: the absent, all-zero controls of get_net_pred)
+        return (ref_ja, queried_q, queried_qd, None if torques is None else torques.reshape(nstep, -1),
+                None if res_f is None else res_f.reshape(nstep, -1, 6))  # quirk (ii)
 
     def get_foot_height(self, state_body_q):
         """lowest ground-contact candidate per (env, frame); the reference poses the visual meshes instead (dp_model.py:574-579).
@@ -432,7 +443,7 @@ class phys_model(nn.Module):
             outseq_idx = (vidid[:, :1] - vidid) != 0
         target_position, ref_ja, queried_q, queried_qd, torques, res_f = self.get_batch_input(steps_fr)
 
-        res_fin = res_f.clone()
+        res_fin = None if res_f is None else res_f.clone()
         q_init = queried_q[0].reshape(-1)  # a VIEW of queried_q, as in the reference
         qd_init = queried_qd[0]
         if q_init_noise is None:
@@ -452,7 +463,7 @@ class phys_model(nn.Module):
         # check and is not capturable in a HIP graph; the eager and the captured iteration run this one formula (bit-identical losses)
         body_inv_inertia = (self._inv_norm_inertia()[None].repeat(n, 1, 1, 1).view(-1, 3, 3) / body_mass[..., None, None]).contiguous()
         qd_init = convert_ppr_warp(qd_init)  # quirk (i): flat vector
-        res_fin = convert_ppr_warp(res_fin)
+        res_fin = None if res_fin is None else convert_ppr_warp(res_fin)
         F_ = self.frames_per_wdw
         # loss_traj is the ONE term that back-propagates through the rollout (dp_model.py:777-779; the others use sim_position.detach()).
         # fuse_traj_loss (default): the rollout evaluates it where the frame poses are produced and the adjoint seeds itself
@@ -490,8 +501,10 @@ class phys_model(nn.Module):
         loss_dict["pos_state"] = reduce_loss_masked(loss_pos, outseq_idx)
         loss_vel = se3_loss(queried_velocity, sim_velocity.detach()).mean(-1)
         loss_dict["vel_state"] = reduce_loss_masked(loss_vel, outseq_idx)
-        loss_dict["reg_torque"] = _mean_sq(torques)
-        loss_dict["reg_res_f"] = _mean_sq(res_f)
+        # (absent controls are all zeros: the mean square is the 0.0 it was)
+        zero = lambda: torch.zeros((), dtype=torch.float32, device=ref_ja.device)
+        loss_dict["reg_torque"] = zero() if torques is None else _mean_sq(torques)
+        loss_dict["reg_res_f"] = zero() if res_f is None else _mean_sq(res_f)
         loss_dict["reg_foot"] = foot_height.pow(2).mean()
 
         total_loss = 0
@@ -604,7 +617,8 @@ class phys_model(nn.Module):
             torch.cuda.current_stream().wait_stream(side)
             st = dict(graph=graph, fs=g_fs, noise=g_noise, out=out, nan=self._pending_nan, grads=[(p, p.grad) for p in params if p.grad is not None],
                       side=dict(grfs=self.grfs, jafs=self.jafs, sim=self.sim_trajs._dev, tgt=self.target_trajs._dev, pid=self.pid_ref._dev,
-                                info=self.traj_loss_info), shape=(n, self.frames_per_wdw), weights=weights, env=self.env, replays=0)
+                                info=self.traj_loss_info), shape=(n, self.frames_per_wdw), weights=weights, env=self.env, replays=0,
+                      absent=bool(self.absent_zero_controls))   # (the graph holds the static zero buffers and their memsets, or does not)
             if validate:
                 for trial in range(2):
                     draw()
@@ -646,7 +660,7 @@ class phys_model(nn.Module):
     def _graph_usable(self):
         st = getattr(self, "_graph", None)
         return (st is not None and self.training and st["shape"] == (self.num_envs, self.frames_per_wdw) and st["env"] is self.env
-                and all(self.opts.get(k) == v for k, v in st["weights"].items()))
+                and st["absent"] == bool(self.absent_zero_controls) and all(self.opts.get(k) == v for k, v in st["weights"].items()))
 
     def iteration(self):
         """forward() + backward() of one optimisation iteration; returns forward()'s dict.  The replay of the captured graph when there is

@@ -2,7 +2,8 @@
 """One optimisation iteration of phys_model on the reference's own training window (main.py:86: 10 envs x 760 steps, 24 frames):
 eager forward() + backward() + update() against phys_model.iteration() replaying the captured HIP graph (capture_iteration) + update().
 Prints ms per iteration of both, and whether the losses of 20 iterations and the parameters after them are bit-identical.
-    python scripts/gpu_iter_graph.py [num_envs] [frames_per_wdw] [iterations]"""
+    python scripts/gpu_iter_graph.py [num_envs] [frames_per_wdw] [iterations] [--absent-zero-controls]
+--absent-zero-controls: the two skipping modes run with model.absent_zero_controls = True (no zero torques / res_f tensors at all)."""
 import importlib.util
 import os
 import sys
@@ -16,6 +17,8 @@ import torch
 from diffphys_amd.dataloader import DataLoader
 from diffphys_amd.phys_model import phys_model
 
+ABSENT = "--absent-zero-controls" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--absent-zero-controls"]
 nenv = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 fpw = int(sys.argv[2]) if len(sys.argv) > 2 else 24
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 20
@@ -28,6 +31,7 @@ for mode in ("eager-all-mlps", "eager", "graph"):
     torch.manual_seed(0); np.random.seed(0)
     model = phys_model(opts, DataLoader(opts)).cuda(); model.train()
     model.skip_zeroed_mlps = mode != "eager-all-mlps"   # False: torque_mlp / residual_f_mlp evaluated and multiplied by zero, as the reference does
+    model.absent_zero_controls = ABSENT and model.skip_zeroed_mlps
     model.reinit_envs(nenv, frames_per_wdw=fpw)
     if mode == "graph":
         t0 = time.perf_counter()
