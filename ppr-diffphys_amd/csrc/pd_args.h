@@ -9,7 +9,7 @@
 #define PD_BWAVES 4
 #define PD_BLOCK (2 * PD_BWAVES * 64)
 #define PD_FK_BLOCK (PD_BWAVES * 64)
-#define PD_BLOCK3 (3 * PD_BWAVES * 64)  // 3-role adjoint (k_rollout_bwd3): integrate, contact and joint wave per env group
+#define PD_BLOCK3 (3 * PD_BWAVES * 64)  // forward kernels with the cull wave (k_rollout_fwd CULLW): body, contact and cull wave per env group
 
 // Forward sweeps log their hit list (count + up to PD_HITLOG-1 entries) so that the adjoint replays it instead of
 // repeating the three cull levels; count -1 = did not fit, the adjoint then culls again for that wave.
@@ -25,14 +25,14 @@ enum { PD_K_ROLLOUT_FWD = 0, PD_K_ROLLOUT_BWD = 1, PD_K_FK_FWD = 2, PD_K_FK_BWD 
 // Which rollout launches run wave-specialised -- shared by the kernel TUs and the host.
 //   forward : revolute-only robots always; other joint mixes while a CU holds at most one full workgroup (the latency
 //             regime: human at 1024 envs -32 %), else the unsplit kernel packs twice as many body waves per SIMD
-//   adjoint : revolute-only robots the 2-role kernel (body + contact wave); other joint mixes the 2-role k_rollout_bwd3
+//   adjoint : revolute-only robots the 2-role kernel k_rollout_bwd (body + contact wave); other joint mixes the 2-role k_rollout_bwd3
 //             (integrate + contacts wave, joint wave).  The variants that were measured and rejected (3-role, early hand-over, unsplit
-//             compound adjoint: EXPERIMENTS.md) left the sources in round 5; `git log` has them (commit 837bfbd and before).
+//             compound adjoint: EXPERIMENTS.md) are not in the sources: no template flag, no PD_KV_* value; `git log` has them.
 constexpr bool pd_split(int jt) { return jt == PD_JT_REVOLUTE; }
 // the specialised instantiations (one joint type) are only launched for PLAIN models: non-FREE joints all hang on a body, child
 // joint frames are not rotated (pd_host.hip)
 constexpr bool pd_parented(int jt) { return jt == PD_JT_REVOLUTE || jt == PD_JT_COMPOUND; }
-enum { PD_KV_FWD_SPLIT = 0, PD_KV_FWD_UNSPLIT, PD_KV_BWD_2ROLE, PD_KV_BWD_2ROLE_EARLY, PD_KV_BWD_3ROLE, PD_KV_BWD3_2ROLE, PD_KV_BWD_UNSPLIT, PD_KV_FK,
+enum { PD_KV_FWD_SPLIT = 0, PD_KV_FWD_UNSPLIT, PD_KV_BWD_2ROLE, PD_KV_BWD3_2ROLE, PD_KV_FK,
        PD_KV_FWD_QUAD, PD_KV_BWD_QUAD };  // quad-lane (four lanes per body) small-batch kernels, 64-lane mapping, revolute-only plain models
 struct PdLaunchCfg {
   int kernel;    // PD_KV_*
@@ -66,7 +66,7 @@ inline int pd_fwd_cull_cap(int nb, int segw, int list_cap, int env_lds_floats, i
   return env_lds_floats - (spec_off + 8 * nb + 4 + list_cap + 8 * segw + 6 * segw + 8 * segw);
 }
 inline int pd_variant_roles(int kv) {
-  return kv == PD_KV_BWD_3ROLE ? 3 : ((kv == PD_KV_FWD_UNSPLIT || kv == PD_KV_BWD_UNSPLIT || kv == PD_KV_FK) ? 1 : 2);
+  return (kv == PD_KV_FWD_UNSPLIT || kv == PD_KV_FK) ? 1 : 2;
 }
 
 #define PD_TRAJ_FLOATS 20  // floats of saved trajectory per body-step: 5 float4 planes (pd_kernels.hip: PD_TRAJ_G)

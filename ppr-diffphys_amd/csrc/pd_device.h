@@ -694,7 +694,7 @@ PD_DEV void joint_fwd(const PdDevModel &m, const BodyConst &c, const BodyState &
 // Two halves: joint_adj_prep recomputes everything that depends on the stored state and the controls only (the joint
 // frames and errors, and for a COMPOUND joint the whole forward pass: angle decomposition, axes, PD forces) -- the
 // role-split adjoint kernel runs it on the joint wave BEFORE the wrench adjoints exist -- and joint_adj_apply is the part
-// that needs them.  joint_adj = prep + apply.
+// that needs them.  The joint's adjoint = prep + apply.
 struct JointPrep {
   JointCtx j;
   v3 f_raw, f_total;
@@ -877,20 +877,11 @@ PD_DEV void joint_adj_apply(const PdDevModel &m, const BodyConst &c, const BodyS
   }
 }
 
-template <int JT, bool HP = false>
-PD_DEV void joint_adj(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, const float *rec, const float *tgt,
-                      const float *act, const float *ke, const float *kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own,
-                      BodyAdj &par, float *a_tgt, float *a_act, float *a_ke, float *a_kd) {
-  JointPrep P;
-  joint_adj_prep<JT, HP>(m, c, s, rc_c, rec, tgt, act, ke, kd, P);
-  joint_adj_apply<JT, HP>(m, c, s, P, tgt, act, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, a_tgt, a_act, a_ke, a_kd);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Revolute joint adjoint in two halves (wave-specialised adjoint kernel): rev_forward recomputes everything that depends
 // on the stored state and the controls only -- it runs on the otherwise idle contact wave and is handed over through
 // LDS -- and rev_adjoint, on the body wave, is the part that needs the wrench adjoints.  Together they equal the
-// revolute branch of joint_adj.
+// revolute branch of joint_adj_prep + joint_adj_apply.
 #define PD_JC 23  // floats of the hand-over record (odd stride)
 #define PD_QPRE 22  // floats per LANE of the quad-lane adjoint's state-only hand-over (contact wave -> body wave, [field][64 lanes]): s (4), t0, f0,
                     // clamp mask, rc, rotm rows (3) and columns (3), the forward values of integrate_bodies' adjoint (QIntTmp: wb, Iwb, tb, u, w1, il, r1), pad

@@ -272,8 +272,8 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
   d.env_lds_rec2 = (segw == 64 && jt == PD_JT_REVOLUTE && nb <= 16) ? PD_QGEN * (((nb * (4 + PD_REC) + 31) / 32) * 32 + PD_QPRE * 64 + d.env_lds_jc) : 0;
   d.env_lds_bwd3 = ((nb * (2 * (4 + PD_REC) + PD_W6 + 3 * PD_ADJ + PD_GACC) + PD_GACC + PD_ADJ + std::max(ntiles, 2 * nb) + 8 * segw + PD_ADJ * segw + 3) / 4) * 4 + 4;
   d.env_lds_bwd3 += (16 - d.env_lds_bwd3 % 32 + 32) % 32;  // env stride 16 mod 32, as above
-  // revolute-only: 2-role kernel (+ joint hand-over records) or the 3-role one, no tables; other joint mixes: the 2-role
-  // k_rollout_bwd3 with the contact tables in LDS (or the unsplit kernel, A/B only)
+  // revolute-only: 2-role kernel (+ joint hand-over records), no tables; other joint mixes: the 2-role k_rollout_bwd3 with the
+  // contact tables in LDS  (the bound keeps the terms of the variants that are gone: the sizes a model is refused at do not move)
   const size_t lds_rollout_bwd = jt == PD_JT_REVOLUTE
                                      ? (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4
                                      : lds_tab + (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats) * 4;
@@ -364,9 +364,8 @@ static PdLaunchCfg launch_cfg(const pd_model *m, int kind, int n_envs, bool loss
   c.threads = c.roles * c.groups * 64;
   const size_t envs = (size_t)c.groups * epw;
   switch (c.kernel) {
-    case PD_KV_FWD_SPLIT: case PD_KV_FWD_UNSPLIT: case PD_KV_BWD_UNSPLIT: c.lds = tab + envs * d.env_lds_floats * 4; break;
-    case PD_KV_BWD_2ROLE: case PD_KV_BWD_2ROLE_EARLY: c.lds = envs * (d.env_lds_floats + 2 * d.env_lds_jc) * 4; break;
-    case PD_KV_BWD_3ROLE: c.lds = envs * d.env_lds_bwd3 * 4; break;
+    case PD_KV_FWD_SPLIT: case PD_KV_FWD_UNSPLIT: c.lds = tab + envs * d.env_lds_floats * 4; break;
+    case PD_KV_BWD_2ROLE: c.lds = envs * (d.env_lds_floats + 2 * d.env_lds_jc) * 4; break;
     case PD_KV_BWD3_2ROLE: c.lds = tab + envs * d.env_lds_bwd3 * 4; break;
     default: c.lds = m->lds_fk; break;
   }

@@ -63,7 +63,7 @@ typedef const __attribute__((address_space(4))) int *pd_const_int_p;  // constan
 // and the loop pays a 64-bit vector add per access plus the scalar chain that feeds it.  PD_OPAQUE_V / _S make a value opaque where they
 // stand (no instruction: an empty asm that "updates" the register), which keeps the two halves apart until selection (round 6).
 #define PD_OPAQUE_V(x) asm volatile("" : "+v"(x))
-#define PD_OPAQUE_S(x) do { if constexpr (CLONE && SPLIT && SEGW < 64) asm volatile("" : "+s"(x)); } while (0)  // (the unsplit instantiations keep these bases in vector registers, and the 64-lane segment's instantiation with all of them forced does not compile -- "illegal VGPR to SGPR copy": not forced there)
+#define PD_OPAQUE_S(x) do { if constexpr (CLONE && SEGW < 64) asm volatile("" : "+s"(x)); } while (0)  // (k_rollout_fwd's body wave only -- CLONE is its "wave-specialised, plain model": the unsplit instantiations keep these bases in vector registers, and the 64-lane segment's instantiation with all of them forced does not compile -- "illegal VGPR to SGPR copy": not forced there)
 PD_DEV int ld_uniform(const int *p, int i) { return ((pd_const_int_p)(unsigned long long)p)[i]; }  // read-only input, wave-uniform index
 PD_DEV float ldg(const float *ubase, unsigned boff) { return *(const float *)((const char *)ubase + boff); }
 PD_DEV void stg(float *ubase, unsigned boff, float v) { *(float *)((char *)ubase + boff) = v; }
@@ -1514,8 +1514,8 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
 }
 
 // =============================================================================================
-// EARLY (SPLIT only): hand-over A is signalled from inside the adjoint of integrate_bodies, as soon as the wrench adjoint
-// exists (integrate_adj2), instead of after it.
+// Adjoint rollout of revolute-only plain models (the headline Laikago path), wave-specialised like their forward kernel: a body wave and a
+// contact wave per group of 64/SEGW envs.  (Other joint mixes: k_rollout_bwd3 below.)
 #ifdef PD_KNOCK
 #undef pair_wait
 #if !(PD_KNOCK & 16)
@@ -1535,13 +1535,13 @@ __device__ __forceinline__ bool grad_wanted(const float *g) {
   else return true;
 }
 
-template <int SEGW, int JT, bool SPLIT, bool EARLY = false, bool QUAD = false, bool SEL = false>
-__global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutArgs a) {
+template <int SEGW, int JT, bool QUAD = false, bool SEL = false>
+__global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutArgs a) {
+  static_assert(JT == PD_JT_REVOLUTE, "the wave-specialised adjoint of revolute-only plain models: every jointed body is a revolute joint on a parent body");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
-  constexpr int ND = (JT & PD_JT_COMPOUND) ? 3 : 1;
-  const int bw = (int)blockDim.x / (QUAD ? 192 : (SPLIT ? 128 : 64));  // env groups per workgroup (host's choice per launch)
-  const int role = SPLIT ? (int)(threadIdx.x >> 6) / bw : 0;  // wave-uniform: 0 body wave, 1 contact wave, 2 (QUAD) state wave
+  const int bw = (int)blockDim.x / (QUAD ? 192 : 128);  // env groups per workgroup (host's choice per launch)
+  const int role = (int)(threadIdx.x >> 6) / bw;  // wave-uniform: 0 body wave, 1 contact wave, 2 (QUAD) state wave
   const bool contact_wave = role != 0;
   [[maybe_unused]] const int knock_role = role;
   const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6) % bw;
@@ -1556,22 +1556,20 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
   // itself was measured slower at every batch size -- EXPERIMENTS.md round 3 -- and is gone from the sources since round 5)
 
   SweepTables tabs;
-  const int env_stride = m.env_lds_floats + (SPLIT ? 2 * m.env_lds_jc : 0) + (QUAD ? m.env_lds_rec2 : 0);
-  float *scratch = lds_setup<!SPLIT>(m, smem, tabs, wave * EPW + seg, env_stride);
+  const int env_stride = m.env_lds_floats + 2 * m.env_lds_jc + (QUAD ? m.env_lds_rec2 : 0);
+  float *scratch = lds_setup<false>(m, smem, tabs, wave * EPW + seg, env_stride);
   float4 *cull = (float4 *)scratch;
   // cslot: nb + 1 records, the last one stays zero and stands in for "no child" (the gather then needs no predicates)
   float *rec = scratch + 4 * nb, *adjf = rec + nb * PD_REC, *cslot = adjf + nb * PD_W6, *cacc = cslot + (nb + 1) * PD_ADJ;
   int *list = (int *)(cacc + nb * PD_ADJ), *hits = list + m.list_cap;
   float *slot = (float *)(hits + PD_HIT_CAP_TILES * SEGW);
-  // SPLIT: revolute joint hand-over records, PD_JC floats per body, two generations (by step parity: the contact wave
+  // revolute joint hand-over records, PD_JC floats per body, two generations (by step parity: the contact wave
   // writes step k - 1's while the body wave may still read step k's)
   float *jc = scratch + m.env_lds_floats;
   // pair signals: the spare words at the end of the first env's area
   int *sig = (int *)(scratch - (size_t)seg * env_stride + m.env_lds_floats - 4);
-  if (SPLIT) {
-    if (lane == 0 && !contact_wave) { sig[0] = 0; sig[1] = 0; sig[2] = 0; sig[3] = 0; }
-    __syncthreads();
-  }
+  if (lane == 0 && !contact_wave) { sig[0] = 0; sig[1] = 0; sig[2] = 0; sig[3] = 0; }
+  __syncthreads();
   PD_KNOCK_EXIT(false, knock_role);
   if constexpr (QUAD) {
     if (!env_ok) return;  // one env per wave pair: a pair past the batch has nothing to do (no workgroup barrier follows)
@@ -1602,7 +1600,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     }
     adj_store(out, o);
   };
-  if (SPLIT && contact_wave) {
+  if (contact_wave) {
     // ---- contact wave.  Per step:
     //   .. A  : (idle time of the old design) nothing here waits for the body wave: fetch the hit list the forward
     //           sweep logged for the NEXT iteration, the points / materials of this iteration's hits, and the stored
@@ -1709,7 +1707,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
           if (rev) {
             const qt q_c = Q4(pose[0].x, pose[0].y, pose[0].z, pose[0].w), qp = Q4(pose[2].x, pose[2].y, pose[2].z, pose[2].w);
             const v3 w_c = V3(pose[1].x, pose[1].y, pose[1].z), pp = V3(pose[4].x, pose[4].y, pose[4].z), w_p = V3(pose[3].x, pose[3].y, pose[3].z);
-            rev_cache_store(jcq + g3 * m.env_lds_jc + b * PD_JC, rev_forward<pd_parented(JT)>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
+            rev_cache_store(jcq + g3 * m.env_lds_jc + b * PD_JC, rev_forward<true>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
           }
           q_pre(npl_c, g3);
           load_ctrl(step - 1, tgt_c, act_c); load_pose(step - 1, pose); load_planes(step - 1, npl_c);
@@ -1733,7 +1731,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
         const qt q_c = Q4(pose[0].x, pose[0].y, pose[0].z, pose[0].w), qp = Q4(pose[2].x, pose[2].y, pose[2].z, pose[2].w);
         const v3 w_c = V3(pose[1].x, pose[1].y, pose[1].z), pp = V3(pose[4].x, pose[4].y, pose[4].z), w_p = V3(pose[3].x, pose[3].y, pose[3].z);
         float *dst = jc + (step & 1) * m.env_lds_jc + b * PD_JC;
-        rev_cache_store(dst, rev_forward<pd_parented(JT)>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
+        rev_cache_store(dst, rev_forward<true>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
       }
       STAMP(8);
       // request everything the next iteration needs; nothing loaded here is touched before the next PD_WAIT_VMEM
@@ -1812,7 +1810,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     return;
   }
   if constexpr (QUAD) {
-    static_assert(SEGW == 64 && SPLIT && !EARLY && JT == PD_JT_REVOLUTE, "quad-lane body wave: one env per wave, revolute-only plain models");
+    static_assert(SEGW == 64, "quad-lane body wave: one env per wave");
     // ================= body wave, four lanes per body (see k_rollout_fwd): the reverse sweep of dp_model.py:1251-1400
     const int qb = lane >> 2, qc = lane & 3, bb = qb < nb ? qb : nb - 1, qv = qc < 3 ? qc : 2;
     // round 6 (see the forward kernel's quad-lane loop): waves past the batch have left, idle quads clone the env's last body, lane 3 of a quad
@@ -2081,6 +2079,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     }
     return;
   }
+  constexpr int ND = 1;  // dofs of a revolute joint (the per-dof values stay one-element arrays: as scalars the kernel compiles to other code)
   const size_t idx = (size_t)ec * nb + b;
   const int ndof = c.type == PD_JOINT_REVOLUTE ? 1 : (c.type == PD_JOINT_COMPOUND ? 3 : 0);
 
@@ -2112,7 +2111,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
   const bool zero_by_lanes = m.jtype[0] == PD_JOINT_FREE && nb >= 7;  // see the control-gradient stores below
   const unsigned boff_zero = (unsigned)((size_t)ec * m.nqd + m.qdstart[0] + (b >= 1 && b <= 6 ? b - 1 : 0)) * 4u;
   float4 n_s[PD_TRAJ_G];
-  float n_tgt[ND], n_act[ND];
+  float n_tgt[ND];  // (the applied torque enters this wave's adjoint through the contact wave's hand-over record only)
   int n_fr = -1;  // frame seeded into state step + 1 (or -1), fetched with the state
   auto load_step = [&](int step) {
     const int sc = __builtin_amdgcn_readfirstlane(step >= 0 ? step : 0);  // keeps the address arithmetic scalar
@@ -2125,7 +2124,6 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     for (int k = 0; k < ND; ++k) {
       bool on = k < ndof;
       n_tgt[k] = on ? ldg(a.refs + o + k, boff_qd) : 0.f;
-      n_act[k] = on && ptr_given<SEL>(a.torques) ? ldg(a.torques + o + k, boff_qd) : 0.f;
     }
   };
   if (a.nsteps > 0) load_step(a.nsteps - 1);
@@ -2142,14 +2140,11 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     s.p = V3(n_s[2].x, n_s[2].y, n_s[2].z); s.v = V3(n_s[1].w, n_s[2].w, n_s[3].x);
     v3 t0 = V3(n_s[3].y, n_s[3].z, n_s[3].w), f0 = V3(n_s[4].x, n_s[4].y, n_s[4].z);
     const unsigned clamp_mask = __float_as_uint(n_s[4].w);  // which of (w, v) the forward pass clamped in this step
-    float tgt[ND], act[ND];
+    float tgt[ND];
 #pragma unroll
-    for (int k = 0; k < ND; ++k) { tgt[k] = n_tgt[k]; act[k] = n_act[k]; }
+    for (int k = 0; k < ND; ++k) tgt[k] = n_tgt[k];
     const size_t oc = (size_t)step * a.bs * m.nqd;  // uniform part; the lane part is boff_qd
     load_step(step - 1);
-    // unsplit kernels replay the forward hit list inline further down: fetch its length now, far ahead of its use
-    int *lg = a.hitlog + ((size_t)step * a.bs + ec) * PD_HITLOG;
-    const int log_cnt = (!SPLIT && env_ok) ? lg[0] : 0;
     float Rm[9];
     rotm(s.r, Rm);  // the body's rotation as a matrix: shared by the staging and the adjoint of integrate_bodies
     const v3 rc = mat_vec(Rm, c.com);
@@ -2158,26 +2153,9 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     // ---- adjoint of integrate_bodies
     BodyAdj ga = adj_zero();
     v3 adj_t0 = V3(0, 0, 0), adj_f0 = adj_t0;
-    float aR[9];  // matrix adjoint of Rm, summed over integrate_bodies and (revolute, split) the joint; converted after both
+    float aR[9];  // matrix adjoint of Rm, summed over integrate_bodies and the joint; converted after both
 #pragma unroll
     for (int k = 0; k < 9; ++k) aR[k] = 0.f;
-    if (SPLIT && EARLY) {
-      integrate_adj2(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, a.dt, gn, ga, aR, g_inv_m, g_I, g_invI, [&](v3 t, v3 f) {
-        adj_t0 = t; adj_f0 = f;
-        if (is_body) {
-          float *o = adjf + b * PD_W6;
-          o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = f.x; o[4] = f.y; o[5] = f.z;
-        }
-        pair_signal(sig, a.nsteps - step);  // A: records + wrench adjoints are staged
-      });
-      if (grad_wanted<SEL>(a.g_res_f) && is_body) {
-        float *o = a.g_res_f + (size_t)step * N * 6;  // adjoint of wp_add
-        stg2(o, boff * 6u, make_float2(NZ(adj_t0.x), NZ(adj_t0.y))); stg2(o + 2, boff * 6u, make_float2(NZ(adj_t0.z), NZ(adj_f0.x)));
-        stg2(o + 4, boff * 6u, make_float2(NZ(adj_f0.y), NZ(adj_f0.z)));
-      }
-      STAMP(1);
-      pair_wait(sig + 1, a.nsteps - step);  // the contact wave's joint hand-over records
-    } else {
     integrate_adj(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, a.dt, gn, ga, aR, adj_t0, adj_f0, g_inv_m, g_I, g_invI);
     if (is_body) {
       float *f = adjf + b * PD_W6;
@@ -2187,33 +2165,23 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
     // A: hand records + wrench adjoints to the contact wave FIRST -- at 4096 envs it is the later wave of the pair, and whatever
     // this wave does ahead of the signal delays it: with the remove_nan selects and the g_res_f stores before the signal the
     // adjoint took 0.324 ms, behind it 0.312 (same-box A/B) -- then the stores, then take its joint hand-over records
-    if (SPLIT) pair_signal(sig, a.nsteps - step);
+    pair_signal(sig, a.nsteps - step);
     if (grad_wanted<SEL>(a.g_res_f) && is_body) {
       float *o = a.g_res_f + (size_t)step * N * 6;  // adjoint of wp_add
       stg2(o, boff * 6u, make_float2(NZ(adj_t0.x), NZ(adj_t0.y))); stg2(o + 2, boff * 6u, make_float2(NZ(adj_t0.z), NZ(adj_f0.x)));
       stg2(o + 4, boff * 6u, make_float2(NZ(adj_f0.y), NZ(adj_f0.z)));
     }
-    if (SPLIT) {
-      pair_wait(sig + 1, a.nsteps - step);  // the contact wave's joint hand-over records
-    } else {
-      WAVE_SYNC();
-    }
-    }
+    pair_wait(sig + 1, a.nsteps - step);  // the contact wave's joint hand-over records
     // ---- adjoint of eval_body_joints (runs while the contact wave sweeps)
     BodyAdj par = adj_zero();
     float a_tgt[ND], a_act[ND], a_ke[ND], a_kd[ND];
 #pragma unroll
     for (int k = 0; k < ND; ++k) { a_tgt[k] = 0.f; a_act[k] = 0.f; a_ke[k] = 0.f; a_kd[k] = 0.f; }
     if (is_body && c.type != PD_JOINT_FREE) {
-      v3 gp_t = V3(0, 0, 0), gp_f = gp_t;
-      if ((SPLIT && pd_parented(JT)) || c.parent >= 0) { gp_t = ld3(adjf + c.parent * PD_W6); gp_f = ld3(adjf + c.parent * PD_W6 + 3); }
-      if (SPLIT)  // revolute only: the state-only half comes from the contact wave
-      {
-        const RevCache R = rev_cache_load(jc + (step & 1) * m.env_lds_jc + b * PD_JC);
-        rev_adjoint<pd_parented(JT)>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
-      }
-      else
-        joint_adj<JT>(m, c, s, rc, rec, tgt, act, ke, kd, adj_t0, adj_f0, gp_t, gp_f, ga, par, a_tgt, a_act, a_ke, a_kd);
+      const v3 gp_t = ld3(adjf + c.parent * PD_W6), gp_f = ld3(adjf + c.parent * PD_W6 + 3);  // (plain model: every jointed body hangs on one)
+      // the state-only half comes from the contact wave
+      const RevCache R = rev_cache_load(jc + (step & 1) * m.env_lds_jc + b * PD_JC);
+      rev_adjoint<true>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
     }
     rotm_adj(s.r, aR, ga.r);
     if (is_body) {
@@ -2253,17 +2221,7 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
       if (is_body && cid != 0xff) adj_add_from(ga, cslot + cid * PD_ADJ);
     }
     STAMP(3);
-    if (SPLIT) {
-      pair_wait(sig + 2, a.nsteps - step);  // B: contact adjoints are complete
-    } else {
-      const bool replay = __ballot(log_cnt < 0) == 0ull;
-      int log_n_unused;
-      const int cnt = log_cnt;
-      sweep_contacts<SEGW, PD_ADJ, PD_ADJ, !SPLIT>(m, tabs, c, is_body ? cull[b] : make_float4(0.f, 0.f, 1.f, 0.f), rec, cull, list, hits, slot,
-                                                   cacc, is_body, env_ok, seg, l, replay ? lg : nullptr, replay ? cnt : PD_NO_REPLAY,
-                                                   log_n_unused, contact_hit STAMP_PASS);
-      WAVE_SYNC();
-    }
+    pair_wait(sig + 2, a.nsteps - step);  // B: contact adjoints are complete
     if (is_body) {
       float *d = cacc + b * PD_ADJ;
       const float *const src[1] = {d};
@@ -2272,7 +2230,6 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
       for (int k = 0; k < PD_ADJ; ++k) d[k] = 0.f;
     }
     gn = ga;
-    if (!SPLIT) WAVE_SYNC();
     STAMP(4);
   }
   STAMP_FLUSH(a);
@@ -2324,33 +2281,30 @@ __global__ __launch_bounds__(SPLIT ? PD_BLOCK : PD_FK_BLOCK) void k_rollout_bwd(
 }
 
 // =============================================================================================
-// Role-split adjoint rollout (revolute-only robots, i.e. the headline Laikago path): THREE waves per group of 64/SEGW envs,
-// one of each per SIMD (12 waves per workgroup; <= 168 VGPRs each so that three fit a SIMD):
+// Role-split adjoint rollout of every joint mix but revolute-only (compound-only robots -- human, quad -- and the generic instantiation):
+// TWO waves per group of 64/SEGW envs, <= 256 VGPRs each (8 waves per workgroup, two per SIMD):
 //   I  integrate wave : owns the running state adjoint gn.  Per step: seeds, adjoint of integrate_bodies in two phases --
 //                       the short path to the wrench adjoint (adj_t0, adj_f0) first, published to LDS (hand-over A), then
-//                       the rest (state adjoint, inertia / inverse-mass gradients) while the other two waves work; finally
-//                       it gathers the joint wave's results (own + children, hand-over J) and the contact sums (hand-over C)
-//   J  joint wave     : the whole adjoint of eval_body_joints.  Before A it recomputes the state-only half of its joint
-//                       (rev_forward) from the stored trajectory, prefetched a step ahead, and keeps it in registers; after A
-//                       it reads the wrench adjoints and the staged records, runs rev_adjoint, publishes (own, parent)
+//                       the rest (state adjoint, inertia / inverse-mass gradients); then, while the joint wave works, the adjoint
+//                       of eval_body_contacts inline -- a replay of the forward's hit list (these robots' box contacts are a handful
+//                       of points), the tables in LDS unless GT; it stages the NEXT step's records (hand-over S) and finally
+//                       gathers the joint wave's results (own + children, hand-over J) and its own contact sums
+//   J  joint wave     : the whole adjoint of eval_body_joints.  After S it runs the state-only half (joint_adj_prep) on the staged
+//                       records, after A it reads the wrench adjoints, runs joint_adj_apply, publishes (own, parent)
 //                       contributions, then writes the control gradients off the critical path
-//   C  contact wave   : adjoint of eval_body_contacts for the logged hits, one lane per hit (as in the 2-role kernel)
-// Per step the critical chain is  phase 1 (I) -> max(rev_adjoint (J), contacts (C), phase 2 (I)) -> gather (I)  instead of
-// integrate_adj + rev_adjoint + gather on one wave.  Arithmetic and summation order are those of the 2-role kernel.
-#define PD_BWD3_BOUNDS(roles) ((roles) * PD_BWAVES * 64)
-// ROLES = 3: I, C, J waves (<= 168 VGPRs each).  ROLES = 2: the integrate wave also replays the contacts (between its phase 2
-// and the wait for the joint wave) -- compound-joint robots, whose joint adjoint needs more than 168 registers but whose
-// box contacts are a handful of points: two waves per env group, <= 256 VGPRs each.
-template <int SEGW, int JT, int ROLES, bool GT = false, bool SEL = false>  // GT: contact tables in global memory, as k_rollout_fwd; SEL: see k_rollout_bwd
-__global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevModel m, RolloutArgs a) {
+// Per step the critical chain is  phase 1 (I) -> max(joint adjoint (J), phase 2 + contacts (I)) -> gather (I)  instead of
+// integrate_adj + joint adjoint + contacts + gather on one wave.  (The "3" of the name is history: a third, contact wave and the revolute-only
+// instantiations were measured and rejected -- EXPERIMENTS.md; `git log` has them.)
+template <int SEGW, int JT, bool GT = false, bool SEL = false>  // GT: contact tables in global memory, as k_rollout_fwd; SEL: see k_rollout_bwd
+__global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd3(PdDevModel m, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
   constexpr int ND = (JT & PD_JT_COMPOUND) ? 3 : 1;
-  static_assert(ROLES == 2 || ROLES == 3, "two or three roles");
-  const int bw = (int)blockDim.x / (64 * ROLES);  // env groups per workgroup (host's choice per launch)
+  static_assert(JT != PD_JT_REVOLUTE, "revolute-only models take k_rollout_bwd");
+  const int bw = (int)blockDim.x / (64 * 2);  // env groups per workgroup (host's choice per launch)
   const int lane = threadIdx.x & 63, wave_id = threadIdx.x >> 6;
-  // 0: I (+ contacts when ROLES == 2), 1: C, 2: J   (wave-uniform)
-  const int role = ROLES == 3 ? wave_id / bw : (wave_id / bw ? 2 : 0), wave = wave_id % bw;
+  // 0: I (+ contacts), 2: J   (wave-uniform)
+  const int role = wave_id / bw ? 2 : 0, wave = wave_id % bw;
   [[maybe_unused]] const int knock_role = role;
   const int seg = lane / SEGW, l = lane % SEGW;
   const int env = (blockIdx.x * bw + wave) * EPW + seg;
@@ -2361,8 +2315,8 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
   const int nb = m.nb, N = a.bs * nb;
 
   SweepTables tabs;
-  // ROLES == 2: the (small) contact tables are copied into LDS, the inline replay then has no exposed global loads
-  float *scratch = lds_setup<ROLES == 2 && !GT>(m, smem, tabs, wave * EPW + seg, m.env_lds_bwd3);
+  // the (small) contact tables are copied into LDS, the inline replay then has no exposed global loads
+  float *scratch = lds_setup<!GT>(m, smem, tabs, wave * EPW + seg, m.env_lds_bwd3);
   // staged records and cull vectors: TWO generations, by step parity -- the integrate wave stages step - 1 while the other
   // waves still work on step (the joint wave then starts the state-only half of step - 1 without waiting for anybody)
   float4 *const cull0 = (float4 *)scratch;
@@ -2374,13 +2328,13 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
   float *adjf = rec0 + 2 * nb * PD_REC, *cslot = adjf + nb * PD_W6, *oslot = cslot + (nb + 1) * PD_ADJ;
   float *cacc = oslot + nb * PD_ADJ;
   // gacc: the integrate wave's running gradients of body_inertia / body_inv_inertia (2 x 9 per body) followed by the body's
-  // inertia and inverse inertia (2 x 9); they live here, not in registers, so that the wave stays within the 168 VGPRs
-  // three waves per SIMD allow (stride 37: odd, conflict-free)
+  // inertia and inverse inertia (2 x 9); they live here, not in registers: 36 VGPRs less across the step (stride 37: odd,
+  // conflict-free)
   float *gacc = cacc + nb * PD_ADJ;
   int *list = (int *)(gacc + (nb + 1) * PD_GACC), *hits = list + m.list_cap;
   float *slot = (float *)(hits + PD_HIT_CAP_TILES * SEGW);
-  // hand-over words (step counters) at the end of the wave's first env: [0] A (I -> J, C)   [1] J (J -> I)   [2] C (C -> I)
-  // [3] S (I -> J: records staged; joint mixes other than revolute-only)
+  // hand-over words (step counters) at the end of the wave's first env: [0] A (I -> J)   [1] J (J -> I)   [2] unused
+  // [3] S (I -> J: records staged)
   int *sig = (int *)(scratch - (size_t)seg * m.env_lds_bwd3 + m.env_lds_bwd3 - 4);
   if (role == 0) {
     if (lane == 0) { sig[0] = 0; sig[1] = 0; sig[2] = 0; sig[3] = 0; }
@@ -2399,82 +2353,8 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
   const size_t idx = (size_t)ec * nb + b;
   const unsigned boff = (unsigned)idx * 4u;  // per-lane byte offset of this body's float
 
-  // (each role loads the per-body constants itself: what one role needs is dead in the others, and a shared load ahead
-  // of the role branch kept all of them live -- 68 spilled VGPRs at the 168 three waves per SIMD allow)
-  if (ROLES == 3 && role == 1) {
-    // ---- C: contact wave
-    BodyConst c = load_body_const(m, b, ec);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) c.small_e[u] = m.small_tiles[u * 64 + (l < 64 ? l : 0)];
-    auto contact_hit = [&](const float *r, float4 P, float4 mat, float *out) {
-      const int pb = (int)(r - rec) / PD_REC;
-      BodyAdj o = adj_zero();
-      contact_point_adj(r, cull[pb], P, mat, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
-      adj_store(out, o);
-    };
-    STAMP_DECL;
-    const int lq = l < PD_HITLOG - 1 ? l : PD_HITLOG - 2;
-    const unsigned boff_lg = (unsigned)ec * (PD_HITLOG * 4u);
-    auto load_log = [&](int step, int &cnt, int &e) {
-      const int *lg = a.hitlog + (size_t)__builtin_amdgcn_readfirstlane(step > 0 ? step : 0) * a.bs * PD_HITLOG;
-      cnt = __float_as_int(ldg((const float *)lg, boff_lg)); e = __float_as_int(ldg((const float *)lg + 1, boff_lg + (unsigned)lq * 4u));
-    };
-    auto fetch_point = [&](int cnt, int &e, float4 &P, float4 &M) {  // entries past the count are uninitialised memory
-      if (!(env_ok && l < cnt && l < PD_HITLOG - 1)) e = 0;
-      P = m.pts[e & 0xffff]; M = m.materials[(e >> 16) & 0xff];
-    };
-    int cnt_c = 0, e_c = 0, cnt_n = 0, e_n = 0;
-    float4 P_c, M_c;
-    if (a.nsteps > 0) {
-      load_log(a.nsteps - 1, cnt_c, e_c);
-      load_log(a.nsteps - 2, cnt_n, e_n);
-      fetch_point(cnt_c, e_c, P_c, M_c);
-    }
-    for (int step = a.nsteps - 1; step >= 0; --step) {
-      PD_WAIT_VMEM();
-      select_step(step);
-      float4 P_n, M_n;
-      int cnt_n2, e_n2;
-      fetch_point(cnt_n, e_n, P_n, M_n);
-      load_log(step - 2, cnt_n2, e_n2);
-      const bool fast = __ballot(env_ok && (cnt_c < 0 || cnt_c > SEGW)) == 0ull;  // wave-uniform
-      const int nh = fast && env_ok ? cnt_c : 0;
-      STAMP(7);
-      pair_wait(sig, a.nsteps - step);  // A: records, cull vectors and wrench adjoints of this step are staged
-      STAMP(9);
-      if (fast) {
-        float out[PD_ADJ];
-#pragma unroll
-        for (int i = 0; i < PD_ADJ; ++i) out[i] = 0.f;
-        const int pb = l < nh ? (e_c >> 24) & 0x3f : -2;
-        if (l < nh) contact_hit(rec + pb * PD_REC, P_c, M_c, out);
-        STAMP(10);
-        bool last;
-        seg_run_sum<PD_ADJ>(out, pb, l, nh, last);
-        if (last) {  // cacc is zero (its owner clears it after reading) and a body has one run
-#pragma unroll
-          for (int i = 0; i < PD_ADJ; ++i) cacc[pb * PD_ADJ + i] = out[i];
-        }
-        STAMP(11);
-      } else {
-        float4 cv = make_float4(0.f, 0.f, 1.f, 0.f);
-        if (is_body) cv = cull[b];
-        int *lg = a.hitlog + ((size_t)step * a.bs + ec) * PD_HITLOG;
-        const bool replay = __ballot(env_ok && cnt_c < 0) == 0ull;  // -1: the list did not fit the log, cull again (whole wave)
-        int log_n_unused;
-        sweep_contacts<SEGW, PD_ADJ, PD_ADJ, false>(m, tabs, c, cv, rec, cull, list, hits, slot, cacc, is_body, env_ok, seg, l,
-                                                    replay ? lg : nullptr, replay ? (env_ok ? cnt_c : 0) : PD_NO_REPLAY, log_n_unused,
-                                                    contact_hit STAMP_PASS);
-      }
-      STAMP(12);
-      pair_signal(sig + 2, a.nsteps - step);  // C: contact adjoints are complete
-      cnt_c = cnt_n; e_c = e_n; P_c = P_n; M_c = M_n;
-      cnt_n = cnt_n2; e_n = e_n2;
-    }
-    STAMP_FLUSH(a);
-    return;
-  }
-
+  // (each role loads the per-body constants itself: what one role needs is dead in the other, and a shared load ahead
+  // of the role branch kept all of them live)
   if (role == 2) {
     // ---- J: joint wave
     STAMP_DECL;
@@ -2535,115 +2415,58 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
         }
       }
     };
-    if constexpr (JT == PD_JT_REVOLUTE) {
-      const bool rev = is_body && c.type == PD_JOINT_REVOLUTE;
-      const unsigned boff_p = (unsigned)((size_t)ec * nb + (has_par ? c.parent : b)) * 4u;
-      // stored pose of this lane's body (q, w) and of its parent (p, q, w), and the controls, one iteration ahead
-      float4 pose[5];
-      float tgt_n = 0.f, act_n = 0.f;
+    // any joint mix: the whole joint adjoint after hand-over A, state from the staged records; controls a step ahead
+    float n_tgt[ND], n_act[ND];
+    auto load_next = [&](int step) {
+      const size_t o = (size_t)__builtin_amdgcn_readfirstlane(step > 0 ? step : 0) * a.bs * m.nqd;
 #pragma unroll
-      for (int k = 0; k < 5; ++k) pose[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      auto load_next = [&](int step) {
-        const int sc = __builtin_amdgcn_readfirstlane(step > 0 ? step : 0);
-        const float *tj = a.ws + (size_t)sc * (PD_TRAJ_G * 4) * N;
-        if (rev) {
-          pose[0] = ldg4(tj, boff * 4u); pose[1] = ldg4(tj + (size_t)4 * N, boff * 4u);
-          pose[2] = ldg4(tj, boff_p * 4u); pose[3] = ldg4(tj + (size_t)4 * N, boff_p * 4u); pose[4] = ldg4(tj + (size_t)8 * N, boff_p * 4u);
-          const size_t o = (size_t)sc * a.bs * m.nqd;
-          tgt_n = ldg(a.refs + o, boff_qd); act_n = ptr_given<SEL>(a.torques) ? ldg(a.torques + o, boff_qd) : 0.f;
-        }
-      };
-      if (a.nsteps > 0) load_next(a.nsteps - 1);
-      for (int step = a.nsteps - 1; step >= 0; --step) {
-        PD_WAIT_VMEM();
-        const qt q_c = Q4(pose[0].x, pose[0].y, pose[0].z, pose[0].w), qp = Q4(pose[2].x, pose[2].y, pose[2].z, pose[2].w);
-        const v3 w_c = V3(pose[1].x, pose[1].y, pose[1].z), pp = V3(pose[4].x, pose[4].y, pose[4].z), w_p = V3(pose[3].x, pose[3].y, pose[3].z);
-        const float tgt = tgt_n, act = act_n;
-        RevCache R = rev_forward<pd_parented(JT)>(m, c, q_c, w_c, pp, qp, w_p, tgt, act, ke[0], kd[0]);
-        STAMP(8);
-        load_next(step - 1);  // nothing loaded here is touched before the next PD_WAIT_VMEM
-        STAMP(7);
-        pair_wait(sig, a.nsteps - step);  // A: wrench adjoints and records of this step are staged
-        STAMP(9);
-        select_step(step);
-        BodyAdj own = adj_zero(), par = adj_zero();
-        float a_tgt[1] = {0.f}, a_act[1] = {0.f}, a_ke[1] = {0.f}, a_kd[1] = {0.f};
-        if (rev) {
-          // one batch of LDS reads: own wrench adjoint, the parent's, and what rev_adjoint needs beyond the prefetched pose
-          const float *r = rec + b * PD_REC, *prec = rec + (has_par ? c.parent : b) * PD_REC;
-          const v3 gc_t = ld3(adjf + b * PD_W6), gc_f = ld3(adjf + b * PD_W6 + 3);
-          v3 gp_t = V3(0, 0, 0), gp_f = gp_t;
-          if (has_par) { gp_t = ld3(adjf + c.parent * PD_W6); gp_f = ld3(adjf + c.parent * PD_W6 + 3); }
-          BodyState s;
-          s.p = ld3(r); s.r = q_c; s.w = w_c; s.v = ld3(r + 10);
-          const v3 rc_c = ld3(r + 13), v_p = ld3(prec + 10), rc_par = ld3(prec + 13);
-          float aR[9];
-#pragma unroll
-          for (int k = 0; k < 9; ++k) aR[k] = 0.f;
-          rev_adjoint_core<pd_parented(JT)>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke[0], kd[0], gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt[0], a_act[0],
-                                            a_ke[0], a_kd[0]);
-          rotm_adj(s.r, aR, own.r);
-        }
-        if (is_body) { adj_store(cslot + b * PD_ADJ, par); adj_store(oslot + b * PD_ADJ, own); }
-        STAMP(10);
-        pair_signal(sig + 1, a.nsteps - step);  // J: (own, parent) contributions are complete
-        store_controls(step, a_tgt, a_act, a_ke, a_kd);  // control gradients, off the critical path
-        STAMP(11);
+      for (int k = 0; k < ND; ++k) {
+        const bool on = CLONE3 || (is_body && k < ndof);  // (CLONE3: unconditional; the root reads the first of its own dofs and never uses them)
+        n_tgt[k] = on ? ldg(a.refs + o + k, boff_qd) : 0.f;
+        n_act[k] = on && ptr_given<SEL>(a.torques) ? ldg(a.torques + o + k, boff_qd) : 0.f;
       }
-    } else {
-      // any joint mix: the whole joint adjoint after hand-over A, state from the staged records; controls a step ahead
-      float n_tgt[ND], n_act[ND];
-      auto load_next = [&](int step) {
-        const size_t o = (size_t)__builtin_amdgcn_readfirstlane(step > 0 ? step : 0) * a.bs * m.nqd;
+    };
+    if (a.nsteps > 0) load_next(a.nsteps - 1);  // (a zero-step rollout has no controls: null pointers)
+    for (int step = a.nsteps - 1; step >= 0; --step) {
+      PD_WAIT_VMEM();
+      float tgt[ND], act[ND];
 #pragma unroll
-        for (int k = 0; k < ND; ++k) {
-          const bool on = CLONE3 || (is_body && k < ndof);  // (CLONE3: unconditional; the root reads the first of its own dofs and never uses them)
-          n_tgt[k] = on ? ldg(a.refs + o + k, boff_qd) : 0.f;
-          n_act[k] = on && ptr_given<SEL>(a.torques) ? ldg(a.torques + o + k, boff_qd) : 0.f;
-        }
-      };
-      if (a.nsteps > 0) load_next(a.nsteps - 1);  // (a zero-step rollout has no controls: null pointers)
-      for (int step = a.nsteps - 1; step >= 0; --step) {
-        PD_WAIT_VMEM();
-        float tgt[ND], act[ND];
-#pragma unroll
-        for (int k = 0; k < ND; ++k) { tgt[k] = n_tgt[k]; act[k] = n_act[k]; }
-        load_next(step - 1);
-        STAMP(7);
-        // S: the records of this step are staged -- the integrate wave does that during the PREVIOUS step, before it waits
-        // for this wave -- so the state-only half of the joint adjoint starts right after the previous step's hand-over J
-        pair_wait(sig + 3, a.nsteps - step);
-        select_step(step);
-        BodyState s;
-        s.p = V3(0, 0, 0); s.r = Q4(0, 0, 0, 1); s.w = V3(0, 0, 0); s.v = V3(0, 0, 0);
-        JointPrep P;
-        const bool jointed = wr && c.type != PD_JOINT_FREE;
-        if (jointed) {
-          const float *r = rec + b * PD_REC;
-          s.p = ld3(r); s.r = ld4(r + 3); s.w = ld3(r + 7); s.v = ld3(r + 10);
-          joint_adj_prep<JT, pd_parented(JT), CLONE3>(m, c, s, ld3(r + 13), rec, tgt, act, ke, kd, P);
-        }
-        STAMP(8);
-        pair_wait(sig, a.nsteps - step);  // A: the wrench adjoints of this step are staged
-        __builtin_amdgcn_s_setprio(PD_PRIO_CRITICAL);  // the integrate wave will wait for these contributions (quad 8192: 1.43 -> 1.40 ms)
-        STAMP(9);
-        BodyAdj own = adj_zero(), par = adj_zero();
-        float a_tgt[ND], a_act[ND], a_ke[ND], a_kd[ND];
-#pragma unroll
-        for (int k = 0; k < ND; ++k) { a_tgt[k] = 0.f; a_act[k] = 0.f; a_ke[k] = 0.f; a_kd[k] = 0.f; }
-        if (jointed) {
-          const v3 gc_t = ld3(adjf + b * PD_W6), gc_f = ld3(adjf + b * PD_W6 + 3);
-          v3 gp_t = V3(0, 0, 0), gp_f = gp_t;
-          if (CLONE3 || has_par) { gp_t = ld3(adjf + c.pidx * PD_W6); gp_f = ld3(adjf + c.pidx * PD_W6 + 3); }  // (plain model: every jointed body hangs on one)
-          joint_adj_apply<JT, pd_parented(JT), CLONE3>(m, c, s, P, tgt, act, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, a_tgt, a_act, a_ke, a_kd);
-        }
-        if (wr) { adj_store(cslot + b * PD_ADJ, par); adj_store(oslot + b * PD_ADJ, own); }
-        STAMP(10);
-        pair_signal(sig + 1, a.nsteps - step);  // J: (own, parent) contributions are complete
-        __builtin_amdgcn_s_setprio(0);
-        store_controls(step, a_tgt, a_act, a_ke, a_kd);
-        STAMP(11);
+      for (int k = 0; k < ND; ++k) { tgt[k] = n_tgt[k]; act[k] = n_act[k]; }
+      load_next(step - 1);
+      STAMP(7);
+      // S: the records of this step are staged -- the integrate wave does that during the PREVIOUS step, before it waits
+      // for this wave -- so the state-only half of the joint adjoint starts right after the previous step's hand-over J
+      pair_wait(sig + 3, a.nsteps - step);
+      select_step(step);
+      BodyState s;
+      s.p = V3(0, 0, 0); s.r = Q4(0, 0, 0, 1); s.w = V3(0, 0, 0); s.v = V3(0, 0, 0);
+      JointPrep P;
+      const bool jointed = wr && c.type != PD_JOINT_FREE;
+      if (jointed) {
+        const float *r = rec + b * PD_REC;
+        s.p = ld3(r); s.r = ld4(r + 3); s.w = ld3(r + 7); s.v = ld3(r + 10);
+        joint_adj_prep<JT, pd_parented(JT), CLONE3>(m, c, s, ld3(r + 13), rec, tgt, act, ke, kd, P);
       }
+      STAMP(8);
+      pair_wait(sig, a.nsteps - step);  // A: the wrench adjoints of this step are staged
+      __builtin_amdgcn_s_setprio(PD_PRIO_CRITICAL);  // the integrate wave will wait for these contributions (quad 8192: 1.43 -> 1.40 ms)
+      STAMP(9);
+      BodyAdj own = adj_zero(), par = adj_zero();
+      float a_tgt[ND], a_act[ND], a_ke[ND], a_kd[ND];
+#pragma unroll
+      for (int k = 0; k < ND; ++k) { a_tgt[k] = 0.f; a_act[k] = 0.f; a_ke[k] = 0.f; a_kd[k] = 0.f; }
+      if (jointed) {
+        const v3 gc_t = ld3(adjf + b * PD_W6), gc_f = ld3(adjf + b * PD_W6 + 3);
+        v3 gp_t = V3(0, 0, 0), gp_f = gp_t;
+        if (CLONE3 || has_par) { gp_t = ld3(adjf + c.pidx * PD_W6); gp_f = ld3(adjf + c.pidx * PD_W6 + 3); }  // (plain model: every jointed body hangs on one)
+        joint_adj_apply<JT, pd_parented(JT), CLONE3>(m, c, s, P, tgt, act, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, a_tgt, a_act, a_ke, a_kd);
+      }
+      if (wr) { adj_store(cslot + b * PD_ADJ, par); adj_store(oslot + b * PD_ADJ, own); }
+      STAMP(10);
+      pair_signal(sig + 1, a.nsteps - step);  // J: (own, parent) contributions are complete
+      __builtin_amdgcn_s_setprio(0);
+      store_controls(step, a_tgt, a_act, a_ke, a_kd);
+      STAMP(11);
     }
     if (is_body) {
       const size_t og = (size_t)ec * m.nqd + c.qdstart;
@@ -2659,22 +2482,14 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
     return;
   }
 
-  // ---- I: integrate wave.  The loop needs the centre of mass and the child list only; everything else of the per-body
-  // constants is loaded after the loop, for the adjoint of eval_fk (nothing of it is live across the steps)
+  // ---- I: integrate wave.  The loop needs the centre of mass, the child list and, for the inline contact replay and its re-cull
+  // fallback, the cull constants; the per-body constants are loaded again after the loop, for the adjoint of eval_fk (nothing else of
+  // them is live across the steps)
   BodyConst c;
-  if (ROLES == 2) {  // the inline contact replay (and its re-cull fallback) needs the cull constants too
-    c = load_body_const(m, b, ec);
+  c = load_body_const(m, b, ec);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) c.small_e[u] = m.small_tiles[u * 64 + (l < 64 ? l : 0)];
-  } else {
-    c.com = ld3(m.com + b * 3); c.children = m.children[b];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      int cid = (int)((c.children >> (8 * k)) & 0xffull);
-      c.child[k] = cid == 0xff ? -1 : cid;
-    }
-  }
-  auto contact_hit = [&](const float *r, float4 P, float4 mat, float *out) {  // ROLES == 2 only
+  for (int u = 0; u < 4; ++u) c.small_e[u] = m.small_tiles[u * 64 + (l < 64 ? l : 0)];
+  auto contact_hit = [&](const float *r, float4 P, float4 mat, float *out) {
     const int pb = (int)(r - rec) / PD_REC;
     BodyAdj o = adj_zero();
     contact_point_adj<true>(r, cull[pb], P, mat, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
@@ -2723,11 +2538,11 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
     rotm(s.r, Rm);  // the body's rotation as a matrix: shared by the staging and the adjoint of integrate_bodies
     const v3 rc = mat_vec(Rm, c.com);
     if (wr) stage_record(rec, cull, b, s, rc, Rm);
-    if (JT != PD_JT_REVOLUTE) pair_signal(sig + 3, a.nsteps - step);  // S
+    pair_signal(sig + 3, a.nsteps - step);  // S
   };
-  // (ROLES == 2) the forward hit list of a step is replayed inline: its length and this lane's entry are fetched a step ahead
+  // the forward hit list of a step is replayed inline: its length and this lane's entry are fetched a step ahead
   // (with the state), so that the replay does not open with a load at its point of use
-  const bool pre_ok = ROLES == 2 && SEGW >= PD_HITLOG - 1;  // one entry per lane covers every list the log can hold
+  const bool pre_ok = SEGW >= PD_HITLOG - 1;  // one entry per lane covers every list the log can hold
   const int lq = l < PD_HITLOG - 1 ? l : PD_HITLOG - 2;
   const unsigned boff_lg = (unsigned)ec * (PD_HITLOG * 4u);
   int cnt_c = 0, e_c = 0, cnt_n = 0, e_n = 0;
@@ -2743,9 +2558,9 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
     if (fr >= 0) {  // seeds of state step+1 (dp_model.py:1264-1271)
       add_frame_seeds(a, fr, N, idx, gn);
     }
-    // (ROLES == 2) the forward hit list of this step is replayed inline further down: fetch its length now, far ahead
+    // the forward hit list of this step is replayed inline further down: fetch its length now, far ahead
     int *lg = a.hitlog + ((size_t)step * a.bs + ec) * PD_HITLOG;
-    const int log_cnt = (ROLES == 2 && env_ok) ? (pre_ok ? cnt_c : lg[0]) : 0;
+    const int log_cnt = env_ok ? (pre_ok ? cnt_c : lg[0]) : 0;
     STAMP(0);
     // ---- adjoint of integrate_bodies; hand-over A as soon as the wrench adjoint exists
     BodyAdj ga = adj_zero();
@@ -2774,7 +2589,7 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
       stg2(o + 4, boff * 6u, make_float2(NZ(adj_f0.y), NZ(adj_f0.z)));
     }
     STAMP(1);
-    if (ROLES == 2) {  // adjoint of eval_body_contacts, while the joint wave works
+    {  // adjoint of eval_body_contacts, while the joint wave works
       WAVE_SYNC();     // records and wrench adjoints were written by this wave's own lanes
       const bool replay = __ballot(log_cnt < 0) == 0ull;
       int log_n_unused;
@@ -2798,7 +2613,6 @@ __global__ __launch_bounds__(PD_BWD3_BOUNDS(ROLES)) void k_rollout_bwd3(PdDevMod
       if (wr && cid != 0xff) adj_add_from(ga, cslot + cid * PD_ADJ);
     }
     STAMP(3);
-    if (ROLES == 3) pair_wait(sig + 2, a.nsteps - step);  // C: contact adjoints are complete
     if (wr) {
       float *d = cacc + b * PD_ADJ;
       const float *const src[1] = {d};
@@ -2948,75 +2762,73 @@ __global__ __launch_bounds__(PD_FK_BLOCK) void k_seeds_fk(PdDevModel m, SeedsFkA
 // workgroup (the latency regime: human at 1024 envs -32 %); with several workgroups per CU the unsplit kernel's 4-wave
 // workgroups pack twice as many body waves per SIMD (quad at 8192 envs: split +22 %), so the launcher picks per launch.
 
-// cfg: the host's choice for this launch (pd_args.h: pd_launch_cfg) -- kernel variant, workgroups, threads, LDS bytes
+// cfg: the host's choice for this launch (pd_host.hip launch_cfg / launch) -- kernel variant, workgroups, threads, LDS bytes
 // GT: the model keeps its contact tables in global memory (m.global_tables) -- the rollout kernels that copy them into LDS have a GT
 // instantiation, the rest (revolute-only adjoint kernels, FK) read no table from LDS and are the same kernels either way
+//
+// WHICH ROLLOUT KERNELS EXIST is written down here and nowhere else: select_fwd / select_bwd name every instantiation, the launchers
+// launch what they return and set_lds_fwd / set_lds_bwd walk their whole run-time domain -- a kernel cannot be launched without having
+// had its dynamic-LDS limit raised.  nullptr: no such instantiation (the launch fails with hipErrorInvalidValue).
+typedef void (*RolloutKernel)(PdDevModel, RolloutArgs);
+static const int kFwdVariants[] = {PD_KV_FWD_SPLIT, PD_KV_FWD_UNSPLIT, PD_KV_FWD_QUAD}, kBwdVariants[] = {PD_KV_BWD_2ROLE, PD_KV_BWD3_2ROLE, PD_KV_BWD_QUAD};
+
 // The forward variants, each with (SAVE) and without (forward-only) the stores of the trajectory the adjoint reads, and each of those
 // with the loads of torques / res_f as ever and behind tests of their pointers (ZC: a launch with a NULL one)
+// k_rollout_fwd<SEGW, JT, SPLIT, LOSS, QUAD, CULLW, RUNSUM, GT, SAVE, ZC>;  roles == 3: with the cull wave;  runsum: four env groups fill
+// the workgroup (per-body sums in registers);  loss: trajectory loss at the frame states (pd_rollout_forward_traj_loss)
 template <int JT, bool GT, bool SAVE, bool ZC>
-static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
-  const dim3 g(cfg.nblocks), t(cfg.threads);
-  const size_t lds = cfg.lds;
-  const bool loss = a.loss_target != nullptr;
-  if (cfg.kernel == PD_KV_FWD_QUAD) {
+static RolloutKernel select_fwd(int kernel, int roles, bool runsum, bool loss) {
+  if (kernel == PD_KV_FWD_QUAD) {
     if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-      if (cfg.roles == 3) {  // with the cull wave
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-      } else {
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-      }
-      return hipGetLastError();
+      if (roles == 3) return loss ? k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE, ZC> : k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE, ZC>;
+      return loss ? k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE, ZC> : k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE, ZC>;
     } else {
-      return hipErrorInvalidValue;
+      return nullptr;
     }
   }
-  if (cfg.roles == 3) {  // wave-specialised forward with the cull wave (revolute-only robots)
+  if (roles == 3) {  // wave-specialised forward with the cull wave (revolute-only robots)
     if constexpr (JT == PD_JT_REVOLUTE) {
-      if (cfg.groups >= PD_BWAVES) {  // full workgroups: per-body sums in registers (RUNSUM)
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE, ZC>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE, ZC>), g, t, lds, st, m, a);
-      } else {
-        if (loss) hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-        else hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-      }
-      return hipGetLastError();
+      if (runsum) return loss ? k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE, ZC> : k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE, ZC>;
+      return loss ? k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE, ZC> : k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE, ZC>;
     } else {
-      return hipErrorInvalidValue;
+      return nullptr;
     }
   }
-  // (unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation)
-  if (loss) {  // trajectory loss at the frame states (pd_rollout_forward_traj_loss)
-    if (cfg.kernel != PD_KV_FWD_SPLIT) return hipErrorInvalidValue;  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
-    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-  } else if (cfg.kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND)
-    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE, ZC>), g, t, lds, st, m, a);
-  else if constexpr (GT)  // (no unsplit instantiation with global tables -- it does not survive the register allocator: a model with its
-    return hipErrorInvalidValue;  // tables in global memory takes the split kernel at every batch size, pd_host.hip launch_cfg)
-  else
-    hipLaunchKernelGGL((k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE, ZC>), g, t, lds, st, m, a);
-  return hipGetLastError();
+  if (loss)  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
+    return kernel == PD_KV_FWD_SPLIT ? k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE, ZC> : nullptr;
+  if (kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND) return k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE, ZC>;
+  // unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation, and none with
+  // global tables -- it does not survive the register allocator: such a model takes the split kernel at every batch size (launch_cfg)
+  if constexpr (JT == PD_JT_COMPOUND && !GT) return k_rollout_fwd<PD_SEGW, JT, false, false, false, false, false, false, SAVE, ZC>;
+  else return nullptr;
 }
 
+// k_rollout_bwd<SEGW, JT, QUAD, SEL> for revolute-only robots, k_rollout_bwd3<SEGW, JT, GT, SEL> for every other joint mix
+template <int JT, bool GT, bool SEL>
+static RolloutKernel select_bwd(int kernel) {
+  if constexpr (pd_split(JT)) {
+    if (kernel == PD_KV_BWD_QUAD) {
+      if constexpr (PD_SEGW == 64) return k_rollout_bwd<PD_SEGW, JT, true, SEL>;
+      else return nullptr;
+    }
+    return k_rollout_bwd<PD_SEGW, JT, false, SEL>;
+  } else {
+    return k_rollout_bwd3<PD_SEGW, JT, GT, SEL>;
+  }
+}
+
+static hipError_t launch_rollout(RolloutKernel k, const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(cfg.nblocks), dim3(cfg.threads), cfg.lds, st, m, a);
+  return hipGetLastError();
+}
+template <int JT, bool GT, bool SAVE, bool ZC>
+static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
+  return launch_rollout(select_fwd<JT, GT, SAVE, ZC>(cfg.kernel, cfg.roles, cfg.groups >= PD_BWAVES, a.loss_target != nullptr), m, a, cfg, st);
+}
 template <int JT, bool GT, bool SEL>
 static hipError_t launch_bwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
-  const dim3 g(cfg.nblocks), t(cfg.threads);
-  const size_t lds = cfg.lds;
-  if constexpr (pd_split(JT)) {
-    if (cfg.kernel == PD_KV_BWD_QUAD) {
-      if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-        hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false, true, SEL>), g, t, lds, st, m, a);
-        return hipGetLastError();
-      } else {
-        return hipErrorInvalidValue;
-      }
-    }
-    hipLaunchKernelGGL((k_rollout_bwd<PD_SEGW, JT, true, false, false, SEL>), g, t, lds, st, m, a);
-  } else {
-    hipLaunchKernelGGL((k_rollout_bwd3<PD_SEGW, JT, 2, GT, SEL>), g, t, lds, st, m, a);
-  }
-  return hipGetLastError();
+  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel), m, a, cfg, st);
 }
 
 template <int JT, bool GT>
@@ -3058,40 +2870,22 @@ static hipError_t launch_jt(int kind, const PdDevModel &m, const void *args, con
   return hipGetLastError();
 }
 
+static hipError_t set_lds(RolloutKernel k, int bytes) {
+  return k ? hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : hipSuccess;
+}
+// every kernel the selector can return (most of them more than once, which is harmless)
 template <int JT, bool GT, bool SAVE, bool ZC>
 static hipError_t set_lds_fwd(int bytes) {
-  hipError_t e;
-  if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  if constexpr (!GT)
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, JT != PD_JT_COMPOUND, false, false, false, false, false, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  }
-  if constexpr (JT == PD_JT_REVOLUTE) {  // ... with the cull wave
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, false, true, true, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, true, true, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if constexpr (PD_SEGW == 64) {
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, false, true, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, true, true, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    }
-  }
-  return hipFuncSetAttribute((const void *)k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE, ZC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  for (const int kernel : kFwdVariants)
+    for (int roles = 1; roles <= 3; ++roles)
+      for (int flags = 0; flags < 4; ++flags)
+        if (const hipError_t e = set_lds(select_fwd<JT, GT, SAVE, ZC>(kernel, roles, (flags & 1) != 0, (flags & 2) != 0), bytes)) return e;
+  return hipSuccess;
 }
-
 template <int JT, bool GT, bool SEL>
 static hipError_t set_lds_bwd(int bytes) {
-  hipError_t e;
-  if constexpr (pd_split(JT)) {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false, false, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    if constexpr (PD_SEGW == 64 && JT == PD_JT_REVOLUTE) {
-      if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd<PD_SEGW, JT, true, false, true, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-    }
-  } else {
-    if ((e = hipFuncSetAttribute((const void *)k_rollout_bwd3<PD_SEGW, JT, 2, GT, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return e;
-  }
+  for (const int kernel : kBwdVariants)
+    if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel), bytes)) return e;
   return hipSuccess;
 }
 

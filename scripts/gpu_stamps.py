@@ -73,14 +73,7 @@ if segw == 64 and name == "laikago" and os.environ.get("PD_FAMILY", "") != "1": 
     report("BWD", "contact wave", rows(b_all, 1), [(7, "prefetch issue"), (9, "wait at hand-over A"),
                                                   (10, "contact adjoint per hit"), (11, "per-body sums"), (12, "tail / generic sweep")])
     print("BWD state wave: not stamped (it runs up to two steps ahead of the other two)")
-elif wb == 3 * G:  # 3-role adjoint
-    report("BWD", "integrate wave", rows(b_all, 0), [(0, "top: seeds + unpack + stage"), (1, "integrate adj (phase 1, signal A, phase 2) + g_res_f"),
-                                                    (2, "wait J"), (3, "own + child gather"), (4, "wait C + cacc")])
-    report("BWD", "contact wave", rows(b_all, 1), [(7, "prefetch issue"), (9, "wait A"), (10, "contact adjoint per hit"), (11, "per-body sums"),
-                                                  (12, "tail / generic sweep")])
-    report("BWD", "joint wave", rows(b_all, 2), [(8, "rev_forward (state-only half)"), (7, "prefetch issue"), (9, "wait A"),
-                                                (10, "LDS reads + rev_adjoint + slots"), (11, "signal J + control-gradient stores")])
-elif wb == 2 * G and name != "laikago":  # 2-role k_rollout_bwd3: integrate (+ contacts) wave, joint wave
+elif wb == 2 * G and name != "laikago":  # k_rollout_bwd3 (every joint mix but revolute-only): integrate (+ contacts) wave, joint wave
     report("BWD", "integrate wave", rows(b_all, 0), [(0, "top: seeds + unpack + stage + signal S"), (1, "integrate adj (phase 1, signal A, phase 2) + g_res_f"),
                                                     (10, "inline contacts: replay setup"), (11, "inline contacts: hit pass"), (5, "inline contacts: rest"),
                                                     (2, "wait J"), (3, "own + child gather"), (4, "cacc")])
