@@ -31,7 +31,6 @@ struct pd_model {
   int family = 0;  // pd_model_set_kernel_family: 0 automatic (by batch size), 1 lane per body always, 2 quad-lane wherever eligible
   void *blob = nullptr;
   PdDevModel dev{};
-  size_t lds_rollout = 0, lds_rollout_bwd = 0, lds_fk = 0;  // at PD_BWAVES env groups per workgroup (the maximum)
   size_t lds_max = 0;  // what the kernels' dynamic-LDS attribute is at least set to
   size_t lds_tables = 0;                                      // contact tables, for the kernels that copy them into LDS
   // per-env joint_X_p bound by the caller (pd_model_bind_joint_X_p); null = the template's
@@ -104,12 +103,40 @@ static void free_quad(pd_model *m) {
   if (m->quad) { if (m->quad->blob) (void)hipFree(m->quad->blob); delete m->quad; m->quad = nullptr; }
 }
 
-template <typename T>
-static size_t put(std::vector<unsigned char> &buf, const std::vector<T> &v) {
-  size_t off = (buf.size() + 255) & ~(size_t)255;
-  buf.resize(off + std::max<size_t>(v.size() * sizeof(T), 16));
-  if (!v.empty()) memcpy(buf.data() + off, v.data(), v.size() * sizeof(T));
-  return off;
+// The model's arrays as one device allocation: each at a 256-byte boundary, in the order it was added, with the PdDevModel pointer that
+// is to address it (point(), once the blob is on the device).
+struct Blob {
+  std::vector<unsigned char> buf;
+  std::vector<std::pair<size_t, size_t>> fix;  // (offset of the array in buf, offset of its pointer in PdDevModel)
+  template <typename T> void add(const T *PdDevModel::*field, const std::vector<T> &v) {
+    static const PdDevModel z{};
+    const size_t off = (buf.size() + 255) & ~(size_t)255;
+    buf.resize(off + std::max<size_t>(v.size() * sizeof(T), 16));
+    if (!v.empty()) memcpy(buf.data() + off, v.data(), v.size() * sizeof(T));
+    fix.push_back({off, (size_t)((const char *)&(z.*field) - (const char *)&z)});
+  }
+  void point(PdDevModel &d, const unsigned char *base) const {
+    for (const auto &f : fix) { const unsigned char *p = base + f.first; memcpy((char *)&d + f.second, &p, sizeof p); }
+  }
+};
+
+// "numeric policy x segment width -> launcher", [policy][width_index(segw)]  (FK evaluates no joint force: the PD_NUM_STABLE row has the one copy)
+static int width_index(int segw) { return segw == 16 ? 0 : (segw == 32 ? 1 : 2); }
+static decltype(&pd_launch_seg16) const g_launch[2][3] = {{pd_launch_seg16, pd_launch_seg32, pd_launch_seg64},
+                                                          {pd_launch_seg16_literal, pd_launch_seg32_literal, pd_launch_seg64_literal}};
+static decltype(&pd_set_lds_seg16) const g_set_lds[2][3] = {{pd_set_lds_seg16, pd_set_lds_seg32, pd_set_lds_seg64},
+                                                            {pd_set_lds_seg16_literal, pd_set_lds_seg32_literal, pd_set_lds_seg64_literal}};
+
+// LDS bytes per workgroup of kernel variant `kv` (PD_KV_*) with `envs` envs in it; tab: the bytes of the contact tables, for the kernels that
+// copy them into LDS (0: the model keeps them in global memory).  The launch plan and build_device's refusal bounds both come from here.
+static size_t variant_lds(const PdDevModel &d, int kv, size_t envs, size_t tab) {
+  switch (kv) {
+    case PD_KV_FWD_SPLIT: case PD_KV_FWD_UNSPLIT: case PD_KV_FWD_QUAD: return tab + envs * d.env_lds_floats * 4;
+    case PD_KV_BWD_2ROLE: return envs * (d.env_lds_floats + 2 * d.env_lds_jc) * 4;                    // + joint hand-over records, no tables
+    case PD_KV_BWD_QUAD: return envs * (d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4;  // + the state wave's generations
+    case PD_KV_BWD3_2ROLE: return tab + envs * d.env_lds_bwd3 * 4;
+    default: return envs * d.nb * (PD_REC + PD_ADJ) * 4;  // PD_KV_FK: records and their adjoints
+  }
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the kernel ON A DEVICE, not of a model: keep the running
@@ -118,37 +145,38 @@ static size_t put(std::vector<unsigned char> &buf, const std::vector<T> &v) {
 #define PD_MAX_DEVICES 64
 static int g_lds_attr[PD_MAX_DEVICES][3][3];
 static int jt_slot(int jt) { return jt == PD_JT_REVOLUTE ? 0 : (jt == PD_JT_COMPOUND ? 1 : 2); }
+static int raise_lds_attr(int segw, int jt, int lds_max) {
+  int dev_id = 0;
+  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0) dev_id = 0;
+  int uncached = 0;  // (a device index beyond the table is simply never cached: the attribute is set on every build)
+  int &attr = dev_id < PD_MAX_DEVICES ? g_lds_attr[dev_id][width_index(segw)][jt_slot(jt)] : uncached;
+  if (lds_max <= attr) return 0;
+  for (int policy = 0; policy < 2; ++policy) {  // ... and on the PD_NUM_LITERAL kernels, whichever policy the model runs under now
+    hipError_t e = g_set_lds[policy][width_index(segw)](jt, lds_max);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(LDS)");
+  }
+  attr = lds_max;
+  return 0;
+}
 
-// Builds the device copy for segment width `segw` into temporaries and commits blob / dev / lds_* / segw / jt only when
-// every check has passed: a failed call leaves the model exactly as it was.
-// global_tables: the contact tables stay in global memory and only the per-env part of a workgroup's LDS has to fit -- for the
-// models whose tables fit at NO width (pd_model_create); every other model keeps them in LDS.  A -DPD_GLOBAL_TABLES build (checking
-// build: only the tables' address space differs, the bits must not) puts every model there.
-static int build_device(pd_model *m, int segw, bool global_tables) {
-#ifdef PD_GLOBAL_TABLES
-  global_tables = true;
-#endif
+// ---- build_device, piece 1: chain topology (depth, packed children, joint mix)
+struct Chain { std::vector<int> depth; std::vector<unsigned long long> children; int max_depth = 0, max_children = 0, jt = 0; };
+static int chain_topology(const pd_model *m, Chain &c) {
   const int nb = m->nb;
-  if (segw == 0) segw = nb <= 16 ? 16 : (nb <= 32 ? 32 : 64);
-  if (segw != 16 && segw != 32 && segw != 64) return fail("segment width must be 16, 32 or 64");
-  if (nb > segw) return fail("segment width smaller than the number of bodies");
-  // ---- chain topology
-  std::vector<int> depth(nb, 0);
-  std::vector<unsigned long long> children(nb, ~0ull);
-  std::vector<int> nchild(nb, 0);
-  int max_depth = 0, max_children = 0, jt = 0;
+  c.depth.assign(nb, 0); c.children.assign(nb, ~0ull);
+  std::vector<int> nchild(nb, 0); int jt = 0;
   for (int i = 0; i < nb; ++i) {
     int p = m->jparent[i];
     if (p >= i) return fail("parents must precede children");
     if (p >= 0) {
-      depth[i] = depth[p] + 1;
+      c.depth[i] = c.depth[p] + 1;
       if (nchild[p] >= 8) return fail("more than 8 children per body is not supported");
-      children[p] &= ~(0xffull << (8 * nchild[p]));
-      children[p] |= (unsigned long long)i << (8 * nchild[p]);
+      c.children[p] &= ~(0xffull << (8 * nchild[p]));
+      c.children[p] |= (unsigned long long)i << (8 * nchild[p]);
       nchild[p]++;
-      max_children = std::max(max_children, nchild[p]);
+      c.max_children = std::max(c.max_children, nchild[p]);
     }
-    max_depth = std::max(max_depth, depth[i]);
+    c.max_depth = std::max(c.max_depth, c.depth[i]);
     switch (m->jtype[i]) {
       case PD_JOINT_REVOLUTE: jt |= PD_JT_REVOLUTE; break;
       case PD_JOINT_COMPOUND: jt |= PD_JT_COMPOUND; break;
@@ -167,19 +195,28 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
     turned_child_frame |= !(qc[0] == 0.f && qc[1] == 0.f && qc[2] == 0.f && qc[3] == 1.f);
   }
   if ((jt != PD_JT_REVOLUTE && jt != PD_JT_COMPOUND) || world_joint || turned_child_frame) jt = PD_JT_REVOLUTE | PD_JT_COMPOUND | PD_JT_FIXED;
-  // ---- contact table: grouped by body, kd-ordered inside a body, cut into tiles of <= segw points
-  std::vector<float4> pts, tile_lo, tile_hi, mats;
+  c.jt = jt;
+  return 0;
+}
+
+// ---- piece 2: contact tables -- grouped by body, kd-ordered inside a body, cut into tiles of <= segw points
+struct ContactTables {
+  std::vector<float4> pts, tile_lo, tile_hi, mats, body_sphere;
   std::vector<unsigned char> pt_mat;
-  std::vector<int> tile_pack;
-  std::vector<int2> body_tiles(nb, make_int2(0, 0));
-  std::vector<float4> body_sphere(nb, make_float4(0, 0, 0, -1.0f));
-  std::vector<int> order;
+  std::vector<int> tile_pack, small_tiles, order; std::vector<int2> body_tiles;
+  unsigned long long big_bodies = 0ull;
+  int n_small = 0, nc = 0, ntiles = 0;  // (nc, ntiles: before the padding entry of an empty table)
+};
+static int contact_tables(const pd_model *m, int segw, ContactTables &t) {
+  const int nb = m->nb;
+  t.body_tiles.assign(nb, make_int2(0, 0));
+  t.body_sphere.assign(nb, make_float4(0, 0, 0, -1.0f));
   for (int b = 0; b < nb; ++b) {
     std::vector<int> ids;
     for (int k = 0; k < m->nc; ++k) if (m->cbody[k] == b) ids.push_back(k);
-    body_tiles[b] = make_int2((int)tile_pack.size(), 0);
+    t.body_tiles[b] = make_int2((int)t.tile_pack.size(), 0);
     if (ids.empty()) continue;
-    body_sphere[b] = bound_sphere(ids, m->cpoint.data(), m->cdist.data());
+    t.body_sphere[b] = bound_sphere(ids, m->cpoint.data(), m->cdist.data());
     // the ORDER of a body's points is that of the 16-lane mapping whatever the segment width (its tiles are then cut segw points at a
     // time): hit-log entries are indices into this table, and a forward pass in one lane mapping may be followed by an adjoint in
     // another (the quad-lane forward kernel runs on the 64-lane tables, the lane-per-body adjoint on the 16-lane ones)
@@ -188,82 +225,53 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
       std::vector<int> tid(ids.begin() + t0, ids.begin() + std::min(ids.size(), t0 + segw));
       float4 blo, bhi;
       bound_box(tid, m->cpoint.data(), m->cdist.data(), blo, bhi);
-      tile_lo.push_back(blo); tile_hi.push_back(bhi);
-      tile_pack.push_back((int)pts.size() | ((int)tid.size() << 16) | (b << 24));
-      body_tiles[b].y++;
+      t.tile_lo.push_back(blo); t.tile_hi.push_back(bhi);
+      t.tile_pack.push_back((int)t.pts.size() | ((int)tid.size() << 16) | (b << 24));
+      t.body_tiles[b].y++;
       for (int k : tid) {
-        pts.push_back(make_float4(m->cpoint[k * 3], m->cpoint[k * 3 + 1], m->cpoint[k * 3 + 2], m->cdist[k]));
+        t.pts.push_back(make_float4(m->cpoint[k * 3], m->cpoint[k * 3 + 1], m->cpoint[k * 3 + 2], m->cdist[k]));
         int mi = m->cmat[k];
         if (mi < 0 || mi >= m->nmat) return fail("contact_material out of range");
-        pt_mat.push_back((unsigned char)mi);
-        order.push_back(k);
+        t.pt_mat.push_back((unsigned char)mi);
+        t.order.push_back(k);
       }
     }
   }
-  const int nc = (int)pts.size(), ntiles = (int)tile_pack.size();
+  t.nc = (int)t.pts.size(); t.ntiles = (int)t.tile_pack.size();
   // small bodies (<= 8 tiles) contribute their tiles to a static flat list of at most 4*segw entries, laid out as
   // 4 chunks of 64 slots so that lane l of a segment reads entry u*64 + l; the rest are "big" (cooperative L2)
-  std::vector<int> small_tiles(4 * 64, -1);
-  unsigned long long big_bodies = 0ull;
-  int n_small = 0;
+  t.small_tiles.assign(4 * 64, -1);
   for (int b = 0; b < nb; ++b) {
-    int nt = body_tiles[b].y;
+    int nt = t.body_tiles[b].y;
     if (nt == 0) continue;
-    if (nt <= 8 && n_small + nt <= 4 * segw) {
-      for (int t = 0; t < nt; ++t, ++n_small) small_tiles[(n_small / segw) * 64 + n_small % segw] = (body_tiles[b].x + t) | (b << 16);
+    if (nt <= 8 && t.n_small + nt <= 4 * segw) {
+      for (int i = 0; i < nt; ++i, ++t.n_small) t.small_tiles[(t.n_small / segw) * 64 + t.n_small % segw] = (t.body_tiles[b].x + i) | (b << 16);
     } else {
-      big_bodies |= 1ull << b;
+      t.big_bodies |= 1ull << b;
     }
   }
-  if (nc > 65535) return fail("more than 65535 contact candidates per articulation is not supported");
+  if (t.nc > 65535) return fail("more than 65535 contact candidates per articulation is not supported");
   if (m->nmat > 255) return fail("more than 255 contact materials is not supported");
   for (int i = 0; i < m->nmat; ++i)
-    mats.push_back(make_float4(m->materials[i * 4], m->materials[i * 4 + 1], m->materials[i * 4 + 2], m->materials[i * 4 + 3]));
-  if (mats.empty()) mats.push_back(make_float4(0, 0, 0, 0));
-  if (pts.empty()) pts.push_back(make_float4(0, 0, 0, 0));
-  pt_mat.resize(((std::max(nc, 1) + 15) / 16) * 16, 0);
-  if (tile_pack.empty()) { tile_pack.push_back(0); tile_lo.push_back(make_float4(0, 0, 0, 0)); tile_hi.push_back(make_float4(0, 0, 0, 0)); }
+    t.mats.push_back(make_float4(m->materials[i * 4], m->materials[i * 4 + 1], m->materials[i * 4 + 2], m->materials[i * 4 + 3]));
+  if (t.mats.empty()) t.mats.push_back(make_float4(0, 0, 0, 0));
+  if (t.pts.empty()) t.pts.push_back(make_float4(0, 0, 0, 0));
+  t.pt_mat.resize(((std::max(t.nc, 1) + 15) / 16) * 16, 0);
+  if (t.tile_pack.empty()) { t.tile_pack.push_back(0); t.tile_lo.push_back(make_float4(0, 0, 0, 0)); t.tile_hi.push_back(make_float4(0, 0, 0, 0)); }
+  return 0;
+}
 
-  // ---- upload
-  std::vector<unsigned char> buf;
-  size_t o_jtype = put(buf, m->jtype), o_jparent = put(buf, m->jparent), o_qstart = put(buf, m->qstart), o_qdstart = put(buf, m->qdstart);
-  size_t o_depth = put(buf, depth), o_children = put(buf, children);
-  size_t o_Xp = put(buf, m->X_p), o_Xc = put(buf, m->X_c), o_axis = put(buf, m->axis), o_com = put(buf, m->com);
-  size_t o_lo = put(buf, m->lim_lo), o_hi = put(buf, m->lim_hi), o_lke = put(buf, m->lim_ke), o_lkd = put(buf, m->lim_kd);
-  size_t o_pts = put(buf, pts), o_ptm = put(buf, pt_mat), o_mats = put(buf, mats);
-  size_t o_bs = put(buf, body_sphere), o_ts = put(buf, tile_lo), o_th = put(buf, tile_hi), o_ti = put(buf, tile_pack), o_bt = put(buf, body_tiles), o_st = put(buf, small_tiles);
-  // ---- sizes first (nothing is touched if the model does not fit)
-  PdDevModel d{};
-  d.nb = nb; d.nq = m->nq; d.nqd = m->nqd; d.nc = nc; d.ntiles = ntiles;
-  d.max_children = max_children; d.max_depth = max_depth;
-  d.nmat = m->nmat;
-  d.big_bodies = big_bodies; d.n_small = n_small;
-  d.list_cap = std::max(ntiles, 2 * nb);
-  d.has_limits = 0;
-  for (int i = 0; i < m->nqd; ++i) if (m->lim_ke[i] != 0.f || m->lim_kd[i] != 0.f) d.has_limits = 1;
-  d.gx = m->gravity[0]; d.gy = m->gravity[1]; d.gz = m->gravity[2];
-  d.attach_ke = m->attach_ke; d.attach_kd = m->attach_kd;
-  // the speculative cull's margin (pd_kernels.hip sink_margin): tight where candidates are many (mesh robots), generous where they are few
-  d.spec_safety = nc > 512 ? 1.25f : 3.0f; d.spec_slack = nc > 512 ? 1.0e-4f : 1.0e-3f;
-  d.X_p_env = m->xp_env; d.xp_envs = m->xp_envs;
-  d.global_tables = global_tables ? 1 : 0;
+// ---- piece 3: the per-env LDS sizes (into d), the bytes of the contact tables, and the refusals: what a workgroup of PD_BWAVES env
+// groups -- the most a launch uses -- needs against the 160 KiB of a CU.  lds_max: what the kernels' dynamic-LDS attribute must allow.
+static int lds_sizing(PdDevModel &d, int segw, int jt, size_t &lds_tables, int &lds_max) {
+  const int nb = d.nb, nc = d.nc, ntiles = d.ntiles;
   // cull vectors (float4 per body, 16-B aligned) + records + wrench slots + adjoint slots + tile list + hit list (8*segw) + per-hit result slots (13*segw)
   d.env_lds_floats = ((nb * (4 + PD_REC + PD_W6 + 2 * PD_ADJ) + PD_ADJ + std::max(ntiles, 2 * nb) + 8 * segw + PD_ADJ * segw + 3) / 4) * 4 + 4;  // + PD_ADJ: the zero record
   // lanes (env e, body b) of one wave address base_e + f(b): an env stride of 16 mod 32 floats lets the envs of a wave
   // alternate between the two halves of the 32 LDS banks (2-way, the minimum for 64 lanes) instead of piling onto one
   d.env_lds_floats += (16 - d.env_lds_floats % 32 + 32) % 32;
-  const int envs_per_block = PD_BWAVES * (64 / segw);
-  const size_t lds_tables = (size_t)std::max(nc, 1) * 16 + (size_t)std::max(ntiles, 1) * 32 + (size_t)std::max(m->nmat, 1) * 16 +
-                            (size_t)((std::max(ntiles, 1) + 3) & ~3) * 4 + (size_t)((nb + 1) & ~1) * 8 + (size_t)((std::max(nc, 1) + 15) & ~15);
-  // (the kernels that copy the tables into LDS take them from global memory instead when global_tables is set: they need no LDS then.
-  // The cull wave's candidate and tile lists are part of env_lds_floats, so pd_fwd_cull_cap gives the same answer either way)
-  const size_t lds_tab = global_tables ? 0 : lds_tables;
-  const size_t lds_rollout = lds_tab + (size_t)envs_per_block * d.env_lds_floats * 4;
-  {
-    int dev_id = 0, cus = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess) cus = 0;
-    d.cu_count = cus;
-  }
+  lds_tables = (size_t)std::max(nc, 1) * 16 + (size_t)std::max(ntiles, 1) * 32 + (size_t)std::max(d.nmat, 1) * 16 +
+               (size_t)((std::max(ntiles, 1) + 3) & ~3) * 4 + (size_t)((nb + 1) & ~1) * 8 + (size_t)((std::max(nc, 1) + 15) & ~15);
   // the role-split adjoint (k_rollout_bwd3) keeps the contact tables in global memory; per env: two generations of cull vectors and records,
   // wrench adjoints, (parent, own) joint slots + the zero record, contact sums, inertia-gradient accumulators, tile list, hit list, per-hit slots, signals
   d.env_lds_jc = ((nb * PD_JC + 31) / 32) * 32;
@@ -272,56 +280,83 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
   d.env_lds_rec2 = (segw == 64 && jt == PD_JT_REVOLUTE && nb <= 16) ? PD_QGEN * (((nb * (4 + PD_REC) + 31) / 32) * 32 + PD_QPRE * 64 + d.env_lds_jc) : 0;
   d.env_lds_bwd3 = ((nb * (2 * (4 + PD_REC) + PD_W6 + 3 * PD_ADJ + PD_GACC) + PD_GACC + PD_ADJ + std::max(ntiles, 2 * nb) + 8 * segw + PD_ADJ * segw + 3) / 4) * 4 + 4;
   d.env_lds_bwd3 += (16 - d.env_lds_bwd3 % 32 + 32) % 32;  // env stride 16 mod 32, as above
+  // (the kernels that copy the tables into LDS take them from global memory instead when global_tables is set: they need no LDS then.
+  // The cull wave's candidate and tile lists are part of env_lds_floats, so pd_fwd_cull_cap gives the same answer either way)
+  const size_t tab = d.global_tables ? 0 : lds_tables, envs = (size_t)PD_BWAVES * (64 / segw);
+  const size_t lds_rollout = variant_lds(d, PD_KV_FWD_SPLIT, envs, tab);
   // revolute-only: 2-role kernel (+ joint hand-over records), no tables; other joint mixes: the 2-role k_rollout_bwd3 with the
   // contact tables in LDS  (the bound keeps the terms of the variants that are gone: the sizes a model is refused at do not move)
-  const size_t lds_rollout_bwd = jt == PD_JT_REVOLUTE
-                                     ? (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4
-                                     : lds_tab + (size_t)envs_per_block * std::max(d.env_lds_bwd3, d.env_lds_floats) * 4;
-  // (the 160 KiB checks below are for PD_BWAVES env groups per workgroup, the most a launch uses)
-  const size_t lds_fk = (size_t)envs_per_block * nb * (PD_REC + PD_ADJ) * 4;
-  if (global_tables) {  // (the tables are out of LDS already: what is left is the envs' own scratch)
+  // RETIRED, revolute-only: k_rollout_bwd3 without tables (env_lds_bwd3) and the lane-per-body state-wave adjoint (floats + 2 jc + rec2).
+  // They are spelled out here and NOT taken from variant_lds: no kernel that runs at this width has them, and a change to a living
+  // variant's LDS must not move which models are refused.
+  const size_t retired = envs * (size_t)std::max(d.env_lds_bwd3, d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4;
+  const size_t lds_rollout_bwd = jt == PD_JT_REVOLUTE ? std::max(retired, variant_lds(d, PD_KV_BWD_2ROLE, envs, 0))
+                                                      : std::max(variant_lds(d, PD_KV_BWD3_2ROLE, envs, tab), lds_rollout);
+  if (d.global_tables) {  // (the tables are out of LDS already: what is left is the envs' own scratch)
     if (lds_rollout_bwd > 160 * 1024 || lds_rollout > 160 * 1024)
       return fail("model needs " + std::to_string(std::max(lds_rollout, lds_rollout_bwd)) + " B of LDS per workgroup for its envs' scratch alone, contact tables in global memory (> 160 KiB)");
   }
   if (lds_rollout_bwd > 160 * 1024) return fail("model needs " + std::to_string(lds_rollout_bwd) + " B of LDS per workgroup (> 160 KiB); use a wider segment");
   if (lds_rollout > 160 * 1024) return fail("model needs " + std::to_string(lds_rollout) + " B of LDS per workgroup (> 160 KiB); use a wider segment");
   // (k_reduce_fk runs FK workgroups of PD_REDUCE_BLOCK / 64 body waves: that many times the 4-wave FK workgroup's records)
-  const size_t lds_fk_wide = lds_fk * (PD_REDUCE_BLOCK / 64 / PD_BWAVES);
+  const size_t lds_fk = variant_lds(d, PD_KV_FK, envs, 0), lds_fk_wide = variant_lds(d, PD_KV_FK, envs * (PD_REDUCE_BLOCK / 64 / PD_BWAVES), 0);
   if (lds_fk_wide > 160 * 1024) return fail("model needs " + std::to_string(lds_fk_wide) + " B of LDS per FK workgroup (> 160 KiB); use a wider segment");
-  const int lds_max = (int)std::max(std::max(std::max(lds_rollout, lds_rollout_bwd), lds_fk), lds_fk_wide);
+  lds_max = (int)std::max(std::max(std::max(lds_rollout, lds_rollout_bwd), lds_fk), lds_fk_wide);
+  return 0;
+}
+
+// Builds the device copy for segment width `segw` into temporaries and commits blob / dev / lds_* / segw / jt only when
+// every check has passed: a failed call leaves the model exactly as it was.
+// global_tables: the contact tables stay in global memory and only the per-env part of a workgroup's LDS has to fit -- for the
+// models whose tables fit at NO width (pd_model_create); every other model keeps them in LDS.  A -DPD_GLOBAL_TABLES build (checking
+// build: only the tables' address space differs, the bits must not) puts every model there.
+static int build_device(pd_model *m, int segw, bool global_tables) {
+#ifdef PD_GLOBAL_TABLES
+  global_tables = true;
+#endif
+  const int nb = m->nb;
+  if (segw == 0) segw = nb <= 16 ? 16 : (nb <= 32 ? 32 : 64);
+  if (segw != 16 && segw != 32 && segw != 64) return fail("segment width must be 16, 32 or 64");
+  if (nb > segw) return fail("segment width smaller than the number of bodies");
+  Chain ch; ContactTables t;
+  if (chain_topology(m, ch) || contact_tables(m, segw, t)) return 1;
+  PdDevModel d{};
+  d.nb = nb; d.nq = m->nq; d.nqd = m->nqd; d.nc = t.nc; d.ntiles = t.ntiles;
+  d.max_children = ch.max_children; d.max_depth = ch.max_depth; d.nmat = m->nmat;
+  d.big_bodies = t.big_bodies; d.n_small = t.n_small;
+  d.list_cap = std::max(t.ntiles, 2 * nb);
+  d.has_limits = 0;
+  for (int i = 0; i < m->nqd; ++i) if (m->lim_ke[i] != 0.f || m->lim_kd[i] != 0.f) d.has_limits = 1;
+  d.gx = m->gravity[0]; d.gy = m->gravity[1]; d.gz = m->gravity[2];
+  d.attach_ke = m->attach_ke; d.attach_kd = m->attach_kd;
+  // the speculative cull's margin (pd_kernels.hip sink_margin): tight where candidates are many (mesh robots), generous where they are few
+  d.spec_safety = t.nc > 512 ? 1.25f : 3.0f; d.spec_slack = t.nc > 512 ? 1.0e-4f : 1.0e-3f;
+  d.X_p_env = m->xp_env; d.xp_envs = m->xp_envs;
+  d.global_tables = global_tables ? 1 : 0;
   int dev_id = 0;
-  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0) dev_id = 0;
-  int uncached = 0;  // (a device index beyond the table is simply never cached: the attribute is set on every build)
-  int &attr = dev_id < PD_MAX_DEVICES ? g_lds_attr[dev_id][segw == 16 ? 0 : (segw == 32 ? 1 : 2)][jt_slot(jt)] : uncached;
-  if (lds_max > attr) {
-    hipError_t ea = segw == 16 ? pd_set_lds_seg16(jt, lds_max) : (segw == 32 ? pd_set_lds_seg32(jt, lds_max) : pd_set_lds_seg64(jt, lds_max));
-    if (ea == hipSuccess)  // ... and on the PD_NUM_LITERAL kernels, whichever policy the model runs under now
-      ea = segw == 16 ? pd_set_lds_seg16_literal(jt, lds_max) : (segw == 32 ? pd_set_lds_seg32_literal(jt, lds_max) : pd_set_lds_seg64_literal(jt, lds_max));
-    if (ea != hipSuccess) return hip_fail(ea, "hipFuncSetAttribute(LDS)");
-    attr = lds_max;
-  }
+  if (hipGetDevice(&dev_id) != hipSuccess || hipDeviceGetAttribute(&d.cu_count, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess) d.cu_count = 0;
+  // ---- sizes first (nothing is touched if the model does not fit)
+  size_t lds_tables = 0; int lds_max = 0;
+  if (lds_sizing(d, segw, ch.jt, lds_tables, lds_max) || raise_lds_attr(segw, ch.jt, lds_max)) return 1;
   // ---- upload into a fresh blob, then commit
+  Blob b;
+  b.add(&PdDevModel::jtype, m->jtype); b.add(&PdDevModel::jparent, m->jparent); b.add(&PdDevModel::qstart, m->qstart); b.add(&PdDevModel::qdstart, m->qdstart);
+  b.add(&PdDevModel::depth, ch.depth); b.add(&PdDevModel::children, ch.children);
+  b.add(&PdDevModel::X_p, m->X_p); b.add(&PdDevModel::X_c, m->X_c); b.add(&PdDevModel::axis, m->axis); b.add(&PdDevModel::com, m->com);
+  b.add(&PdDevModel::lim_lo, m->lim_lo); b.add(&PdDevModel::lim_hi, m->lim_hi); b.add(&PdDevModel::lim_ke, m->lim_ke); b.add(&PdDevModel::lim_kd, m->lim_kd);
+  b.add(&PdDevModel::pts, t.pts); b.add(&PdDevModel::pt_mat, t.pt_mat); b.add(&PdDevModel::materials, t.mats);
+  b.add(&PdDevModel::body_sphere, t.body_sphere); b.add(&PdDevModel::tile_lo, t.tile_lo); b.add(&PdDevModel::tile_hi, t.tile_hi);
+  b.add(&PdDevModel::tile_pack, t.tile_pack); b.add(&PdDevModel::body_tiles, t.body_tiles); b.add(&PdDevModel::small_tiles, t.small_tiles);
   void *blob = nullptr;
-  hipError_t e = hipMalloc(&blob, buf.size());
+  hipError_t e = hipMalloc(&blob, b.buf.size());
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(model)");
-  e = hipMemcpy(blob, buf.data(), buf.size(), hipMemcpyHostToDevice);
+  e = hipMemcpy(blob, b.buf.data(), b.buf.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(blob); return hip_fail(e, "hipMemcpy(model)"); }
-  unsigned char *base = (unsigned char *)blob;
-  d.jtype = (const int *)(base + o_jtype); d.jparent = (const int *)(base + o_jparent);
-  d.qstart = (const int *)(base + o_qstart); d.qdstart = (const int *)(base + o_qdstart);
-  d.depth = (const int *)(base + o_depth); d.children = (const unsigned long long *)(base + o_children);
-  d.X_p = (const float *)(base + o_Xp); d.X_c = (const float *)(base + o_Xc);
-  d.axis = (const float *)(base + o_axis); d.com = (const float *)(base + o_com);
-  d.lim_lo = (const float *)(base + o_lo); d.lim_hi = (const float *)(base + o_hi);
-  d.lim_ke = (const float *)(base + o_lke); d.lim_kd = (const float *)(base + o_lkd);
-  d.pts = (const float4 *)(base + o_pts); d.pt_mat = base + o_ptm; d.materials = (const float4 *)(base + o_mats);
-  d.body_sphere = (const float4 *)(base + o_bs); d.tile_lo = (const float4 *)(base + o_ts); d.tile_hi = (const float4 *)(base + o_th);
-  d.tile_pack = (const int *)(base + o_ti); d.body_tiles = (const int2 *)(base + o_bt);
-  d.small_tiles = (const int *)(base + o_st);
+  b.point(d, (const unsigned char *)blob);
   free_device(m);
   m->blob = blob; m->dev = d;
-  m->lds_rollout = lds_rollout; m->lds_rollout_bwd = lds_rollout_bwd; m->lds_fk = lds_fk; m->lds_tables = lds_tables; m->lds_max = (size_t)lds_max;
-  m->segw = segw; m->jt = jt; m->contact_order = order;
+  m->lds_tables = lds_tables; m->lds_max = (size_t)lds_max;
+  m->segw = segw; m->jt = ch.jt; m->contact_order = t.order;
   return 0;
 }
 
@@ -340,82 +375,62 @@ static void build_quad(pd_model *m) {
 
 static int g_groups = 0;   // -DPD_STAMPS diagnostic builds only (pd_debug_set_groups): env groups per workgroup, 0 = automatic
 
-// Launch geometry of one call: kernel variant, env groups per workgroup (small batches spread over all CUs), LDS bytes.
-static PdLaunchCfg launch_cfg(const pd_model *m, int kind, int n_envs, bool loss = false) {
-  const PdDevModel &d = m->dev;
-  const int epw = 64 / m->segw, n_groups = (n_envs + epw - 1) / epw;
-  const size_t tab = d.global_tables ? 0 : m->lds_tables;  // contact tables in LDS, for the kernels that copy them there
-  PdLaunchCfg c{};
-  c.kernel = pd_kernel_variant(kind, m->jt, n_groups, d.cu_count);
-  // the loss-evaluating forward exists wave-specialised only (round 6): its unsplit instantiation does not survive the register allocator in
-  // the branch-free form the other forward kernels of plain models have, and an env must give the same bits whichever kernel runs it
-  if (loss && c.kernel == PD_KV_FWD_UNSPLIT) c.kernel = PD_KV_FWD_SPLIT;
-  // ... and so does every forward of a model with its contact tables in global memory: the unsplit kernel has no such instantiation
-  // (its register allocation fails to compile with the table pointers in registers); both kernels give an env the same bits
-  if (d.global_tables && c.kernel == PD_KV_FWD_UNSPLIT) c.kernel = PD_KV_FWD_SPLIT;
-  c.roles = pd_variant_roles(c.kernel);
-#ifndef PD_NO_CULLW
-  // revolute-only robots: a third wave per env group runs the speculative contact cull (k_rollout_fwd CULLW)
-  if (c.kernel == PD_KV_FWD_SPLIT && m->jt == PD_JT_REVOLUTE && pd_fwd_cull_cap(d.nb, m->segw, d.list_cap, d.env_lds_floats, PD_REC, PD_W6) >= PD_CULLW_MIN_CAP)
-    c.roles = 3;
-#endif
-  c.groups = kind <= PD_K_ROLLOUT_BWD ? (g_groups ? g_groups : pd_groups_per_wg(n_groups, d.cu_count)) : PD_BWAVES;
-  c.nblocks = (n_groups + c.groups - 1) / c.groups;
-  c.threads = c.roles * c.groups * 64;
-  const size_t envs = (size_t)c.groups * epw;
-  switch (c.kernel) {
-    case PD_KV_FWD_SPLIT: case PD_KV_FWD_UNSPLIT: c.lds = tab + envs * d.env_lds_floats * 4; break;
-    case PD_KV_BWD_2ROLE: c.lds = envs * (d.env_lds_floats + 2 * d.env_lds_jc) * 4; break;
-    case PD_KV_BWD3_2ROLE: c.lds = tab + envs * d.env_lds_bwd3 * 4; break;
-    default: c.lds = m->lds_fk; break;
-  }
-  return c;
-}
-
 // Small batches of an eligible robot take the quad-lane forward kernel: one env per wave pair, so up to PD_BWAVES x CUs envs fill the
 // chip with one workgroup per CU (1 024 on MI355X); beyond that the lane-per-body kernels (four envs per wave) have the throughput.
-static bool use_quad(const pd_model *m, int kind, int n_envs, const void *args) {
+static bool use_quad(const pd_model *m, int kind, int n_envs) {
   if (!m->quad || m->family == 1 || (kind != PD_K_ROLLOUT_FWD && kind != PD_K_ROLLOUT_BWD)) return false;
   // forward: while one workgroup per CU holds the batch (4 x CUs envs); adjoint: while every wave has a SIMD to itself (2 x CUs) --
   // measured: 1 024 envs forward 0.153 ms against 0.184, adjoint 0.273 against 0.244 (two quad pairs per SIMD lose)
   return m->family == 2 || n_envs <= (kind == PD_K_ROLLOUT_FWD ? PD_BWAVES : PD_BWAVES / 2) * m->quad->dev.cu_count;
 }
 
-static hipError_t launch(const pd_model *m, int kind, const void *args, int n_envs, hipStream_t st) {
-  if (use_quad(m, kind, n_envs, args)) {
-    const PdDevModel &d = m->quad->dev;
-    PdLaunchCfg c{};
-    c.kernel = kind == PD_K_ROLLOUT_FWD ? PD_KV_FWD_QUAD : PD_KV_BWD_QUAD;
-    c.roles = 3;   // forward: body, contact and cull wave per env; adjoint: body, contact and state wave
+// Everything one launch is decided by: the geometry, the device copy the kernel gets (the model's own, or the 64-lane copy of the quad-lane
+// family) with its joint mix, the launcher's row and column in g_launch, and what pd_last_launch_info reports (workgroups, threads, LDS
+// bytes and envs per workgroup).  plan_launch is pure: no HIP call, no write to the model.
+struct LaunchPlan { PdLaunchCfg cfg; const PdDevModel *dev; int jt, policy, wi, info[4]; };
+// cfg.kernel / roles / groups are set: the rest of the geometry for n_groups env groups of epw envs behind `lead` other workgroups
+static void finish_cfg(PdLaunchCfg &c, const PdDevModel &d, int n_groups, int epw, size_t tab, int lead, size_t lead_lds) {
+  c.nblocks = lead + (n_groups + c.groups - 1) / c.groups;
+  c.threads = c.roles * c.groups * 64;
+  c.lds = std::max(lead_lds, variant_lds(d, c.kernel, (size_t)c.groups * epw, tab));
+}
+static LaunchPlan plan_launch(const pd_model *m, int kind, int n_envs, bool loss) {
+  const bool rollout = kind <= PD_K_ROLLOUT_BWD, fwd = kind == PD_K_ROLLOUT_FWD, quad = use_quad(m, kind, n_envs);
+  const PdDevModel &d = quad ? m->quad->dev : m->dev;
+  const int segw = quad ? 64 : m->segw, jt = quad ? m->quad->jt : m->jt;
+  const int epw = 64 / segw, n_groups = (n_envs + epw - 1) / epw;  // (quad-lane: one env per group)
+  // the forward kernels' cull wave, where its tile list fits the per-env LDS (pd_args.h pd_fwd_cull_cap)
+  bool cullw = pd_fwd_cull_cap(d.nb, segw, d.list_cap, d.env_lds_floats, PD_REC, PD_W6) >= PD_CULLW_MIN_CAP;
 #ifdef PD_NO_CULLW
-    if (kind == PD_K_ROLLOUT_FWD) c.roles = 2;
+  cullw = false;
 #endif
-    if (kind == PD_K_ROLLOUT_FWD && pd_fwd_cull_cap(d.nb, 64, d.list_cap, d.env_lds_floats, PD_REC, PD_W6) < PD_CULLW_MIN_CAP) c.roles = 2;
-    c.groups = g_groups ? g_groups : pd_groups_per_wg(n_envs, d.cu_count);
-    if (kind == PD_K_ROLLOUT_BWD && c.groups > 2) c.groups = 2;   // (three roles: at most 384 threads, two waves per SIMD -- the body wave needs its 256 VGPRs)
-    c.nblocks = (n_envs + c.groups - 1) / c.groups;
-    c.threads = c.roles * c.groups * 64;
-    c.lds = kind == PD_K_ROLLOUT_FWD ? (d.global_tables ? 0 : m->quad->lds_tables) + (size_t)c.groups * d.env_lds_floats * 4   // contact tables in LDS (unless global)
-                                     : (size_t)c.groups * (d.env_lds_floats + 2 * d.env_lds_jc + d.env_lds_rec2) * 4;  // adjoint: + joint hand-over records + second generation of records
-    if (c.nblocks == 0) return hipSuccess;
-    int *ll = const_cast<pd_model *>(m)->last_launch[kind];
-    ll[0] = c.nblocks; ll[1] = c.threads; ll[2] = (int)c.lds; ll[3] = c.groups;
-    return (m->policy == PD_NUM_LITERAL ? pd_launch_seg64_literal : pd_launch_seg64)(kind, m->quad->jt, d, args, c, st);
+  PdLaunchCfg c{};
+  if (quad) {
+    c.kernel = fwd ? PD_KV_FWD_QUAD : PD_KV_BWD_QUAD;
+    c.roles = fwd && !cullw ? 2 : 3;  // forward: body, contact and cull wave per env; adjoint: body, contact and state wave
+  } else {
+    c.kernel = pd_kernel_variant(kind, jt, n_groups, d.cu_count);
+    // the loss-evaluating forward exists wave-specialised only (round 6): its unsplit instantiation does not survive the register allocator in
+    // the branch-free form the other forward kernels of plain models have, and an env must give the same bits whichever kernel runs it
+    if (loss && c.kernel == PD_KV_FWD_UNSPLIT) c.kernel = PD_KV_FWD_SPLIT;
+    // ... and so does every forward of a model with its contact tables in global memory: the unsplit kernel has no such instantiation
+    // (its register allocation fails to compile with the table pointers in registers); both kernels give an env the same bits
+    if (d.global_tables && c.kernel == PD_KV_FWD_UNSPLIT) c.kernel = PD_KV_FWD_SPLIT;
+    // revolute-only robots: a third wave per env group runs the speculative contact cull (k_rollout_fwd CULLW)
+    c.roles = c.kernel == PD_KV_FWD_SPLIT && jt == PD_JT_REVOLUTE && cullw ? 3 : pd_variant_roles(c.kernel);
   }
-  const PdLaunchCfg c = launch_cfg(m, kind, n_envs, kind == PD_K_ROLLOUT_FWD && ((const RolloutArgs *)args)->loss_target != nullptr);
-  if (c.nblocks == 0) return hipSuccess;
-  if (kind < 2) {
-    int *ll = const_cast<pd_model *>(m)->last_launch[kind];
-    ll[0] = c.nblocks; ll[1] = c.threads; ll[2] = (int)c.lds; ll[3] = c.groups * (64 / m->segw);
-  }
-  if (m->policy == PD_NUM_LITERAL && kind <= PD_K_ROLLOUT_BWD) {  // (FK evaluates no joint force: one copy of those kernels)
-    if (m->segw == 16) return pd_launch_seg16_literal(kind, m->jt, m->dev, args, c, st);
-    if (m->segw == 32) return pd_launch_seg32_literal(kind, m->jt, m->dev, args, c, st);
-    return pd_launch_seg64_literal(kind, m->jt, m->dev, args, c, st);
-  }
-  if (m->segw == 16) return pd_launch_seg16(kind, m->jt, m->dev, args, c, st);
-  if (m->segw == 32) return pd_launch_seg32(kind, m->jt, m->dev, args, c, st);
-  return pd_launch_seg64(kind, m->jt, m->dev, args, c, st);
+  // env groups per workgroup: small batches spread over all CUs (pd_groups_per_wg); the FK kinds always run PD_BWAVES
+  c.groups = !rollout ? PD_BWAVES : (g_groups ? g_groups : pd_groups_per_wg(n_groups, d.cu_count));
+  if (c.kernel == PD_KV_BWD_QUAD && c.groups > 2) c.groups = 2;  // (three roles: at most 384 threads, two waves per SIMD -- the body wave needs its 256 VGPRs)
+  finish_cfg(c, d, n_groups, epw, d.global_tables ? 0 : (quad ? m->quad->lds_tables : m->lds_tables), 0, 0);
+  return LaunchPlan{c, &d, jt, rollout && m->policy == PD_NUM_LITERAL ? 1 : 0, width_index(segw), {c.nblocks, c.threads, (int)c.lds, c.groups * epw}};
+}
+
+static hipError_t launch(const pd_model *m, int kind, const void *args, int n_envs, hipStream_t st) {
+  const LaunchPlan p = plan_launch(m, kind, n_envs, kind == PD_K_ROLLOUT_FWD && ((const RolloutArgs *)args)->loss_target != nullptr);
+  if (p.cfg.nblocks == 0) return hipSuccess;
+  if (kind <= PD_K_ROLLOUT_BWD) std::copy(p.info, p.info + 4, const_cast<pd_model *>(m)->last_launch[kind]);
+  return g_launch[p.policy][p.wi](kind, p.jt, *p.dev, args, p.cfg, st);
 }
 
 static void timing_begin(pd_model *m, int kind, hipStream_t st) {
@@ -603,17 +618,13 @@ static FkArgs fk_ride_args(const pd_fk_ride *fk) {
 }
 // lead_blocks workgroups of the carrying pass (needing lead_lds bytes), then the FK workgroups of fk_n articulations
 static hipError_t launch_ride(const pd_model *m, int kind, const void *args, int fk_n, int lead_blocks, size_t lead_lds, hipStream_t st) {
-  const int epw = 64 / m->segw, n_groups = (fk_n + epw - 1) / epw;
+  const int epw = 64 / m->segw;
   PdLaunchCfg c{};
-  c.kernel = PD_KV_FK; c.roles = 1;
+  c.kernel = PD_KV_FK; c.roles = pd_variant_roles(PD_KV_FK);
   c.groups = kind == PD_K_REDUCE_FK ? PD_REDUCE_BLOCK / 64 : PD_BWAVES;
-  c.nblocks = lead_blocks + (n_groups + c.groups - 1) / c.groups;
-  c.threads = c.groups * 64;
-  c.lds = std::max(lead_lds, m->lds_fk * (size_t)(c.groups / PD_BWAVES));
+  finish_cfg(c, m->dev, (fk_n + epw - 1) / epw, epw, 0, lead_blocks, lead_lds);
   if (c.nblocks == 0) return hipSuccess;
-  if (m->segw == 16) return pd_launch_seg16(kind, m->jt, m->dev, args, c, st);
-  if (m->segw == 32) return pd_launch_seg32(kind, m->jt, m->dev, args, c, st);
-  return pd_launch_seg64(kind, m->jt, m->dev, args, c, st);
+  return g_launch[0][width_index(m->segw)](kind, m->jt, m->dev, args, c, st);
 }
 static int reduce_launch(const pd_model *m, int bs, int nframes, const float *table, float *reduced, float *scale, const pd_fk_ride *fk, hipStream_t st) {
   if (!fk || fk->n == 0) return pd_traj_loss_reduce_launch(bs, nframes, table, reduced, scale, st) ? fail("trajectory-loss reduction launch failed") : 0;
@@ -626,75 +637,74 @@ static int reduce_launch(const pd_model *m, int bs, int nframes, const float *ta
   return e == hipSuccess ? 0 : hip_fail(e, "reduce_loss + fk launch");
 }
 
-static int rollout_forward_impl(const pd_model *cm, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
-                       const float *torques, const float *res_f, const float *refs, const float *target_ke,
-                       const float *target_kd, const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes,
-                       const int *frame2step, float *ws, float *wp_pos, float *wp_vel, float *grf, float *jaf, const TrajLossFwd *tl,
-                       const pd_fk_ride *fk, void *stream) {
-  pd_model *m = const_cast<pd_model *>(cm);
+// What every rollout entry checks first, in this order; -> the device frame table
+static int rollout_prologue(pd_model *m, int bs, int nsteps, int nframes, const int *frame2step, const pd_fk_ride *fk, bool backward,
+                            const int **fos, hipStream_t st) {
   if (!m) return fail("null model");
   if (bs < 0 || nsteps < 0) return fail("negative size");
-  if (batch_too_large(m, bs)) return 1;
-  if (check_fk_ride(fk, false)) return 1;
-  const int *fos = nullptr;
-  if (frame_table(m, nsteps, nframes, frame2step, &fos, (hipStream_t)stream)) return 1;
-  if (bs == 0) {  // nothing to roll out; an empty batch still gets a defined reduced loss (0) from the trajectory-loss entry
-    if (tl && tl->reduced) return reduce_launch(m, 0, nframes, tl->table, tl->reduced, tl->scale, fk, (hipStream_t)stream);
-    return 0;
-  }
-  // qd_init == NULL: resumed rollout -- q_init is then the body state [bs*nb][13] that state 0 is taken from (k_rollout_fwd: a.state0)
-  const bool resumed = q_init && !qd_init;
-  if (resumed && tl)
-    return fail("qd_init is NULL: a rollout resumed from a body state is pd_rollout_forward's alone, the trajectory-loss entries start from (q_init, qd_init)");
-  if (!q_init || (!qd_init && !resumed) || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia) return fail("null device pointer");
-  // torques / res_f may each be NULL: "all zeros" -- nothing is read for it, the launch takes the forward kernels' zero-controls twins
-  // (pd_kernels.hip ZC), whose outputs are those of the launch with explicit zero tensors bit for bit; refs stays required
-  if (nsteps > 0 && !refs) return fail("null device pointer: refs_dev (the PD targets are required; only torques_dev and res_f_dev may be NULL, meaning all zeros)");
-  if (nframes > 0 && (!wp_pos || !wp_vel)) return fail("null device pointer");
-  if (m->xp_env && m->xp_envs != bs) return fail("joint_X_p is bound for " + std::to_string(m->xp_envs) + " envs, rollout has " + std::to_string(bs));
-  // ws == NULL with nsteps > 0: forward-only -- the kernels store no trajectory, hit log or loss seeds (k_rollout_fwd SAVE = false), and
-  // no adjoint can follow.  (A rollout of no steps has no trajectory: it keeps the saving kernel, which writes the seeds of frame 0.)
-  const bool save = ws != nullptr || nsteps == 0;
-  if (!save && tl && (tl->seed_pos || tl->seed_gt))
-    return fail("seed_pos / seed_gt given without a workspace: the seeds serve only an adjoint, which needs the saved trajectory (pass a workspace, or NULL seeds for a forward-only rollout)");
+  if (batch_too_large(m, bs) || check_fk_ride(fk, backward)) return 1;
+  return frame_table(m, nsteps, nframes, frame2step, fos, st);
+}
+static int check_xp_batch(const pd_model *m, int bs) {
+  return m->xp_env && m->xp_envs != bs ? fail("joint_X_p is bound for " + std::to_string(m->xp_envs) + " envs, rollout has " + std::to_string(bs)) : 0;
+}
+// The arguments all rollout entries share, as the kernel argument block their impl completes: the entries add their own pointers (outputs,
+// seeds, gradients) as the caller gave them; the impls validate, split a resumed rollout's q_init into state0 and add the workspace tail
+static RolloutArgs rollout_inputs(int bs, int nsteps, float dt, const float *q_init, const float *qd_init, const float *torques, const float *refs,
+                                  const float *target_ke, const float *target_kd, const float *inv_mass, const float *inertia,
+                                  const float *inv_inertia, int nframes) {
   RolloutArgs a{};
   a.bs = bs; a.nsteps = nsteps; a.nframes = nframes; a.dt = dt;
-  a.q_init = resumed ? nullptr : q_init; a.qd_init = qd_init; a.state0 = resumed ? q_init : nullptr;
-  a.torques = torques; a.res_f = res_f; a.refs = refs;
+  a.q_init = q_init; a.qd_init = qd_init; a.torques = torques; a.refs = refs;
   a.target_ke = target_ke; a.target_kd = target_kd; a.inv_mass = inv_mass; a.inertia = inertia; a.inv_inertia = inv_inertia;
-  a.frame_of_step = fos; a.ws = ws; a.wp_pos = wp_pos; a.wp_vel = wp_vel; a.grf = grf; a.jaf = jaf; a.dbg = g_dbg;
-  a.hitlog = ws ? (int *)(ws + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb) : nullptr;
+  return a;
+}
+
+static int rollout_forward_impl(const pd_model *cm, RolloutArgs a, const int *frame2step, const TrajLossFwd *tl, const pd_fk_ride *fk, void *stream) {
+  pd_model *m = const_cast<pd_model *>(cm);
+  hipStream_t st = (hipStream_t)stream;
+  const int bs = a.bs, nsteps = a.nsteps, nframes = a.nframes;
+  if (rollout_prologue(m, bs, nsteps, nframes, frame2step, fk, false, &a.frame_of_step, st)) return 1;
+  if (bs == 0) {  // nothing to roll out; an empty batch still gets a defined reduced loss (0) from the trajectory-loss entry
+    return tl && tl->reduced ? reduce_launch(m, 0, nframes, tl->table, tl->reduced, tl->scale, fk, st) : 0;
+  }
+  // qd_init == NULL: resumed rollout -- q_init is then the body state [bs*nb][13] that state 0 is taken from (k_rollout_fwd: a.state0)
+  const bool resumed = a.q_init && !a.qd_init;
+  if (resumed && tl)
+    return fail("qd_init is NULL: a rollout resumed from a body state is pd_rollout_forward's alone, the trajectory-loss entries start from (q_init, qd_init)");
+  if (!a.q_init || (!a.qd_init && !resumed) || !a.target_ke || !a.target_kd || !a.inv_mass || !a.inertia || !a.inv_inertia) return fail("null device pointer");
+  // torques / res_f may each be NULL: "all zeros" -- nothing is read for it, the launch takes the forward kernels' zero-controls twins
+  // (pd_kernels.hip ZC), whose outputs are those of the launch with explicit zero tensors bit for bit; refs stays required
+  if (nsteps > 0 && !a.refs) return fail("null device pointer: refs_dev (the PD targets are required; only torques_dev and res_f_dev may be NULL, meaning all zeros)");
+  if (nframes > 0 && (!a.wp_pos || !a.wp_vel)) return fail("null device pointer");
+  if (check_xp_batch(m, bs)) return 1;
+  // ws == NULL with nsteps > 0: forward-only -- the kernels store no trajectory, hit log or loss seeds (k_rollout_fwd SAVE = false), and
+  // no adjoint can follow.  (A rollout of no steps has no trajectory: it keeps the saving kernel, which writes the seeds of frame 0.)
+  const bool save = a.ws != nullptr || nsteps == 0;
+  if (!save && tl && (tl->seed_pos || tl->seed_gt))
+    return fail("seed_pos / seed_gt given without a workspace: the seeds serve only an adjoint, which needs the saved trajectory (pass a workspace, or NULL seeds for a forward-only rollout)");
+  if (resumed) { a.state0 = a.q_init; a.q_init = nullptr; }
+  a.dbg = g_dbg;
+  a.hitlog = a.ws ? (int *)(a.ws + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb) : nullptr;
   if (tl) {
     if (nframes > 0 && (!tl->target || (save && !tl->seed_pos) || !tl->table || !tl->reduced || !tl->scale)) return fail("null device pointer (trajectory loss)");
     a.loss_target = nframes > 0 ? tl->target : nullptr; a.loss_outseq = tl->outseq; a.loss_rot_ratio = tl->rot_ratio;
     a.loss_seed_pos = tl->seed_pos; a.loss_seed_gt = tl->seed_gt; a.loss_table = tl->table;
   }
-  hipStream_t st = (hipStream_t)stream;
   timing_begin(m, 0, st);
   hipError_t e = launch(m, PD_K_ROLLOUT_FWD, &a, bs, st);
   timing_end(m, 0, st);
   if (e != hipSuccess) return hip_fail(e, "rollout_forward launch");
-  if (tl) return reduce_launch(m, bs, nframes, tl->table, tl->reduced, tl->scale, fk, st);
-  return 0;
+  return tl ? reduce_launch(m, bs, nframes, tl->table, tl->reduced, tl->scale, fk, st) : 0;
 }
 
 int pd_rollout_forward(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
                        const float *torques, const float *res_f, const float *refs, const float *target_ke,
                        const float *target_kd, const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes,
                        const int *frame2step, float *ws, float *wp_pos, float *wp_vel, float *grf, float *jaf, void *stream) {
-  return rollout_forward_impl(m, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia,
-                              nframes, frame2step, ws, wp_pos, wp_vel, grf, jaf, nullptr, nullptr, stream);
-}
-
-int pd_rollout_forward_traj_loss(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
-                                 const float *torques, const float *res_f, const float *refs, const float *target_ke,
-                                 const float *target_kd, const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes,
-                                 const int *frame2step, float *ws, float *wp_pos, float *wp_vel, float *grf, float *jaf,
-                                 const float *target_pos, const unsigned char *outseq, float rot_ratio, float *seed_pos, float *seed_gt,
-                                 float *loss_table, float *reduced, float *scale, void *stream) {
-  const TrajLossFwd tl{target_pos, outseq, rot_ratio, seed_pos, seed_gt, loss_table, reduced, scale};
-  return rollout_forward_impl(m, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia,
-                              nframes, frame2step, ws, wp_pos, wp_vel, grf, jaf, &tl, nullptr, stream);
+  RolloutArgs a = rollout_inputs(bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes);
+  a.res_f = res_f; a.ws = ws; a.wp_pos = wp_pos; a.wp_vel = wp_vel; a.grf = grf; a.jaf = jaf;
+  return rollout_forward_impl(m, a, frame2step, nullptr, nullptr, stream);
 }
 
 int pd_rollout_forward_traj_loss_fk(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
@@ -703,76 +713,76 @@ int pd_rollout_forward_traj_loss_fk(const pd_model *m, int bs, int nsteps, float
                                     const int *frame2step, float *ws, float *wp_pos, float *wp_vel, float *grf, float *jaf,
                                     const float *target_pos, const unsigned char *outseq, float rot_ratio, float *seed_pos, float *seed_gt,
                                     float *loss_table, float *reduced, float *scale, const pd_fk_ride *fk, void *stream) {
+  RolloutArgs a = rollout_inputs(bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes);
+  a.res_f = res_f; a.ws = ws; a.wp_pos = wp_pos; a.wp_vel = wp_vel; a.grf = grf; a.jaf = jaf;
   const TrajLossFwd tl{target_pos, outseq, rot_ratio, seed_pos, seed_gt, loss_table, reduced, scale};
-  return rollout_forward_impl(m, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia,
-                              nframes, frame2step, ws, wp_pos, wp_vel, grf, jaf, &tl, fk, stream);
+  return rollout_forward_impl(m, a, frame2step, &tl, fk, stream);
 }
 
-static int rollout_backward_impl(const pd_model *cm, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
-                        const float *torques, const float *refs, const float *target_ke, const float *target_kd,
-                        const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes, const int *frame2step,
-                        const float *ws, const float *adj_pos, const float *adj_vel, float *g_q_init, float *g_qd_init,
-                        float *g_torques, float *g_res_f, float *g_refs, float *g_ke, float *g_kd, float *g_inv_mass,
-                        float *g_inertia, float *g_inv_inertia, const TrajLossBwd *tl, const pd_fk_ride *fk, void *stream) {
+int pd_rollout_forward_traj_loss(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
+                                 const float *torques, const float *res_f, const float *refs, const float *target_ke,
+                                 const float *target_kd, const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes,
+                                 const int *frame2step, float *ws, float *wp_pos, float *wp_vel, float *grf, float *jaf,
+                                 const float *target_pos, const unsigned char *outseq, float rot_ratio, float *seed_pos, float *seed_gt,
+                                 float *loss_table, float *reduced, float *scale, void *stream) {
+  return pd_rollout_forward_traj_loss_fk(m, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, inv_mass, inertia,
+                                         inv_inertia, nframes, frame2step, ws, wp_pos, wp_vel, grf, jaf, target_pos, outseq, rot_ratio,
+                                         seed_pos, seed_gt, loss_table, reduced, scale, nullptr, stream);
+}
+
+static void set_grads(RolloutArgs &a, float *g_q_init, float *g_qd_init, float *g_torques, float *g_res_f, float *g_refs, float *g_ke,
+                      float *g_kd, float *g_inv_mass, float *g_inertia, float *g_inv_inertia) {
+  a.g_q_init = g_q_init; a.g_qd_init = g_qd_init; a.g_torques = g_torques; a.g_res_f = g_res_f; a.g_refs = g_refs;
+  a.g_ke = g_ke; a.g_kd = g_kd; a.g_inv_mass = g_inv_mass; a.g_inertia = g_inertia; a.g_inv_inertia = g_inv_inertia;
+}
+static int rollout_backward_impl(const pd_model *cm, RolloutArgs a, const int *frame2step, const TrajLossBwd *tl, const pd_fk_ride *fk, void *stream) {
   pd_model *m = const_cast<pd_model *>(cm);
-  if (!m) return fail("null model");
-  if (bs < 0 || nsteps < 0) return fail("negative size");
-  if (batch_too_large(m, bs)) return 1;
-  if (check_fk_ride(fk, true)) return 1;
-  const int *fos = nullptr;
-  if (frame_table(m, nsteps, nframes, frame2step, &fos, (hipStream_t)stream)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const int bs = a.bs, nsteps = a.nsteps, nframes = a.nframes;
+  if (rollout_prologue(m, bs, nsteps, nframes, frame2step, fk, true, &a.frame_of_step, st)) return 1;
   if (bs == 0) {
     if (fk && fk->n > 0) {  // no rollout, but the FK adjoint that rides along still runs
       SeedsFkArgs sa{};
       sa.fk = fk_ride_args(fk);
-      hipError_t e = launch_ride(m, PD_K_SEEDS_FK, &sa, fk->n, 0, 0, (hipStream_t)stream);
+      hipError_t e = launch_ride(m, PD_K_SEEDS_FK, &sa, fk->n, 0, 0, st);
       if (e != hipSuccess) return hip_fail(e, "fk backward launch");
     }
     return 0;
   }
   // qd_init == NULL: adjoint of a resumed rollout -- q_init is the body state [bs*nb][13], g_q_init receives its gradient (raw: it is
   // the adjoint that flows on into the rollout before), and there is no g_qd_init
-  const bool resumed = q_init && !qd_init;
+  const bool resumed = a.q_init && !a.qd_init;
   if (resumed && (tl || fk))
     return fail("qd_init is NULL: a rollout resumed from a body state is pd_rollout_backward's alone, the trajectory-loss entries start from (q_init, qd_init)");
-  if (resumed && g_qd_init)
+  if (resumed && a.g_qd_init)
     return fail("g_qd_init given with a NULL qd_init: a resumed rollout has one state gradient, g_q_init [bs*nb][13] (pass a NULL g_qd_init)");
-  if (!q_init || (!qd_init && !resumed) || !target_ke || !target_kd || !inv_mass || !inertia || !inv_inertia || !g_q_init ||
-      (!g_qd_init && !resumed) || !g_ke || !g_kd || !g_inv_mass || !g_inertia || !g_inv_inertia)
+  if (!a.q_init || (!a.qd_init && !resumed) || !a.target_ke || !a.target_kd || !a.inv_mass || !a.inertia || !a.inv_inertia || !a.g_q_init ||
+      (!a.g_qd_init && !resumed) || !a.g_ke || !a.g_kd || !a.g_inv_mass || !a.g_inertia || !a.g_inv_inertia)
     return fail("null device pointer");
   // g_torques / g_res_f / g_refs may each be NULL: that per-step gradient is not wanted -- the launch then takes the adjoint kernel's
   // selective instantiation (pd_kernels.hip SEL), which computes and stores nothing for it; the inputs and the workspace stay required
   // torques may be NULL ("all zeros", exactly when the forward's was): the same twin, with the load of torques behind a test as well
-  if (nsteps > 0 && !refs) return fail("null device pointer: refs_dev (the PD targets are required; only torques_dev may be NULL, meaning all zeros)");
-  if (nsteps > 0 && !ws) return fail("null device pointer");
-  if (!tl && nframes > 0 && (!adj_pos || !adj_vel)) return fail("null device pointer");
-  if (tl && ((adj_pos == nullptr) != (adj_vel == nullptr))) return fail("adj_pos and adj_vel come together (both, or neither)");
+  if (nsteps > 0 && !a.refs) return fail("null device pointer: refs_dev (the PD targets are required; only torques_dev may be NULL, meaning all zeros)");
+  if (nsteps > 0 && !a.ws) return fail("null device pointer");
+  if (!tl && nframes > 0 && (!a.adj_pos || !a.adj_vel)) return fail("null device pointer");
+  if (tl && ((a.adj_pos == nullptr) != (a.adj_vel == nullptr))) return fail("adj_pos and adj_vel come together (both, or neither)");
   if (tl && nframes > 0 && (!tl->seed_pos || !tl->scale || !tl->gain || !tl->work)) return fail("null device pointer (trajectory loss)");
-  if (m->xp_env && m->xp_envs != bs) return fail("joint_X_p is bound for " + std::to_string(m->xp_envs) + " envs, rollout has " + std::to_string(bs));
-  RolloutArgs a{};
-  a.bs = bs; a.nsteps = nsteps; a.nframes = nframes; a.dt = dt;
+  if (check_xp_batch(m, bs)) return 1;
+  const bool seeds = tl && nframes > 0;
   if (fk && fk->n > 0) {  // seeds pass (if any) + FK backward workgroups in one launch
     SeedsFkArgs sa{};
     sa.fk = fk_ride_args(fk);
-    const bool seeds = tl && nframes > 0;
-    if (seeds) sa.seeds = TrajSeedsArgs{bs, m->nb, nframes, tl->seed_pos, tl->scale, tl->gain, adj_pos, adj_vel, tl->work, pd_traj_seeds_blocks(bs, m->nb, nframes)};
-    hipError_t e = launch_ride(m, PD_K_SEEDS_FK, &sa, fk->n, sa.seeds.nblocks, 0, (hipStream_t)stream);
+    if (seeds) sa.seeds = TrajSeedsArgs{bs, m->nb, nframes, tl->seed_pos, tl->scale, tl->gain, a.adj_pos, a.adj_vel, tl->work, pd_traj_seeds_blocks(bs, m->nb, nframes)};
+    hipError_t e = launch_ride(m, PD_K_SEEDS_FK, &sa, fk->n, sa.seeds.nblocks, 0, st);
     if (e != hipSuccess) return hip_fail(e, "seeds + fk backward launch");
-    if (seeds) { adj_pos = tl->work; adj_vel = tl->work + (size_t)nframes * bs * m->nb * 7; }
-  } else if (tl && nframes > 0) {
+  } else if (seeds) {
     // the seeds of this sweep, built on the device: work = [F][bs*nb][7] poses then [F][bs*nb][6] twists (pd_trajloss.h traj_seeds_block)
-    if (pd_traj_seeds_launch(bs, m->nb, nframes, tl->seed_pos, tl->scale, tl->gain, adj_pos, adj_vel, tl->work, (hipStream_t)stream)) return fail("seed launch failed");
-    adj_pos = tl->work; adj_vel = tl->work + (size_t)nframes * bs * m->nb * 7;
+    if (pd_traj_seeds_launch(bs, m->nb, nframes, tl->seed_pos, tl->scale, tl->gain, a.adj_pos, a.adj_vel, tl->work, st)) return fail("seed launch failed");
   }
-  a.q_init = resumed ? nullptr : q_init; a.qd_init = qd_init; a.state0 = resumed ? q_init : nullptr;
-  a.torques = torques; a.refs = refs;
-  a.target_ke = target_ke; a.target_kd = target_kd; a.inv_mass = inv_mass; a.inertia = inertia; a.inv_inertia = inv_inertia;
-  a.frame_of_step = fos; a.ws = const_cast<float *>(ws); a.adj_pos = adj_pos; a.adj_vel = adj_vel;
-  a.g_q_init = resumed ? nullptr : g_q_init; a.g_qd_init = g_qd_init; a.g_state0 = resumed ? g_q_init : nullptr;
-  a.g_torques = g_torques; a.g_res_f = g_res_f; a.g_refs = g_refs;
-  a.g_ke = g_ke; a.g_kd = g_kd; a.g_inv_mass = g_inv_mass; a.g_inertia = g_inertia; a.g_inv_inertia = g_inv_inertia; a.dbg = g_dbg;
-  a.hitlog = (int *)(const_cast<float *>(ws) + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb);
-  hipStream_t st = (hipStream_t)stream;
+  if (seeds) { a.adj_pos = tl->work; a.adj_vel = tl->work + (size_t)nframes * bs * m->nb * 7; }
+  if (resumed) { a.state0 = a.q_init; a.q_init = nullptr; a.g_state0 = a.g_q_init; a.g_q_init = nullptr; }
+  a.dbg = g_dbg;
+  a.hitlog = (int *)(a.ws + (size_t)nsteps * PD_TRAJ_FLOATS * (size_t)bs * m->nb);
   timing_begin(m, 1, st);
   hipError_t e = launch(m, PD_K_ROLLOUT_BWD, &a, bs, st);
   timing_end(m, 1, st);
@@ -785,21 +795,10 @@ int pd_rollout_backward(const pd_model *m, int bs, int nsteps, float dt, const f
                         const float *ws, const float *adj_pos, const float *adj_vel, float *g_q_init, float *g_qd_init,
                         float *g_torques, float *g_res_f, float *g_refs, float *g_ke, float *g_kd, float *g_inv_mass,
                         float *g_inertia, float *g_inv_inertia, void *stream) {
-  return rollout_backward_impl(m, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes,
-                               frame2step, ws, adj_pos, adj_vel, g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass,
-                               g_inertia, g_inv_inertia, nullptr, nullptr, stream);
-}
-
-int pd_rollout_backward_traj_loss(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
-                                  const float *torques, const float *refs, const float *target_ke, const float *target_kd,
-                                  const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes, const int *frame2step,
-                                  const float *ws, const float *adj_pos, const float *adj_vel, const float *seed_pos, const float *scale,
-                                  const float *g_loss, float *seed_work, float *g_q_init, float *g_qd_init, float *g_torques, float *g_res_f, float *g_refs,
-                                  float *g_ke, float *g_kd, float *g_inv_mass, float *g_inertia, float *g_inv_inertia, void *stream) {
-  const TrajLossBwd tl{seed_pos, scale, g_loss, seed_work};
-  return rollout_backward_impl(m, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes,
-                               frame2step, ws, adj_pos, adj_vel, g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass,
-                               g_inertia, g_inv_inertia, &tl, nullptr, stream);
+  RolloutArgs a = rollout_inputs(bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes);
+  a.ws = const_cast<float *>(ws); a.adj_pos = adj_pos; a.adj_vel = adj_vel;
+  set_grads(a, g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass, g_inertia, g_inv_inertia);
+  return rollout_backward_impl(m, a, frame2step, nullptr, nullptr, stream);
 }
 
 int pd_rollout_backward_traj_loss_fk(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
@@ -809,10 +808,23 @@ int pd_rollout_backward_traj_loss_fk(const pd_model *m, int bs, int nsteps, floa
                                      const float *g_loss, float *seed_work, float *g_q_init, float *g_qd_init, float *g_torques, float *g_res_f, float *g_refs,
                                      float *g_ke, float *g_kd, float *g_inv_mass, float *g_inertia, float *g_inv_inertia, const pd_fk_ride *fk,
                                      void *stream) {
+  RolloutArgs a = rollout_inputs(bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes);
+  a.ws = const_cast<float *>(ws); a.adj_pos = adj_pos; a.adj_vel = adj_vel;
+  set_grads(a, g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass, g_inertia, g_inv_inertia);
   const TrajLossBwd tl{seed_pos, scale, g_loss, seed_work};
-  return rollout_backward_impl(m, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia, nframes,
-                               frame2step, ws, adj_pos, adj_vel, g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass,
-                               g_inertia, g_inv_inertia, &tl, fk, stream);
+  return rollout_backward_impl(m, a, frame2step, &tl, fk, stream);
+}
+
+int pd_rollout_backward_traj_loss(const pd_model *m, int bs, int nsteps, float dt, const float *q_init, const float *qd_init,
+                                  const float *torques, const float *refs, const float *target_ke, const float *target_kd,
+                                  const float *inv_mass, const float *inertia, const float *inv_inertia, int nframes, const int *frame2step,
+                                  const float *ws, const float *adj_pos, const float *adj_vel, const float *seed_pos, const float *scale,
+                                  const float *g_loss, float *seed_work, float *g_q_init, float *g_qd_init, float *g_torques, float *g_res_f, float *g_refs,
+                                  float *g_ke, float *g_kd, float *g_inv_mass, float *g_inertia, float *g_inv_inertia, void *stream) {
+  return pd_rollout_backward_traj_loss_fk(m, bs, nsteps, dt, q_init, qd_init, torques, refs, target_ke, target_kd, inv_mass, inertia,
+                                          inv_inertia, nframes, frame2step, ws, adj_pos, adj_vel, seed_pos, scale, g_loss, seed_work,
+                                          g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass, g_inertia, g_inv_inertia,
+                                          nullptr, stream);
 }
 
 int pd_fk_forward(const pd_model *m, int n, const float *joint_q, const float *joint_qd, float *body_q, float *body_qd, void *stream) {

@@ -2762,7 +2762,7 @@ __global__ __launch_bounds__(PD_FK_BLOCK) void k_seeds_fk(PdDevModel m, SeedsFkA
 // workgroup (the latency regime: human at 1024 envs -32 %); with several workgroups per CU the unsplit kernel's 4-wave
 // workgroups pack twice as many body waves per SIMD (quad at 8192 envs: split +22 %), so the launcher picks per launch.
 
-// cfg: the host's choice for this launch (pd_host.hip launch_cfg / launch) -- kernel variant, workgroups, threads, LDS bytes
+// cfg: the host's choice for this launch (pd_host.hip plan_launch / launch) -- kernel variant, workgroups, threads, LDS bytes
 // GT: the model keeps its contact tables in global memory (m.global_tables) -- the rollout kernels that copy them into LDS have a GT
 // instantiation, the rest (revolute-only adjoint kernels, FK) read no table from LDS and are the same kernels either way
 //
@@ -2794,11 +2794,11 @@ static RolloutKernel select_fwd(int kernel, int roles, bool runsum, bool loss) {
       return nullptr;
     }
   }
-  if (loss)  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip launch_cfg)
+  if (loss)  // (the host sends every loss-evaluating launch to the split kernel: pd_host.hip plan_launch)
     return kernel == PD_KV_FWD_SPLIT ? k_rollout_fwd<PD_SEGW, JT, true, true, false, false, false, GT, SAVE, ZC> : nullptr;
   if (kernel == PD_KV_FWD_SPLIT || JT != PD_JT_COMPOUND) return k_rollout_fwd<PD_SEGW, JT, true, false, false, false, false, GT, SAVE, ZC>;
   // unsplit: compound-only robots above 4 x CUs env groups -- pd_kernel_variant; no other joint mix has that instantiation, and none with
-  // global tables -- it does not survive the register allocator: such a model takes the split kernel at every batch size (launch_cfg)
+  // global tables -- it does not survive the register allocator: such a model takes the split kernel at every batch size (plan_launch)
   if constexpr (JT == PD_JT_COMPOUND && !GT) return k_rollout_fwd<PD_SEGW, JT, false, false, false, false, false, false, SAVE, ZC>;
   else return nullptr;
 }

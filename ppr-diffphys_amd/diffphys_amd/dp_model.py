@@ -175,6 +175,23 @@ def _view(g, name, like):
     return g[name].view_as(like) if name in g else None
 
 
+def _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf):
+    """The side outputs on ``self`` that phys_model.query() consumes (dp_model.py:855-860).  A frame at state `nsteps` has no force
+    snapshot in the reference (:1225-1228 append for step in steps_idx only): keep its list lengths."""
+    has_f = [f for f, s in enumerate(frame2step) if s < nsteps]
+    self.grfs = [grf[f] for f in has_f]
+    self.jafs = [jaf[f] for f in has_f]
+    self.sim_trajs = HostFrames(wp_pos[:, : dm.nb])
+
+
+def _grad_tuple(g, init, torques, res_f, refs, inertia, inv_inertia, mass_shape, device):
+    """The gradients of the eleven rollout inputs in ForwardWarp's order.  init: those of the first two inputs; a per-step gradient that
+    was not asked for is None; body_mass gets zeros (the module docstring)."""
+    return init + (_view(g, "torques", torques), _view(g, "res_f", res_f), _view(g, "refs", refs), g["target_ke"], g["target_kd"],
+                   torch.zeros(mass_shape, dtype=torch.float32, device=device), g["body_inv_mass"],
+                   g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia))
+
+
 _SUMMED = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")  # gradients that are sums over the steps
 
 
@@ -281,12 +298,7 @@ class ForwardWarp(torch.autograd.Function):
         ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
         ctx.save_for_backward(ws, *inp)
         ctx.mass_shape = body_mass.shape
-        # side outputs consumed by phys_model.query() (dp_model.py:855-860); a frame at state `nsteps` has no force
-        # snapshot in the reference (:1225-1228 append for step in steps_idx only): keep its list lengths
-        has_f = [f for f, s in enumerate(frame2step) if s < nsteps]
-        self.grfs = [grf[f] for f in has_f]
-        self.jafs = [jaf[f] for f in has_f]
-        self.sim_trajs = HostFrames(wp_pos[:, : dm.nb])
+        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
         return wp_pos, wp_vel
 
     @staticmethod
@@ -304,10 +316,7 @@ class ForwardWarp(torch.autograd.Function):
                                         adj_body_qd.to(torch.float32).contiguous(), **want)
         # remove_nan (dp_model.py:1294-1384: NaN -> 0 on every returned gradient, inf kept) is applied by the adjoint kernel where it
         # stores the gradients (pd_rollout_backward): no pass over the tensors here
-        return (g["q_init"], g["qd_init"], _view(g, "torques", torques), _view(g, "res_f", res_f),
-                _view(g, "refs", refs), g["target_ke"], g["target_kd"],
-                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=refs.device), g["body_inv_mass"],
-                g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
+        return _grad_tuple(g, (g["q_init"], g["qd_init"]), torques, res_f, refs, inertia, inv_inertia, ctx.mass_shape, refs.device) + (None,)
 
 
 class ForwardWarpState(torch.autograd.Function):
@@ -336,10 +345,7 @@ class ForwardWarpState(torch.autograd.Function):
         ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
         ctx.save_for_backward(ws, state0, *inp)
         ctx.mass_shape, ctx.q0_shape, ctx.qd0_shape = body_mass.shape, body_q0.shape, body_qd0.shape
-        has_f = [f for f, s in enumerate(frame2step) if s < nsteps]
-        self.grfs = [grf[f] for f in has_f]
-        self.jafs = [jaf[f] for f in has_f]
-        self.sim_trajs = HostFrames(wp_pos[:, : dm.nb])
+        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
         return wp_pos, wp_vel
 
     @staticmethod
@@ -350,10 +356,8 @@ class ForwardWarpState(torch.autograd.Function):
                                     adj_body_qs.to(torch.float32).contiguous(), adj_body_qd.to(torch.float32).contiguous(), state0=state0,
                                     **_want_kw(ctx))
         g0 = _remove_nan(g["state0"])
-        return (g0[:, :7].reshape(ctx.q0_shape), g0[:, 7:].reshape(ctx.qd0_shape), _view(g, "torques", torques), _view(g, "res_f", res_f),
-                _view(g, "refs", refs), g["target_ke"], g["target_kd"],
-                torch.zeros(ctx.mass_shape, dtype=torch.float32, device=refs.device), g["body_inv_mass"],
-                g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), None)
+        init = (g0[:, :7].reshape(ctx.q0_shape), g0[:, 7:].reshape(ctx.qd0_shape))
+        return _grad_tuple(g, init, torques, res_f, refs, inertia, inv_inertia, ctx.mass_shape, refs.device) + (None,)
 
 
 class ForwardWarpTrajLoss(torch.autograd.Function):
@@ -428,10 +432,7 @@ def _traj_loss_forward(ctx, rollout_inputs, target_position, outseq_idx, self, q
     ctx.fk_shapes = None if fk is None else (tuple(tl["fk_body_q"].shape), tuple(tl["fk_body_qd"].shape))
     ctx.save_for_backward(ws, *inp, *(fk or ()))
     ctx.mass_shape, ctx.tgt_shape = body_mass.shape, target_position.shape
-    has_f = [f for f, s in enumerate(frame2step) if s < nsteps]
-    self.grfs = [grf[f] for f in has_f]
-    self.jafs = [jaf[f] for f in has_f]
-    self.sim_trajs = HostFrames(wp_pos[:, : dm.nb])
+    _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
     self.traj_loss_info = tl["reduced"]
     ctx.mark_non_differentiable(wp_pos, wp_vel)
     out = (tl["reduced"][0].clone(), wp_pos, wp_vel)
@@ -460,10 +461,7 @@ def _traj_loss_backward(ctx, g_loss, g_queried):
         # a zero share is an ASSIGNMENT in the reference (loss_seq[i, idx:] = 0, loss_traj[outseq_idx] = 0): nothing flows there, not 0 * inf
         k = (tl["scale"] * (gl / ctx.dm.nb))[:, :, None, None]
         g_tgt = torch.where(k != 0, tl["seed_gt"] * k, torch.zeros_like(tl["seed_gt"])).view(ctx.tgt_shape)
-    out = (g["q_init"], g["qd_init"], _view(g, "torques", torques), _view(g, "res_f", res_f),
-           _view(g, "refs", refs), g["target_ke"], g["target_kd"],
-           torch.zeros(ctx.mass_shape, dtype=torch.float32, device=ws.device), g["body_inv_mass"],
-           g["body_inertia"].view_as(inertia), g["body_inv_inertia"].view_as(inv_inertia), g_tgt, None)
+    out = _grad_tuple(g, (g["q_init"], g["qd_init"]), torques, res_f, refs, inertia, inv_inertia, ctx.mass_shape, ws.device) + (g_tgt, None)
     if g_queried is not None:
         out += (g.get("fk_joint_q"), g.get("fk_joint_qd"))
     ctx.tl = None  # the sweep's buffers go with it (a second backward through the same graph is not supported, as with saved tensors)

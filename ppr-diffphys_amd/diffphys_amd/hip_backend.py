@@ -107,14 +107,27 @@ def lib():
             L.pd_model_contact_order.argtypes = [ctypes.c_void_p, _ip, ctypes.c_int]
         L.pd_model_bind_joint_X_p.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.pd_rollout_forward.argtypes = [vp, ci, ci, cf] + [vp] * 10 + [ci, _ip] + [vp] * 5 + [vp]
-        L.pd_rollout_backward.argtypes = [vp, ci, ci, cf] + [vp] * 9 + [ci, _ip] + [vp] * 3 + [vp] * 10 + [vp]
+        # the parameter runs of the six rollout entries, named as in the header (include/ppr_diffphys.h); DeviceModel builds the
+        # arguments from the helpers of the same names
+        head = [vp, ci, ci, cf, vp, vp]       # model, bs, nsteps, dt, q_init, qd_init                           (_head)
+        params = [vp] * 7                     # torques, refs, target_ke, target_kd, inv_mass, inertia, inv_inertia  (_params)
+        fwd_params = [vp] * 8                 # the same with res_f after torques                                   (_params(res_f=))
+        frames = [ci, _ip]                    # nframes, frame2step                                              (_f2s)
+        fwd_out = [vp] * 5                    # workspace, wp_pos, wp_vel, grf, jaf                              (_fwd_out)
+        fwd_loss = [vp, vp, cf] + [vp] * 5    # target_pos, outseq, rot_ratio, seed_pos, seed_gt, loss_table, reduced, scale
+        bwd_in = [vp] * 3                     # workspace, adj_pos, adj_vel                                      (_bwd_in)
+        bwd_loss = [vp] * 4                   # seed_pos, scale, g_loss, seed_work
+        # g_q_init, g_qd_init, g_torques, g_res_f, g_refs, g_ke, g_kd, g_inv_mass, g_inertia, g_inv_inertia     (_grad_tail)
+        grads = [vp] * 10
+        ride, stream = [ctypes.POINTER(_FkRide)], [vp]
+        L.pd_rollout_forward.argtypes = head + fwd_params + frames + fwd_out + stream
+        L.pd_rollout_backward.argtypes = head + params + frames + bwd_in + grads + stream
         if hasattr(L, "pd_rollout_forward_traj_loss"):
-            L.pd_rollout_forward_traj_loss.argtypes = [vp, ci, ci, cf] + [vp] * 10 + [ci, _ip] + [vp] * 5 + [vp, vp, cf] + [vp] * 5 + [vp]
-            L.pd_rollout_backward_traj_loss.argtypes = [vp, ci, ci, cf] + [vp] * 9 + [ci, _ip] + [vp] * 3 + [vp] * 4 + [vp] * 10 + [vp]
+            L.pd_rollout_forward_traj_loss.argtypes = head + fwd_params + frames + fwd_out + fwd_loss + stream
+            L.pd_rollout_backward_traj_loss.argtypes = head + params + frames + bwd_in + bwd_loss + grads + stream
         if hasattr(L, "pd_rollout_forward_traj_loss_fk"):
-            L.pd_rollout_forward_traj_loss_fk.argtypes = L.pd_rollout_forward_traj_loss.argtypes[:-1] + [ctypes.POINTER(_FkRide), vp]
-            L.pd_rollout_backward_traj_loss_fk.argtypes = L.pd_rollout_backward_traj_loss.argtypes[:-1] + [ctypes.POINTER(_FkRide), vp]
+            L.pd_rollout_forward_traj_loss_fk.argtypes = head + fwd_params + frames + fwd_out + fwd_loss + ride + stream
+            L.pd_rollout_backward_traj_loss_fk.argtypes = head + params + frames + bwd_in + bwd_loss + grads + ride + stream
         L.pd_fk_forward.argtypes = [vp, ci] + [vp] * 4 + [vp]
         L.pd_fk_backward.argtypes = [vp, ci] + [vp] * 6 + [vp]
         L.pd_se3_loss.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp, vp]
@@ -138,6 +151,12 @@ def _check(rc):
         raise RuntimeError("ppr_diffphys: " + lib().pd_last_error().decode())
 
 
+def _check_rc(name, rc):
+    """the entries that keep no error text (everything but the model and rollout calls)"""
+    if rc != 0:
+        raise RuntimeError("%s failed (rc %d)" % (name, rc))
+
+
 def _dev(t, name, shape_numel=None):
     """Device pointer of a contiguous float32 GPU tensor (an int: ctypes converts it for the c_void_p parameters); anything else raises
     -- no silent copy, no CPU fallback.  The checks run on every call of every entry point: one fast path, messages on the slow one."""
@@ -155,6 +174,11 @@ def _dev(t, name, shape_numel=None):
     if not t.is_contiguous():
         raise ValueError("%s must be contiguous" % name)
     raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), shape_numel))
+
+
+def _ptr(t, name, n=None):
+    """_dev(t), or None for an absent or an empty tensor (empty tensors have a null data_ptr: the library accepts it)"""
+    return _dev(t, name, n) if (t is not None and t.numel()) else None
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -320,6 +344,48 @@ class DeviceModel:
         f = [int(x) for x in frame2step]
         return (ctypes.c_int * max(len(f), 1))(*f), len(f)
 
+    # -- the argument runs of the six rollout entries, in the header's order (the argtypes of lib() carry the same names) --------
+    def _head(self, bs, nsteps, dt, q_init, qd_init, state0=None):
+        """state0 (a resumed rollout): the body state goes in q_init's place, NULL in qd_init's"""
+        if state0 is not None:
+            return self.h, bs, nsteps, float(dt), _ptr(state0, "state0", bs * self.nb * 13), None
+        return self.h, bs, nsteps, float(dt), _ptr(q_init, "q_init", bs * self.nq), _ptr(qd_init, "qd_init", bs * self.nqd)
+
+    _NO_RES_F = object()  # (_params: the adjoint entries have no res_f parameter -- None is a value, "all zeros")
+
+    def _params(self, bs, nsteps, torques, refs, target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia, res_f=_NO_RES_F):
+        """controls and parameters; the forward entries give res_f=, whose pointer follows that of torques"""
+        nb, nqd = self.nb, self.nqd
+        ctl = (_ptr(torques, "torques", nsteps * bs * nqd),)
+        if res_f is not self._NO_RES_F:
+            ctl += (_ptr(res_f, "res_f", nsteps * bs * nb * 6),)
+        return (ctl
+                + (_ptr(refs, "refs", nsteps * bs * nqd), _ptr(target_ke, "target_ke", bs * nqd), _ptr(target_kd, "target_kd", bs * nqd),
+                   _ptr(body_inv_mass, "body_inv_mass", bs * nb), _ptr(body_inertia, "body_inertia", bs * nb * 9),
+                   _ptr(body_inv_inertia, "body_inv_inertia", bs * nb * 9)))
+
+    def _fwd_buffers(self, out, bs, nsteps, nframes, dev, want_forces, save_trajectory):
+        """(ws, wp_pos, wp_vel, grf, jaf) of a forward rollout: the caller's ``out=`` or fresh ones"""
+        if out is None:
+            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False, save_trajectory=save_trajectory)
+        grf, jaf = (out["grf"], out["jaf"]) if want_forces else (None, None)
+        return out["ws"] if save_trajectory else None, out["wp_pos"], out["wp_vel"], grf, jaf
+
+    def _fwd_out(self, bs, nsteps, nframes, ws, wp_pos, wp_vel, grf, jaf):
+        n = nframes * bs * self.nb
+        return (_ptr(ws, "workspace", self.workspace_floats(bs, nsteps)), _ptr(wp_pos, "wp_pos", n * 7), _ptr(wp_vel, "wp_vel", n * 6),
+                _ptr(grf, "grf", n * 6), _ptr(jaf, "jaf", n * 6))
+
+    def _bwd_in(self, bs, nsteps, nframes, ws, adj_pos, adj_vel):
+        n = nframes * bs * self.nb
+        return _ptr(ws, "workspace", self.workspace_floats(bs, nsteps)), _ptr(adj_pos, "adj_pos", n * 7), _ptr(adj_vel, "adj_vel", n * 6)
+
+    @staticmethod
+    def _grad_tail(g, g_init=None):
+        """the ten gradient pointers; a per-step gradient that is no key of g is NULL (not wanted).  g_init: a resumed rollout's pair"""
+        return (g_init or (_ptr(g["q_init"], "g"), _ptr(g["qd_init"], "g"))) + tuple(_ptr(g.get(n), "g") for n in GRAD_NAMES) + tuple(
+            _ptr(g[n], "g") for n in ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia"))
+
     def rollout_forward(self, bs, nsteps, dt, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass,
                         body_inertia, body_inv_inertia, frame2step, want_forces=True, out=None, save_trajectory=True, state0=None):
         """-> wp_pos [F, bs*nb, 7], wp_vel [F, bs*nb, 6], grf, jaf [F, bs*nb, 6] (or None), workspace.
@@ -331,30 +397,17 @@ class DeviceModel:
         (no FK, no re-normalisation): the rollout continues that one bit for bit.
         torques, res_f: each may be None = all zeros -- the library gets NULL, nothing is allocated or read for it, every output is the
         bits of the launch with a zero tensor; its size is then not checked at all, the step count is checked on refs alone."""
-        nb, nq, nqd = self.nb, self.nq, self.nqd
         if state0 is not None:
             if q_init is not None or qd_init is not None:
                 raise ValueError("rollout_forward: state0 takes the place of q_init / qd_init (pass None for both)")
             state0 = self._state0(state0)
-            init = (_dev(state0, "state0", bs * nb * 13) if state0.numel() else None, None)
-        else:
-            init = None
         dev = q_init.device if state0 is None else state0.device
         f2s, nframes = self._f2s(frame2step)
-        if out is None:
-            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False, save_trajectory=save_trajectory)
-        ws, wp_pos, wp_vel = out["ws"] if save_trajectory else None, out["wp_pos"], out["wp_vel"]
-        grf, jaf = (out["grf"], out["jaf"]) if want_forces else (None, None)
-        p = lambda t, name, n: _dev(t, name, n) if (t is not None and t.numel()) else None  # empty tensors have a null data_ptr: the library accepts it
+        ws, wp_pos, wp_vel, grf, jaf = self._fwd_buffers(out, bs, nsteps, nframes, dev, want_forces, save_trajectory)
         _check(lib().pd_rollout_forward(
-            self.h, bs, nsteps, float(dt), *(init or (p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd))),
-            p(torques, "torques", nsteps * bs * nqd), p(res_f, "res_f", nsteps * bs * nb * 6),
-            p(refs, "refs", nsteps * bs * nqd), p(target_ke, "target_ke", bs * nqd),
-            p(target_kd, "target_kd", bs * nqd), p(body_inv_mass, "body_inv_mass", bs * nb),
-            p(body_inertia, "body_inertia", bs * nb * 9), p(body_inv_inertia, "body_inv_inertia", bs * nb * 9),
-            nframes, f2s, p(ws, "workspace", self.workspace_floats(bs, nsteps)), p(wp_pos, "wp_pos", nframes * bs * nb * 7),
-            p(wp_vel, "wp_vel", nframes * bs * nb * 6), p(grf, "grf", nframes * bs * nb * 6) if want_forces else None,
-            p(jaf, "jaf", nframes * bs * nb * 6) if want_forces else None, _stream()))
+            *self._head(bs, nsteps, dt, q_init, qd_init, state0),
+            *self._params(bs, nsteps, torques, refs, target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia, res_f=res_f),
+            nframes, f2s, *self._fwd_out(bs, nsteps, nframes, ws, wp_pos, wp_vel, grf, jaf), _stream()))
         return wp_pos, wp_vel, grf, jaf, ws
 
     # -- rollout with the trajectory loss evaluated at the frame states (C ABI v5, SURVEY section 8 row f4) ------------
@@ -373,10 +426,7 @@ class DeviceModel:
         nb, nq, nqd = self.nb, self.nq, self.nqd
         dev = q_init.device
         f2s, nframes = self._f2s(frame2step)
-        if out is None:
-            out = self.alloc_rollout(bs, nsteps, nframes, dev, want_forces, backward=False, save_trajectory=save_trajectory)
-        ws, wp_pos, wp_vel = out["ws"] if save_trajectory else None, out["wp_pos"], out["wp_vel"]
-        grf, jaf = (out["grf"], out["jaf"]) if want_forces else (None, None)
+        ws, wp_pos, wp_vel, grf, jaf = self._fwd_buffers(out, bs, nsteps, nframes, dev, want_forces, save_trajectory)
         e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
         seeds = save_trajectory or nsteps == 0
         tl = dict(reduced=e(4), table=e(bs, nframes), scale=e(bs, nframes), seed_pos=e(nframes, bs * nb, 7) if seeds else None,
@@ -384,28 +434,22 @@ class DeviceModel:
         if outseq is not None:
             if not (outseq.is_cuda and outseq.dtype in (torch.bool, torch.uint8) and outseq.is_contiguous() and outseq.numel() == bs * nframes):
                 raise ValueError("outseq must be a contiguous bool / uint8 GPU tensor of bs * nframes entries")
-        p = lambda t, name, n: _dev(t, name, n) if (t is not None and t.numel()) else None
         ride = None
         if fk is not None:
             jq, jqd = fk
             Ff, bsf = int(jq.shape[0]), int(jq.shape[1])
             tl["fk_body_q"], tl["fk_body_qd"] = e(bsf, Ff, nb, 7), e(bsf, Ff, nb, 6)
-            ride = _FkRide(Ff * bsf, bsf, p(jq, "fk joint_q", Ff * bsf * nq), p(jqd, "fk joint_qd", Ff * bsf * nqd),
-                           p(tl["fk_body_q"], "fk body_q", None), p(tl["fk_body_qd"], "fk body_qd", None), None, None, None, None)
+            ride = _FkRide(Ff * bsf, bsf, _ptr(jq, "fk joint_q", Ff * bsf * nq), _ptr(jqd, "fk joint_qd", Ff * bsf * nqd),
+                           _ptr(tl["fk_body_q"], "fk body_q"), _ptr(tl["fk_body_qd"], "fk body_qd"), None, None, None, None)
         entry = lib().pd_rollout_forward_traj_loss if ride is None else lib().pd_rollout_forward_traj_loss_fk
         _check(entry(
-            self.h, bs, nsteps, float(dt), p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd),
-            p(torques, "torques", nsteps * bs * nqd), p(res_f, "res_f", nsteps * bs * nb * 6),
-            p(refs, "refs", nsteps * bs * nqd), p(target_ke, "target_ke", bs * nqd),
-            p(target_kd, "target_kd", bs * nqd), p(body_inv_mass, "body_inv_mass", bs * nb),
-            p(body_inertia, "body_inertia", bs * nb * 9), p(body_inv_inertia, "body_inv_inertia", bs * nb * 9),
-            nframes, f2s, p(ws, "workspace", self.workspace_floats(bs, nsteps)), p(wp_pos, "wp_pos", nframes * bs * nb * 7),
-            p(wp_vel, "wp_vel", nframes * bs * nb * 6), p(grf, "grf", nframes * bs * nb * 6) if want_forces else None,
-            p(jaf, "jaf", nframes * bs * nb * 6) if want_forces else None,
-            p(target_pos, "target_pos", bs * nframes * nb * 7),
+            *self._head(bs, nsteps, dt, q_init, qd_init),
+            *self._params(bs, nsteps, torques, refs, target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia, res_f=res_f),
+            nframes, f2s, *self._fwd_out(bs, nsteps, nframes, ws, wp_pos, wp_vel, grf, jaf),
+            _ptr(target_pos, "target_pos", bs * nframes * nb * 7),
             ctypes.c_void_p(outseq.data_ptr()) if (outseq is not None and outseq.numel()) else None, ctypes.c_float(float(rot_ratio)),
-            p(tl["seed_pos"], "seed_pos", nframes * bs * nb * 7), p(tl["seed_gt"], "seed_gt", nframes * bs * nb * 7),
-            p(tl["table"], "loss_table", bs * nframes), _dev(tl["reduced"], "reduced", 4), p(tl["scale"], "scale", bs * nframes),
+            _ptr(tl["seed_pos"], "seed_pos", nframes * bs * nb * 7), _ptr(tl["seed_gt"], "seed_gt", nframes * bs * nb * 7),
+            _ptr(tl["table"], "loss_table", bs * nframes), _dev(tl["reduced"], "reduced", 4), _ptr(tl["scale"], "scale", bs * nframes),
             *(() if ride is None else (ctypes.byref(ride),)), _stream()))
         return wp_pos, wp_vel, grf, jaf, ws, tl
 
@@ -426,7 +470,6 @@ class DeviceModel:
         work = tl.get("work")
         if work is None:  # scratch for the seeds of this sweep (adj_pos / adj_vel layout), kept with the forward's outputs
             work = tl["work"] = torch.empty(nframes * bs * nb * 13, dtype=torch.float32, device=dev)
-        p = lambda t, name, n=None: _dev(t, name, n) if (t is not None and t.numel()) else None
         ride = None
         if fk is not None:
             jq, jqd, aq, aqd = fk
@@ -434,23 +477,16 @@ class DeviceModel:
             g = dict(g)
             g["fk_joint_q"] = torch.empty(Ff, bsf, nq, dtype=torch.float32, device=dev)
             g["fk_joint_qd"] = torch.empty(Ff, bsf, nqd, dtype=torch.float32, device=dev)
-            ride = _FkRide(Ff * bsf, bsf, p(jq, "fk joint_q", Ff * bsf * nq), p(jqd, "fk joint_qd", Ff * bsf * nqd), None, None,
-                           p(aq, "fk adj_body_q", Ff * bsf * nb * 7), p(aqd, "fk adj_body_qd", Ff * bsf * nb * 6),
-                           p(g["fk_joint_q"], "g"), p(g["fk_joint_qd"], "g"))
+            ride = _FkRide(Ff * bsf, bsf, _ptr(jq, "fk joint_q", Ff * bsf * nq), _ptr(jqd, "fk joint_qd", Ff * bsf * nqd), None, None,
+                           _ptr(aq, "fk adj_body_q", Ff * bsf * nb * 7), _ptr(aqd, "fk adj_body_qd", Ff * bsf * nb * 6),
+                           _ptr(g["fk_joint_q"], "g"), _ptr(g["fk_joint_qd"], "g"))
         entry = lib().pd_rollout_backward_traj_loss if ride is None else lib().pd_rollout_backward_traj_loss_fk
         _check(entry(
-            self.h, bs, nsteps, float(dt), p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd),
-            p(torques, "torques", nsteps * bs * nqd), p(refs, "refs", nsteps * bs * nqd),
-            p(target_ke, "target_ke", bs * nqd), p(target_kd, "target_kd", bs * nqd),
-            p(body_inv_mass, "body_inv_mass", bs * nb), p(body_inertia, "body_inertia", bs * nb * 9),
-            p(body_inv_inertia, "body_inv_inertia", bs * nb * 9), nframes, f2s,
-            p(ws, "workspace", self.workspace_floats(bs, nsteps)), p(adj_pos, "adj_pos", nframes * bs * nb * 7),
-            p(adj_vel, "adj_vel", nframes * bs * nb * 6), p(tl["seed_pos"], "seed_pos", nframes * bs * nb * 7),
-            p(tl["scale"], "scale", bs * nframes), _dev(g_loss, "g_loss", 1), p(work, "seed_work", nframes * bs * nb * 13),
-            p(g["q_init"], "g"), p(g["qd_init"], "g"),
-            p(g.get("torques"), "g"), p(g.get("res_f"), "g"), p(g.get("refs"), "g"), p(g["target_ke"], "g"),
-            p(g["target_kd"], "g"), p(g["body_inv_mass"], "g"), p(g["body_inertia"], "g"),
-            p(g["body_inv_inertia"], "g"), *(() if ride is None else (ctypes.byref(ride),)), _stream()))
+            *self._head(bs, nsteps, dt, q_init, qd_init),
+            *self._params(bs, nsteps, torques, refs, target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia),
+            nframes, f2s, *self._bwd_in(bs, nsteps, nframes, ws, adj_pos, adj_vel), _ptr(tl["seed_pos"], "seed_pos", nframes * bs * nb * 7),
+            _ptr(tl["scale"], "scale", bs * nframes), _dev(g_loss, "g_loss", 1), _ptr(work, "seed_work", nframes * bs * nb * 13),
+            *self._grad_tail(g), *(() if ride is None else (ctypes.byref(ride),)), _stream()))
         return g
 
     def saved_trajectory(self, ws, bs, nsteps):
@@ -501,7 +537,6 @@ class DeviceModel:
         torques: None = all zeros, EXACTLY when the forward's was (a mismatch cannot be detected; the step count is then checked on refs
         alone).  The gradients stay independent of it: g["torques"] / g["res_f"] of an absent input are computed when wanted, the bits of
         the launch with zero tensors."""
-        nb, nq, nqd = self.nb, self.nq, self.nqd
         want = grad_want(want)
         resumed = state0 is not None
         if resumed:
@@ -511,24 +546,11 @@ class DeviceModel:
         dev = state0.device if resumed else q_init.device
         f2s, nframes = self._f2s(frame2step)
         g = _select_grads(out["grads"], want) if out is not None else self._alloc_grads(bs, nsteps, dev, resumed=resumed, want=want)
-        p = lambda t, name, n=None: _dev(t, name, n) if (t is not None and t.numel()) else None
-        if resumed:
-            init = (p(state0, "state0", bs * nb * 13), None)
-            g_init = (p(g["state0"], "g state0", bs * nb * 13), None)
-        else:
-            init = (p(q_init, "q_init", bs * nq), p(qd_init, "qd_init", bs * nqd))
-            g_init = (p(g["q_init"], "g"), p(g["qd_init"], "g"))
+        g_init = (_ptr(g["state0"], "g state0", bs * self.nb * 13), None) if resumed else None
         _check(lib().pd_rollout_backward(
-            self.h, bs, nsteps, float(dt), *init,
-            p(torques, "torques", nsteps * bs * nqd), p(refs, "refs", nsteps * bs * nqd),
-            p(target_ke, "target_ke", bs * nqd), p(target_kd, "target_kd", bs * nqd),
-            p(body_inv_mass, "body_inv_mass", bs * nb), p(body_inertia, "body_inertia", bs * nb * 9),
-            p(body_inv_inertia, "body_inv_inertia", bs * nb * 9), nframes, f2s,
-            p(ws, "workspace", self.workspace_floats(bs, nsteps)), p(adj_pos, "adj_pos", nframes * bs * nb * 7),
-            p(adj_vel, "adj_vel", nframes * bs * nb * 6), *g_init,
-            p(g.get("torques"), "g"), p(g.get("res_f"), "g"), p(g.get("refs"), "g"), p(g["target_ke"], "g"),
-            p(g["target_kd"], "g"), p(g["body_inv_mass"], "g"), p(g["body_inertia"], "g"),
-            p(g["body_inv_inertia"], "g"), _stream()))
+            *self._head(bs, nsteps, dt, q_init, qd_init, state0),
+            *self._params(bs, nsteps, torques, refs, target_ke, target_kd, body_inv_mass, body_inertia, body_inv_inertia),
+            nframes, f2s, *self._bwd_in(bs, nsteps, nframes, ws, adj_pos, adj_vel), *self._grad_tail(g, g_init), _stream()))
         return g
 
     # -- FK -----------------------------------------------------------------------
@@ -566,10 +588,8 @@ def se3_loss(pred, gt, rot_ratio, want_grads=True):
     gp = torch.empty_like(pred) if want_grads else None
     gg = torch.empty_like(gt) if want_grads else None
     null = ctypes.c_void_p(0)
-    rc = lib().pd_se3_loss(n, dim, _dev(pred, "pred"), _dev(gt, "gt"), ctypes.c_float(float(rot_ratio)), _dev(loss, "loss"),
-                           _dev(gp, "g_pred") if want_grads else null, _dev(gg, "g_gt") if want_grads else null, _stream())
-    if rc != 0:
-        raise RuntimeError("pd_se3_loss failed (rc %d)" % rc)
+    _check_rc("pd_se3_loss", lib().pd_se3_loss(n, dim, _dev(pred, "pred"), _dev(gt, "gt"), ctypes.c_float(float(rot_ratio)), _dev(loss, "loss"),
+                                               _dev(gp, "g_pred") if want_grads else null, _dev(gg, "g_gt") if want_grads else null, _stream()))
     return loss, gp, gg
 
 
@@ -582,10 +602,9 @@ def reduce_loss(table, clip=False, want_scale=True):
     bs, F = table.shape
     reduced = torch.empty(4, device=table.device, dtype=torch.float32)
     scale = torch.empty_like(table) if want_scale else None
-    rc = lib().pd_reduce_loss(bs, F, _dev(table, "table") if table.numel() else ctypes.c_void_p(0), 1 if clip else 0, _dev(reduced, "reduced"),
-                              _dev(scale, "scale") if want_scale and table.numel() else ctypes.c_void_p(0), _stream())
-    if rc != 0:
-        raise RuntimeError("pd_reduce_loss failed (rc %d)" % rc)
+    _check_rc("pd_reduce_loss", lib().pd_reduce_loss(
+        bs, F, _dev(table, "table") if table.numel() else ctypes.c_void_p(0), 1 if clip else 0, _dev(reduced, "reduced"),
+        _dev(scale, "scale") if want_scale and table.numel() else ctypes.c_void_p(0), _stream()))
     return reduced, scale
 
 
@@ -609,9 +628,7 @@ def pose_op(op, a, b):
     b = target (..., 7)) or rotate_frame_vel(a = global, b = (..., 6)) in one launch; float32 contiguous GPU tensors."""
     n, bcast, no = _pose_n(op, a, b)
     out = torch.empty(b.shape[:-1] + (no,), device=b.device, dtype=torch.float32)
-    rc = lib().pd_pose_op(op, n, _dev(a, "a"), int(bcast), _dev(b, "b"), _dev(out, "out"), _stream())
-    if rc != 0:
-        raise RuntimeError("pd_pose_op failed (rc %d)" % rc)
+    _check_rc("pd_pose_op", lib().pd_pose_op(op, n, _dev(a, "a"), int(bcast), _dev(b, "b"), _dev(out, "out"), _stream()))
     return out
 
 
@@ -626,10 +643,9 @@ def colsum(x):
     n, k = int(x.shape[0]), int(x.shape[1])
     out = torch.empty(k, dtype=torch.float32, device=x.device)
     ws = torch.empty(COLSUM_SLICES * k, dtype=torch.float32, device=x.device) if n > 1024 else None   # row slices first, then the slices in order
-    rc = lib().pd_colsum(n, k, _dev(x, "x", n * k) if n * k else None, _dev(out, "out") if k else None, _dev(ws, "ws") if ws is not None else None,
-                         _stream())
-    if rc != 0:
-        raise RuntimeError("pd_colsum failed (rc %d)" % rc)
+    _check_rc("pd_colsum", lib().pd_colsum(
+        n, k, _dev(x, "x", n * k) if n * k else None, _dev(out, "out") if k else None, _dev(ws, "ws") if ws is not None else None,
+        _stream()))
     return out
 
 
@@ -645,9 +661,9 @@ def linear_wgrad(g, x, want_bias=True):
     gw = torch.empty(m, kin, dtype=torch.float32, device=g.device)
     gb = torch.empty(m, dtype=torch.float32, device=g.device) if want_bias else None
     ws = torch.empty(ws_floats, dtype=torch.float32, device=g.device)
-    rc = lib().pd_linear_wgrad(n, m, kin, _dev(g, "g", n * m), _dev(x, "x", n * kin), _dev(gw, "gw"), _dev(gb, "gb") if want_bias else None, _dev(ws, "ws"), _stream())
-    if rc != 0:
-        raise RuntimeError("pd_linear_wgrad failed (rc %d)" % rc)
+    _check_rc("pd_linear_wgrad", lib().pd_linear_wgrad(
+        n, m, kin, _dev(g, "g", n * m), _dev(x, "x", n * kin), _dev(gw, "gw"), _dev(gb, "gb") if want_bias else None,
+        _dev(ws, "ws"), _stream()))
     return gw, gb
 
 
@@ -658,10 +674,8 @@ def pose_op_vjp(op, a, b, g_out, need_a=True, need_b=True):
     g_a = torch.empty(b.shape[:-1] + (na,), device=b.device, dtype=torch.float32) if need_a else None
     g_b = torch.empty_like(b) if need_b else None
     null = ctypes.c_void_p(0)
-    rc = lib().pd_pose_op_vjp(op, n, _dev(a, "a"), int(bcast), _dev(b, "b"), _dev(g_out, "g_out", n * no),
-                              _dev(g_a, "g_a") if need_a else null, _dev(g_b, "g_b") if need_b else null, _stream())
-    if rc != 0:
-        raise RuntimeError("pd_pose_op_vjp failed (rc %d)" % rc)
+    _check_rc("pd_pose_op_vjp", lib().pd_pose_op_vjp(op, n, _dev(a, "a"), int(bcast), _dev(b, "b"), _dev(g_out, "g_out", n * no),
+                                                     _dev(g_a, "g_a") if need_a else null, _dev(g_b, "g_b") if need_b else null, _stream()))
     if need_a:
         g_a = colsum(g_a.reshape(-1, na)).reshape(a.shape) if bcast else g_a.reshape(a.shape)
     return g_a, g_b
@@ -679,10 +693,9 @@ def foot_height(body_q, c_body, c_point, c_dist):
     n = body_q.numel() // (nb * 7)
     h = torch.empty(body_q.shape[:-2], device=body_q.device, dtype=torch.float32)
     arg = torch.empty(body_q.shape[:-2], device=body_q.device, dtype=torch.int32)
-    rc = lib().pd_foot_height(n, nb, c_body.numel(), _dev(body_q, "body_q"), _dev_int(c_body, "c_body"), _dev(c_point, "c_point", c_body.numel() * 3),
-                              _dev(c_dist, "c_dist", c_body.numel()), _dev(h, "height"), _dev_int(arg, "arg"), _stream())
-    if rc != 0:
-        raise RuntimeError("pd_foot_height failed (rc %d)" % rc)
+    _check_rc("pd_foot_height", lib().pd_foot_height(
+        n, nb, c_body.numel(), _dev(body_q, "body_q"), _dev_int(c_body, "c_body"), _dev(c_point, "c_point", c_body.numel() * 3),
+        _dev(c_dist, "c_dist", c_body.numel()), _dev(h, "height"), _dev_int(arg, "arg"), _stream()))
     return h, arg
 
 
@@ -690,10 +703,9 @@ def foot_height_vjp(body_q, c_body, c_point, arg, g_h):
     nb = body_q.shape[-2]
     n = body_q.numel() // (nb * 7)
     g = torch.empty_like(body_q)
-    rc = lib().pd_foot_height_vjp(n, nb, _dev(body_q, "body_q"), _dev_int(c_body, "c_body"), _dev(c_point, "c_point"), _dev_int(arg, "arg"),
-                                  _dev(g_h, "g_height", n), _dev(g, "g_body_q"), _stream())
-    if rc != 0:
-        raise RuntimeError("pd_foot_height_vjp failed (rc %d)" % rc)
+    _check_rc("pd_foot_height_vjp", lib().pd_foot_height_vjp(
+        n, nb, _dev(body_q, "body_q"), _dev_int(c_body, "c_body"), _dev(c_point, "c_point"), _dev_int(arg, "arg"),
+        _dev(g_h, "g_height", n), _dev(g, "g_body_q"), _stream()))
     return g
 
 
