@@ -12,6 +12,7 @@ Behaviours kept on purpose (each is visible in the reference at the cited line):
   * a <dynamics damping> value, once seen, sticks for all later joints (:217-219)
   * density > 0 ignores the URDF <inertial> block entirely (:225-228)
   * one collision mesh per body; every collision adds a shape (:23-103)
+Not in the reference: ``collapse_fixed_joints=True`` (opt-in) welds the links on ``fixed`` joints into their parents.
 """
 import math
 
@@ -54,7 +55,10 @@ def parse_urdf(
     shape_mu=0.25,
     limit_ke=100.0,
     limit_kd=10.0,
+    collapse_fixed_joints=False,
 ):
+    """``collapse_fixed_joints`` (default off: the reference's import, FIXED joints kept as attachment springs): weld every link on
+    a ``fixed`` joint into its parent link once the robot is built (sim.collapse_builder) and return the sim.CollapseMap."""
     robot = URDF.load(filename)
     link_index = {}
     builder.add_articulation()
@@ -141,3 +145,5 @@ def parse_urdf(
             )
         _add_collisions(builder, link, child_link.collisions, density, *mat)
         link_index[child_name] = link
+    if collapse_fixed_joints:
+        return sim.collapse_builder(builder)

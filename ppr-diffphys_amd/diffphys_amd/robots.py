@@ -51,10 +51,13 @@ def link_weight(scale3, rule, is_kp_link):
 TEMPLATE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "templates")
 
 
-def build_articulation(name, urdf_root, mass_rule=DEFAULT_MASS_RULE):
+def build_articulation(name, urdf_root, mass_rule=DEFAULT_MASS_RULE, collapse_fixed_joints=False):
     """Returns (builder, info).  ``urdf_root`` is the directory holding
     ``laikago/laikago.urdf``, ``human.urdf``, ``quad.urdf`` (the reference keeps
-    them under ``data/urdf_templates``).  ``mass_rule``: see MASS_RULES (human / quad only)."""
+    them under ``data/urdf_templates``).  ``mass_rule``: see MASS_RULES (human / quad only).
+    ``collapse_fixed_joints`` (opt-in): weld the links on FIXED joints into their parents (sim.collapse_builder) AFTER the per-link
+    mass / inertia re-assignment below, so that a collapsed build equals the collapse of the compiled template; ``info["body_names"]``
+    then names the surviving bodies and ``info["collapse_map"]`` is the sim.CollapseMap."""
     rel, attach_ke, attach_kd, kp, kd, shape_ke, shape_kd = PRESETS[name]
     urdf_path = os.path.join(urdf_root, rel)
     b = sim.ModelBuilder()
@@ -95,6 +98,10 @@ def build_articulation(name, urdf_root, mass_rule=DEFAULT_MASS_RULE):
     b.joint_target_kd = [0.0] * 6 + [kd] * (n - 6)
     info = dict(joint_attach_ke=attach_ke, joint_attach_kd=attach_kd, kp=kp, kd=kd, body_names=body_names,
                 mass_rule=mass_rule if name in KP_LINKS else "mesh_density")
+    if collapse_fixed_joints:
+        # the gains above are per dof and a FIXED joint owns none: kp / kd / mass_rule describe the collapsed robot as they did the original
+        cmap = sim.collapse_builder(b)
+        info.update(body_names=[body_names[k] for k in cmap.kept], collapse_map=cmap)
     return b, info
 
 
@@ -115,9 +122,9 @@ def _body_link_names(urdf_path):
     return names
 
 
-def make_env(name, urdf_root, num_envs, device="cuda", mass_rule=DEFAULT_MASS_RULE):
+def make_env(name, urdf_root, num_envs, device="cuda", mass_rule=DEFAULT_MASS_RULE, collapse_fixed_joints=False):
     """What ``reinit_envs`` does (/root/reference/diffphys/dp_model.py:384-401)."""
-    art, info = build_articulation(name, urdf_root, mass_rule)
+    art, info = build_articulation(name, urdf_root, mass_rule, collapse_fixed_joints)
     builder = sim.ModelBuilder()
     for _ in range(num_envs):
         builder.add_rigid_articulation(art)
@@ -129,14 +136,17 @@ def make_env(name, urdf_root, num_envs, device="cuda", mass_rule=DEFAULT_MASS_RU
     return env, art, info
 
 
-def load_template(name):
-    """Compiled template dict (numpy arrays) from ``templates/<name>.npz``."""
+def load_template(name, collapse_fixed_joints=False):
+    """Compiled template dict (numpy arrays) from ``templates/<name>.npz``; with ``collapse_fixed_joints`` the links on FIXED joints
+    welded into their parents (sim.collapse_fixed_joints; sim.CollapseMap.from_template gives the map back)."""
     path = os.path.join(TEMPLATE_DIR, name + ".npz")
     with np.load(path) as z:
         tpl = {k: z[k] for k in z.files}
     tpl.setdefault("mass_rule", np.asarray("mesh_density" if name not in KP_LINKS else DEFAULT_MASS_RULE))
+    if collapse_fixed_joints:
+        tpl = sim.collapse_fixed_joints(tpl)[0]
     return tpl
 
 
-def env_from_template(name, num_envs, device="cuda"):
-    return sim.Model.from_template(load_template(name), num_envs, device)
+def env_from_template(name, num_envs, device="cuda", collapse_fixed_joints=False):
+    return sim.Model.from_template(load_template(name, collapse_fixed_joints), num_envs, device)

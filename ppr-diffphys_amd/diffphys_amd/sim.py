@@ -120,6 +120,250 @@ def _transform_inertia(m, I, p, q):
     return R @ I @ R.T + m * (np.dot(p, p) * np.eye(3) - np.outer(p, p))
 
 
+# ----------------------------------------------------------------------------
+# fixed-joint collapse (opt-in): weld the bodies on FIXED joints into their parents
+# ----------------------------------------------------------------------------
+MAX_CHILDREN = 8  # children per body the device model takes (supported joints)
+
+# template arrays with one row per dof / per coordinate: never trimmed with the bodies, whatever their length
+_PER_DOF_KEYS = ("joint_q", "joint_target_ke", "joint_target_kd", "joint_limit_lower", "joint_limit_upper", "joint_limit_ke",
+                 "joint_limit_kd")
+_MAP_KEYS = ("collapse_kept", "collapse_owner", "collapse_X_rel")  # how a collapsed template carries its CollapseMap
+
+
+def _x7_mul(a, b):
+    """a o b for (p, q) 7-vectors"""
+    return np.concatenate([a[:3] + quat_rotate(a[3:], b[:3]), quat_mul(a[3:], b[3:])])
+
+
+def _x7_inv(a):
+    qi = np.array([-a[3], -a[4], -a[5], a[6]])
+    return np.concatenate([-quat_rotate(qi, a[:3]), qi])
+
+
+def _x7_identity():
+    return np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0])
+
+
+def _collapse_plan(jtype, jparent, X_p, X_c, mass, com, inertia, names=None):
+    """The collapse on float64 arrays.  Returns None when no FIXED joint hangs on a body, else a dict: kept [nb_new] (old index
+    of each new body), owner [nb_old] (new index), X_rel [nb_old, 7], and per NEW body parent, X_p, mass, com, inertia.
+    Rows that the collapse does not touch are copied, not recomputed."""
+    nb = len(jtype)
+    removed = [int(jtype[i]) == JOINT_FIXED and int(jparent[i]) >= 0 for i in range(nb)]
+    if not any(removed):
+        return None
+    root = list(range(nb))  # old index of the surviving body that carries each old body
+    X_rel = np.tile(_x7_identity(), (nb, 1))
+    new_X_p = np.array(X_p, dtype=np.float64)
+    for i in range(nb):  # parents precede children
+        p = int(jparent[i])
+        if p >= i:
+            raise ValueError("parents must precede children (body %d has parent %d)" % (i, p))
+        if removed[i]:
+            X = _x7_mul(new_X_p[i], _x7_inv(np.asarray(X_c[i], dtype=np.float64)))  # c's frame in p's frame
+            X[3:] /= np.linalg.norm(X[3:])  # a stored fp32 quaternion is a unit one to 6e-8 only: weld by a proper rotation
+            X_rel[i] = _x7_mul(X_rel[p], X) if removed[p] else X
+            root[i] = root[p]
+        elif p >= 0 and removed[p]:
+            new_X_p[i] = _x7_mul(X_rel[p], new_X_p[i])
+    kept = [i for i in range(nb) if not removed[i]]
+    new_of = {k: n for n, k in enumerate(kept)}
+    owner = np.array([new_of[root[i]] for i in range(nb)], dtype=np.int32)
+    parent = np.array([new_of[root[int(jparent[k])]] if int(jparent[k]) >= 0 else -1 for k in kept], dtype=np.int32)
+    counts = np.bincount(parent[parent >= 0], minlength=len(kept))
+    if counts.max(initial=0) > MAX_CHILDREN:
+        n = int(counts.argmax())
+        label = "%d" % kept[n] if names is None else "%d (%s)" % (kept[n], names[kept[n]])
+        raise ValueError("collapse_fixed_joints: body %s would have %d children; at most %d per body are supported"
+                         % (label, counts[n], MAX_CHILDREN))
+    m_new = np.array([mass[k] for k in kept], dtype=np.float64)
+    com_new = np.array([com[k] for k in kept], dtype=np.float64).reshape(-1, 3)
+    I_new = np.array([inertia[k] for k in kept], dtype=np.float64).reshape(-1, 3, 3)
+    for n, k in enumerate(kept):
+        group = [i for i in range(nb) if root[i] == k]
+        if len(group) == 1:
+            continue
+        # mass properties of the welded bodies, in k's axes: the inertias are about each body's own com (integrate_bodies), so every part
+        # is rotated into k's axes and moved to the common com by the parallel-axis term (_transform_inertia)
+        ms = np.array([float(mass[i]) for i in group])
+        cs = np.array([com[k] if i == k else quat_rotate(X_rel[i][3:], com[i]) + X_rel[i][:3] for i in group], dtype=np.float64)
+        m = ms.sum()
+        c = (ms[:, None] * cs).sum(0) / m if m != 0.0 else np.asarray(com[k], dtype=np.float64)
+        I = np.zeros((3, 3))
+        for i, mi, ci in zip(group, ms, cs):
+            I += _transform_inertia(mi, np.asarray(inertia[i], dtype=np.float64), ci - c, X_rel[i][3:])
+        m_new[n], com_new[n], I_new[n] = m, c, I
+    return dict(kept=np.array(kept, dtype=np.int32), owner=owner, X_rel=X_rel, parent=parent, X_p=new_X_p[kept], mass=m_new,
+                com=com_new, inertia=I_new, touched=[len([i for i in range(nb) if root[i] == k]) > 1 for k in kept],
+                reparented=[int(jparent[k]) >= 0 and removed[int(jparent[k])] for k in kept])
+
+
+class CollapseMap:
+    """What :func:`collapse_fixed_joints` did to the bodies: ``kept`` [nb_new] the old index of each new body, ``owner`` [nb_old] the
+    new body that carries each old body, ``X_rel`` [nb_old, 7] the old body's pose in its owner's frame (the identity for kept bodies)."""
+
+    def __init__(self, kept, owner, X_rel):
+        self.kept = np.ascontiguousarray(kept, dtype=np.int32)
+        self.owner = np.ascontiguousarray(owner, dtype=np.int32)
+        self.X_rel = np.ascontiguousarray(X_rel, dtype=np.float64).reshape(-1, 7)
+        self._cache = {}
+
+    @property
+    def nb_old(self):
+        return len(self.owner)
+
+    @property
+    def nb_new(self):
+        return len(self.kept)
+
+    @staticmethod
+    def identity(nb):
+        return CollapseMap(np.arange(nb), np.arange(nb), np.tile(_x7_identity(), (nb, 1)))
+
+    @staticmethod
+    def from_template(tpl):
+        """The map a collapsed template carries (``collapse_*`` arrays); the identity map for any other template."""
+        if _MAP_KEYS[0] not in tpl:
+            return CollapseMap.identity(int(tpl["nb"]))
+        return CollapseMap(*[tpl[k] for k in _MAP_KEYS])
+
+    def expand_poses(self, wp_pos):
+        """Poses of the collapsed model's bodies ``[..., nb_new, 7]`` -> poses of the ORIGINAL bodies ``[..., nb_old, 7]``: pose of its
+        owner o X_rel.  float32 GPU tensors go through the library's pose kernel (``pd_pose_op`` PD_POSE_ROTATE_FRAME, one launch) and are
+        differentiable through its VJP; CPU tensors (any float dtype) through the same composition in plain torch."""
+        import torch
+
+        if wp_pos.shape[-2:] != (self.nb_new, 7):
+            raise ValueError("expand_poses: poses (..., %d, 7) of the collapsed model; got %s" % (self.nb_new, tuple(wp_pos.shape)))
+        key = (wp_pos.device, wp_pos.dtype)
+        if key not in self._cache:
+            self._cache[key] = (torch.from_numpy(self.owner.astype(np.int64)).to(wp_pos.device),
+                                torch.from_numpy(self.X_rel).to(device=wp_pos.device, dtype=wp_pos.dtype))
+        owner, x_rel = self._cache[key]
+        a = wp_pos.index_select(-2, owner)
+        b = x_rel.expand(a.shape)
+        if wp_pos.is_cuda:
+            from .dp_utils import _PoseOpHip, _need_gpu
+
+            _need_gpu("expand_poses", wp_pos)
+            return _PoseOpHip.apply(1, a, b.contiguous())
+        return _rotate_frame_torch(a, b)
+
+
+def _rotate_frame_torch(a, b):
+    """se3_mat2vec(se3_vec2mat(a) @ se3_vec2mat(b)) on (..., 7) poses, quaternion real part last: the function of the pose kernel's
+    PD_POSE_ROTATE_FRAME (csrc/pd_pose.hip) -- scale-invariant in both quaternions, unit quaternion out, the largest of its four
+    components positive."""
+    import torch
+
+    def rot(q):  # (x, y, z, w), any norm
+        x, y, z, w = q.unbind(-1)
+        s = 2.0 / (q * q).sum(-1)
+        m = torch.stack([1 - s * (y * y + z * z), s * (x * y - z * w), s * (x * z + y * w),
+                         s * (x * y + z * w), 1 - s * (x * x + z * z), s * (y * z - x * w),
+                         s * (x * z - y * w), s * (y * z + x * w), 1 - s * (x * x + y * y)], -1)
+        return m.reshape(q.shape[:-1] + (3, 3))
+
+    Ra = rot(a[..., 3:])
+    R = Ra @ rot(b[..., 3:])
+    p = a[..., :3] + (Ra @ b[..., :3, None])[..., 0]
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = R.reshape(R.shape[:-2] + (9,)).unbind(-1)
+    d = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], -1)  # 4 w^2, x^2, ..
+    pos = d > 0
+    q_abs = torch.where(pos, torch.sqrt(torch.where(pos, d, torch.ones_like(d))), torch.zeros_like(d))
+    cand = torch.stack([  # rows: the form built on w, x, y, z; columns (w, x, y, z)
+        torch.stack([q_abs[..., 0] ** 2, m21 - m12, m02 - m20, m10 - m01], -1),
+        torch.stack([m21 - m12, q_abs[..., 1] ** 2, m10 + m01, m02 + m20], -1),
+        torch.stack([m02 - m20, m10 + m01, q_abs[..., 2] ** 2, m12 + m21], -1),
+        torch.stack([m10 - m01, m20 + m02, m21 + m12, q_abs[..., 3] ** 2], -1)], -2)
+    cand = cand / (2.0 * q_abs[..., None].clamp(min=0.1))
+    best = q_abs.argmax(-1)
+    q = cand.gather(-2, best[..., None, None].expand(best.shape + (1, 4))).squeeze(-2)
+    return torch.cat([p, q[..., 1:4], q[..., 0:1]], -1)
+
+
+def collapse_fixed_joints(tpl):
+    """Template dict in, ``(template dict, CollapseMap)`` out: every FIXED joint whose parent is a body is removed and its body welded
+    into that parent (chains transitively; a FIXED joint to the world stays).  For a removed body c with surviving ancestor p and
+    X = joint_X_p[c] o inverse(joint_X_c[c]) (fixed chains compose): mass, com and inertia of c are merged into p's, c's contact
+    candidates move to p with contact_point <- X contact_point (order, dist and material kept), c's children hang on p with
+    joint_X_p <- X o joint_X_p.  FIXED joints own no coordinates, so nq, nqd and every per-dof array are unchanged.
+
+    This changes the physics ON PURPOSE: a stiff attachment spring becomes a rigid weld.  Arithmetic is float64; results are stored
+    in the input's dtypes; rows the collapse does not touch keep their bits.  A template without such joints is returned as it is.
+    Raises ValueError when a body would end up with more than MAX_CHILDREN children.  The collapsed template carries its map
+    (``collapse_kept`` / ``collapse_owner`` / ``collapse_X_rel``: :meth:`CollapseMap.from_template`)."""
+    nb = int(tpl["nb"])
+    names = [str(n) for n in tpl["body_names"]] if "body_names" in tpl else None
+    f64 = lambda k: np.asarray(tpl[k], dtype=np.float64)
+    plan = _collapse_plan(np.asarray(tpl["joint_type"]), np.asarray(tpl["joint_parent"]), f64("joint_X_p").reshape(nb, 7),
+                          f64("joint_X_c").reshape(nb, 7), f64("body_mass"), f64("body_com").reshape(nb, 3),
+                          f64("body_inertia").reshape(nb, 3, 3), names)
+    if plan is None:
+        return tpl, CollapseMap.identity(nb)
+    kept, owner, X_rel = plan["kept"], plan["owner"], plan["X_rel"]
+    out = dict(tpl)
+    for k, v in tpl.items():  # every per-body array loses the removed rows (per-dof arrays never: a FIXED joint owns none)
+        a = np.asarray(v)
+        if (k.startswith("body_") or k.startswith("joint_")) and k not in _PER_DOF_KEYS and a.ndim >= 1 and a.shape[0] == nb:
+            out[k] = np.ascontiguousarray(a[kept])
+    out["nb"] = np.asarray(tpl["nb"]).dtype.type(len(kept))
+    out["joint_parent"] = plan["parent"].astype(np.asarray(tpl["joint_parent"]).dtype)
+
+    def put(key, rows, which):  # recomputed rows only, in the stored dtype
+        a = out[key]
+        for n, hit in enumerate(which):
+            if hit:
+                a[n] = rows[n].reshape(a[n].shape).astype(a.dtype)
+
+    put("joint_X_p", plan["X_p"], plan["reparented"])
+    put("body_mass", plan["mass"], plan["touched"])
+    put("body_com", plan["com"], plan["touched"])
+    put("body_inertia", plan["inertia"], plan["touched"])
+    cb = np.asarray(tpl["contact_body"])
+    cp = np.asarray(tpl["contact_point"])
+    new_cp = np.array(cp, copy=True)
+    for i in np.nonzero(kept[owner] != np.arange(nb))[0]:  # the removed bodies
+        sel = cb == i
+        if sel.any():
+            R = quat_to_matrix(X_rel[i][3:])
+            new_cp[sel] = (cp[sel].astype(np.float64) @ R.T + X_rel[i][:3]).astype(cp.dtype)
+    out["contact_body"] = owner[cb].astype(cb.dtype)
+    out["contact_point"] = new_cp
+    out["collapse_kept"], out["collapse_owner"], out["collapse_X_rel"] = kept, owner, X_rel
+    return out, CollapseMap(kept, owner, X_rel)
+
+
+def collapse_builder(b):
+    """:func:`collapse_fixed_joints` on a :class:`ModelBuilder`, in place and in float64 throughout: the same merge of bodies and joints,
+    with the removed bodies' SHAPES moved to their owners (shape_transform <- X o shape_transform) instead of contact candidates.
+    Returns the CollapseMap (the identity map when nothing was collapsed)."""
+    nb = len(b.body_mass)
+    plan = _collapse_plan(b.joint_type, b.joint_parent, np.array([t.as7() for t in b.joint_X_p]).reshape(nb, 7),
+                          np.array([t.as7() for t in b.joint_X_c]).reshape(nb, 7), b.body_mass, b.body_com, b.body_inertia)
+    if plan is None:
+        return CollapseMap.identity(nb)
+    kept, owner, X_rel = plan["kept"], plan["owner"], plan["X_rel"]
+    for name in ("body_mass", "body_inertia", "body_com", "body_q", "body_qd", "joint_type", "joint_parent", "joint_X_p", "joint_X_c",
+                 "joint_axis", "joint_armature", "joint_q_start", "joint_qd_start"):
+        lst = getattr(b, name)
+        setattr(b, name, [lst[k] for k in kept])
+    b.joint_parent = [int(p) for p in plan["parent"]]
+    for n in range(len(kept)):
+        if plan["reparented"][n]:
+            b.joint_X_p[n] = transform(plan["X_p"][n][:3], plan["X_p"][n][3:])
+        if plan["touched"][n]:
+            b.body_mass[n], b.body_com[n], b.body_inertia[n] = float(plan["mass"][n]), plan["com"][n].copy(), plan["inertia"][n].copy()
+    for s, body in enumerate(b.shape_body):
+        if body >= 0:
+            if kept[owner[body]] != body:
+                x = _x7_mul(X_rel[body], b.shape_transform[s].as7())
+                b.shape_transform[s] = transform(x[:3], x[3:])
+            b.shape_body[s] = int(owner[body])
+    return CollapseMap(kept, owner, X_rel)
+
+
 class Mesh:
     """Triangle mesh with density-1 mass properties (SURVEY.md Appendix A.2:
     4-point tetrahedral quadrature about the vertex mean)."""
