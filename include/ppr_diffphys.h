@@ -324,8 +324,23 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * with se3_vec2mat / se3_mat2vec / quaternion <-> matrix as in diffphys/geom_utils.py:148-203 (quaternions are divided
  * by |q|^2, the best-conditioned of the four matrix->quaternion forms is taken).  a_broadcast != 0: `a` is ONE 7-vector
  * shared by all n elements.  The VJP writes g_a [n][7] (per element also when `a` is broadcast: the caller sums) and
- * g_b [n][6 or 7]; either may be NULL. */
-enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2 };
+ * g_b [n][6 or 7]; either may be NULL.
+ *
+ * Pinhole projection of body origins / body-fixed points (the 2D keypoint term; diffphys/dp_utils.py:184-214 parse_rtk,
+ * project_bodies), same launch shape, one lane per element:
+ *   PD_POSE_PROJECT        a = camera row [16] = the reference's rtk 4x4, row-major: rows 0-2 [R|t] world -> view, row 3
+ *                          (fx, fy, cx, cy);  b = pose [n][7], only p is read -> out [n][2] =
+ *                          ((fx x + cx z) / z, (fy y + cy z) / z) with (x, y, z) = R p + t.  No clamp: z = 0 gives
+ *                          inf / NaN as in the reference.
+ *   PD_POSE_PROJECT_POINT  b = [n][10]: a pose followed by a body-frame point c; the projected point is p + R(q) c with
+ *                          R(q) as PD_POSE_ROTATE_FRAME forms it (divided by |q|^2).
+ * For THESE TWO ops a_broadcast is a group size g, not a flag: g = 0 -- one camera row per element; g >= 1 -- camera row
+ * i / g serves element i (g = bodies per (env, frame); g = n: one camera for all).  n % g != 0 (or g < 0) is refused with
+ * a pd_last_error text before anything is launched or written.  The VJP writes g_a [n][16] per element, row 3 included
+ * (the caller sums over each group), and g_b [n][7] (quaternion entries 0) or [n][10]; either may be NULL.
+ * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
+ * leaves its reason in pd_last_error. */
+enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

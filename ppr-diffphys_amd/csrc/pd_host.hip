@@ -12,6 +12,8 @@
 
 static thread_local std::string g_err;
 static int fail(const std::string &msg) { g_err = msg; return 1; }
+// the same for the other translation units (pd_pose.hip); hidden: no part of the C ABI
+__attribute__((visibility("hidden"))) int pd_set_error(const char *msg) { return fail(msg); }
 static int hip_fail(hipError_t e, const char *what) { return fail(std::string(what) + ": " + hipGetErrorString(e)); }
 
 struct pd_model {

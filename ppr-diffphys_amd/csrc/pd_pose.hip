@@ -16,6 +16,9 @@
 #include <hip/hip_runtime.h>
 #include "../../include/ppr_diffphys.h"
 
+// pd_host.hip: sets the text pd_last_error() returns, returns 1 (library-internal: hidden, no part of the C ABI)
+__attribute__((visibility("hidden"))) int pd_set_error(const char *msg);
+
 namespace {
 
 struct Dual { float v, d; };
@@ -107,12 +110,23 @@ __device__ __forceinline__ void compose_out7(const T *Ra, const T *pa, const T *
   out[3] = q[1]; out[4] = q[2]; out[5] = q[3]; out[6] = q[0];
 }
 
-enum { OP_COMPOSE_DELTA = PD_POSE_COMPOSE_DELTA, OP_ROTATE_FRAME = PD_POSE_ROTATE_FRAME, OP_ROTATE_VEL = PD_POSE_ROTATE_VEL };
+enum { OP_COMPOSE_DELTA = PD_POSE_COMPOSE_DELTA, OP_ROTATE_FRAME = PD_POSE_ROTATE_FRAME, OP_ROTATE_VEL = PD_POSE_ROTATE_VEL,
+       OP_PROJECT = PD_POSE_PROJECT, OP_PROJECT_POINT = PD_POSE_PROJECT_POINT };
 
 template <int OP> struct Shape;
 template <> struct Shape<OP_COMPOSE_DELTA> { static constexpr int NA = 7, NB = 6, NO = 7; };  // a = target pose, b = delta (p, axis-angle)
 template <> struct Shape<OP_ROTATE_FRAME> { static constexpr int NA = 7, NB = 7, NO = 7; };   // a = global pose, b = target pose
 template <> struct Shape<OP_ROTATE_VEL> { static constexpr int NA = 7, NB = 6, NO = 6; };     // a = global pose, b = (linear, angular)
+template <> struct Shape<OP_PROJECT> { static constexpr int NA = 16, NB = 7, NO = 2; };       // a = camera (rtk 4x4), b = pose (p used)
+template <> struct Shape<OP_PROJECT_POINT> { static constexpr int NA = 16, NB = 10, NO = 2; };  // a = camera, b = (pose, body-frame point)
+
+// Where element i finds its row of `a`.  Ops 0-2: a_sel is the row stride in floats (0 = ONE row shared by all).  Projection ops: a_sel is
+// the group size g -- camera row i / g serves element i (0 = a row per element).
+template <int OP>
+__device__ __forceinline__ size_t a_offset(int i, int a_sel) {
+  if (OP == OP_PROJECT || OP == OP_PROJECT_POINT) return (size_t)(a_sel ? i / a_sel : i) * Shape<OP>::NA;
+  return (size_t)i * a_sel;
+}
 
 template <int OP, class T>
 __device__ __forceinline__ void pose_fn(const T *a, const T *b, T *out) {
@@ -127,6 +141,20 @@ __device__ __forceinline__ void pose_fn(const T *a, const T *b, T *out) {
     pose7(a, Rg, pg);
     pose7(b, R2, p2);
     compose_out7(Rg, pg, R2, p2, out);
+  } else if (OP == OP_PROJECT || OP == OP_PROJECT_POINT) {  // project_bodies   dp_utils.py:200-214
+    // a = rtk: rows 0-2 [R|t] world -> view, row 3 (fx, fy, cx, cy); K @ (R p + t), then the division by its third entry -- no clamp
+    T p[3] = {b[0], b[1], b[2]};
+    if (OP == OP_PROJECT_POINT) {  // the body-frame point b[7..9] instead of the body origin: p + R(q) c
+      T Rb[9];
+      quat_to_mat(b[6], b[3], b[4], b[5], Rb);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) p[i] = p[i] + (Rb[3 * i] * b[7] + Rb[3 * i + 1] * b[8] + Rb[3 * i + 2] * b[9]);
+    }
+    T v[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[i] = a[4 * i] * p[0] + a[4 * i + 1] * p[1] + a[4 * i + 2] * p[2] + a[4 * i + 3];
+    out[0] = (a[12] * v[0] + a[14] * v[2]) / v[2];
+    out[1] = (a[13] * v[1] + a[15] * v[2]) / v[2];
   } else {  // both halves rotated by the rotation of global   dp_utils.py:76-84
     T Rg[9];
     quat_to_mat(a[6], a[3], a[4], a[5], Rg);
@@ -138,14 +166,14 @@ __device__ __forceinline__ void pose_fn(const T *a, const T *b, T *out) {
 }
 
 template <int OP>
-__global__ __launch_bounds__(256) void k_pose_fwd(int n, const float *__restrict__ a, int a_stride, const float *__restrict__ b,
+__global__ __launch_bounds__(256) void k_pose_fwd(int n, const float *__restrict__ a, int a_sel, const float *__restrict__ b,
                                                   float *__restrict__ out) {
   using S = Shape<OP>;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   float av[S::NA], bv[S::NB], o[S::NO];
 #pragma unroll
-  for (int k = 0; k < S::NA; ++k) av[k] = a[(size_t)i * a_stride + k];
+  for (int k = 0; k < S::NA; ++k) av[k] = a[a_offset<OP>(i, a_sel) + k];
 #pragma unroll
   for (int k = 0; k < S::NB; ++k) bv[k] = b[(size_t)i * S::NB + k];
   pose_fn<OP, float>(av, bv, o);
@@ -154,7 +182,7 @@ __global__ __launch_bounds__(256) void k_pose_fwd(int n, const float *__restrict
 }
 
 template <int OP>
-__global__ __launch_bounds__(256) void k_pose_vjp(int n, const float *__restrict__ a, int a_stride, const float *__restrict__ b,
+__global__ __launch_bounds__(256) void k_pose_vjp(int n, const float *__restrict__ a, int a_sel, const float *__restrict__ b,
                                                   const float *__restrict__ g_out, float *__restrict__ g_a, float *__restrict__ g_b) {
   using S = Shape<OP>;
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -162,7 +190,7 @@ __global__ __launch_bounds__(256) void k_pose_vjp(int n, const float *__restrict
   Dual av[S::NA], bv[S::NB], o[S::NO];
   float g[S::NO];
 #pragma unroll
-  for (int k = 0; k < S::NA; ++k) av[k] = {a[(size_t)i * a_stride + k], 0.0f};
+  for (int k = 0; k < S::NA; ++k) av[k] = {a[a_offset<OP>(i, a_sel) + k], 0.0f};
 #pragma unroll
   for (int k = 0; k < S::NB; ++k) bv[k] = {b[(size_t)i * S::NB + k], 0.0f};
 #pragma unroll
@@ -242,23 +270,31 @@ __global__ __launch_bounds__(256) void k_foot_height_vjp(int n, int nb, const fl
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
-  const int a_stride = a_bcast ? 0 : Shape<OP>::NA;
+  constexpr bool project = OP == OP_PROJECT || OP == OP_PROJECT_POINT;
+  const int a_sel = project ? a_bcast : (a_bcast ? 0 : Shape<OP>::NA);  // (a_offset)
   if (out)
-    hipLaunchKernelGGL(k_pose_fwd<OP>, grid, block, 0, st, n, a, a_stride, b, out);
+    hipLaunchKernelGGL(k_pose_fwd<OP>, grid, block, 0, st, n, a, a_sel, b, out);
   else
-    hipLaunchKernelGGL(k_pose_vjp<OP>, grid, block, 0, st, n, a, a_stride, b, g_out, g_a, g_b);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+    hipLaunchKernelGGL(k_pose_vjp<OP>, grid, block, 0, st, n, a, a_sel, b, g_out, g_a, g_b);
+  if (hipGetLastError() == hipSuccess) return 0;
+  pd_set_error("pd_pose_op: the kernel launch failed");
+  return 2;
 }
 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || op > 2) return 1;
+  if (n < 0 || op < 0 || op > PD_POSE_PROJECT_POINT) return pd_set_error("pd_pose_op: n < 0 or an unknown op");
+  const bool project = op >= PD_POSE_PROJECT;
+  if (project && (a_bcast < 0 || (a_bcast > 0 && n % a_bcast != 0)))  // before the n == 0 return: a bad group size is refused at every n
+    return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the camera group size a_broadcast");
   if (n == 0) return 0;
-  if (!a || !b) return 1;
+  if (!a || !b) return pd_set_error("pd_pose_op: a NULL operand");
   hipStream_t st = (hipStream_t)stream;
   switch (op) {
     case OP_COMPOSE_DELTA: return launch_pose<OP_COMPOSE_DELTA>(n, a, a_bcast, b, out, g_out, g_a, g_b, st);
     case OP_ROTATE_FRAME: return launch_pose<OP_ROTATE_FRAME>(n, a, a_bcast, b, out, g_out, g_a, g_b, st);
-    default: return launch_pose<OP_ROTATE_VEL>(n, a, a_bcast, b, out, g_out, g_a, g_b, st);
+    case OP_ROTATE_VEL: return launch_pose<OP_ROTATE_VEL>(n, a, a_bcast, b, out, g_out, g_a, g_b, st);
+    case OP_PROJECT: return launch_pose<OP_PROJECT>(n, a, a_bcast, b, out, g_out, g_a, g_b, st);
+    default: return launch_pose<OP_PROJECT_POINT>(n, a, a_bcast, b, out, g_out, g_a, g_b, st);
   }
 }
 
@@ -322,13 +358,13 @@ extern "C" int pd_colsum(int n, int k, const float *x_dev, float *out_dev, float
 }
 
 extern "C" int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream) {
-  if (n > 0 && !out_dev) return 1;
+  if (n > 0 && !out_dev) return pd_set_error("pd_pose_op: out_dev is NULL");
   return pose_dispatch(op, n, a_dev, a_broadcast, b_dev, out_dev, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev, float *g_a_dev,
                               float *g_b_dev, void *stream) {
-  if (n > 0 && (!g_out_dev || (!g_a_dev && !g_b_dev))) return 1;
+  if (n > 0 && (!g_out_dev || (!g_a_dev && !g_b_dev))) return pd_set_error("pd_pose_op_vjp: g_out_dev is NULL, or both g_a_dev and g_b_dev");
   return pose_dispatch(op, n, a_dev, a_broadcast, b_dev, nullptr, g_out_dev, g_a_dev, g_b_dev, stream);
 }
 

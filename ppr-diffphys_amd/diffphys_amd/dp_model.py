@@ -369,7 +369,10 @@ class ForwardWarpTrajLoss(torch.autograd.Function):
                                                               outseq_idx [bs,F] bool, self)
 
     loss_traj is the reduced scalar; wp_pos / wp_vel come back DETACHED (non-differentiable outputs: what the other loss terms and
-    query() consume).  Forward = ONE rollout launch that also evaluates se3_loss and its gradients at the frame states + one
+    query() consume) -- unless ``self.differentiable_states`` is True (opt-in, read like ``checkpoint_steps``): then they are differentiable
+    outputs, and what a further term (dp_utils.reproj_loss on project_bodies(wp_pos), say) sends back to them is added to the adjoint's own
+    seeds (adj_pos / adj_vel of ``pd_rollout_backward_traj_loss``): the gradients are those of that library call, bit for bit.
+    Forward = ONE rollout launch that also evaluates se3_loss and its gradients at the frame states + one
     one-workgroup launch for reduce_loss; backward = a few-microsecond launch that builds the seeds from what the forward left, scaled
     by the upstream gradient of loss_traj read on the device, then the adjoint rollout launch -- no pose, seed or per-frame loss goes
     through a torch op in between.
@@ -383,7 +386,7 @@ class ForwardWarpTrajLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _gp, _gv):
-        return _traj_loss_backward(ctx, g_loss, None) + (None,)
+        return _traj_loss_backward(ctx, g_loss, None, (_gp, _gv)) + (None,)
 
 
 class ForwardWarpTrajLossFK(torch.autograd.Function):
@@ -406,7 +409,7 @@ class ForwardWarpTrajLossFK(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _gp, _gv, g_qpos, g_qvel, _pid):
-        g = _traj_loss_backward(ctx, g_loss, (g_qpos, g_qvel))
+        g = _traj_loss_backward(ctx, g_loss, (g_qpos, g_qvel), (_gp, _gv))
         return g[:13] + g[13:] + (None,)
 
 
@@ -434,7 +437,13 @@ def _traj_loss_forward(ctx, rollout_inputs, target_position, outseq_idx, self, q
     ctx.mass_shape, ctx.tgt_shape = body_mass.shape, target_position.shape
     _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
     self.traj_loss_info = tl["reduced"]
-    ctx.mark_non_differentiable(wp_pos, wp_vel)
+    # self.differentiable_states (absent / False: the states come back detached, as they always did): wp_pos / wp_vel are differentiable
+    # outputs and their incoming gradients join the adjoint's own seeds (_traj_loss_backward).  Gradients nobody sent stay None then.
+    ctx.diff_states = bool(getattr(self, "differentiable_states", False))
+    if ctx.diff_states:
+        ctx.set_materialize_grads(False)
+    else:
+        ctx.mark_non_differentiable(wp_pos, wp_vel)
     out = (tl["reduced"][0].clone(), wp_pos, wp_vel)
     if fk is not None:
         body_q, body_qd = tl["fk_body_q"], tl["fk_body_qd"]
@@ -442,10 +451,20 @@ def _traj_loss_forward(ctx, rollout_inputs, target_position, outseq_idx, self, q
     return out
 
 
-def _traj_loss_backward(ctx, g_loss, g_queried):
+def _traj_loss_backward(ctx, g_loss, g_queried, g_states):
     ws, q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = ctx.saved_tensors[:11]
     bs, nsteps, dt, frame2step = ctx.meta
     tl = ctx.tl
+    adj = {}
+    if ctx.diff_states:
+        gp, gv = g_states
+        if gp is not None or gv is not None:  # the entry wants both or neither: an absent one is zeros
+            n = len(frame2step) * bs * ctx.dm.nb
+            z = lambda k: torch.zeros(n * k, dtype=torch.float32, device=ws.device)
+            adj = dict(adj_pos=z(7) if gp is None else gp.detach().to(torch.float32).contiguous(),
+                       adj_vel=z(6) if gv is None else gv.detach().to(torch.float32).contiguous())
+        if g_loss is None:  # only the states were used
+            g_loss = torch.zeros(1, dtype=torch.float32, device=ws.device)
     gl = g_loss.detach().to(torch.float32).reshape(1).contiguous()
     fk = None
     if g_queried is not None and (g_queried[0] is not None or g_queried[1] is not None):
@@ -455,7 +474,7 @@ def _traj_loss_backward(ctx, g_loss, g_queried):
         aqd = z(ctx.fk_shapes[1]) if g_queried[1] is None else g_queried[1].to(torch.float32).contiguous()
         fk = (jq, jqd, aq, aqd)
     g = ctx.dm.rollout_backward_traj_loss(bs, nsteps, dt, q_init, qd_init, torques, refs, ke, kd, inv_m, inertia, inv_inertia,
-                                          frame2step, ws, tl, gl, fk=fk, **_want_kw(ctx))
+                                          frame2step, ws, tl, gl, fk=fk, **adj, **_want_kw(ctx))
     g_tgt = None
     if ctx.needs_input_grad[11] and tl["seed_gt"] is not None:  # d loss_traj / d target pose = g x share / nb x d se3 / d gt
         # a zero share is an ASSIGNMENT in the reference (loss_seq[i, idx:] = 0, loss_traj[outseq_idx] = 0): nothing flows there, not 0 * inf

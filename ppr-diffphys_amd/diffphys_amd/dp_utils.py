@@ -6,7 +6,7 @@ from .dataloader import bullet2gl  # noqa: F401  (re-exported like the reference
 
 
 class _PoseOpHip(torch.autograd.Function):
-    """One of the three pose compositions below as ONE HIP launch, its vector-Jacobian product as one more (C ABI
+    """One of the pose compositions / projections below as ONE HIP launch, its vector-Jacobian product as one more (C ABI
     ``pd_pose_op`` / ``pd_pose_op_vjp``; the Jacobian is taken inside the kernel by forward-mode differentiation of the
     code that computed the value)."""
 
@@ -149,6 +149,55 @@ def se3_loss(pred, gt, rot_ratio=0.1):
     if pred.shape != gt.shape:
         raise ValueError("se3_loss: pred and gt must have the same shape; got %s and %s" % (tuple(pred.shape), tuple(gt.shape)))
     return _Se3LossHip.apply(pred, gt, rot_ratio)
+
+
+def parse_rtk(rtk):
+    """rtk (..., 4, 4): rows 0-2 [R|t] world -> view, row 3 (fx, fy, cx, cy) -> (rtmat (..., 4, 4), kmat (..., 3, 3))   dp_utils.py:184-197.
+    Plain slicing on any device, as the reference does it."""
+    rtmat = torch.zeros_like(rtk)
+    rtmat[..., :3, :] = rtk[..., :3, :]
+    rtmat[..., -1, -1] = 1
+    kmat = torch.zeros_like(rtk[..., :3, :3])
+    kmat[..., 0, 0] = rtk[..., 3, 0]
+    kmat[..., 1, 1] = rtk[..., 3, 1]
+    kmat[..., 0, 2] = rtk[..., 3, 2]
+    kmat[..., 1, 2] = rtk[..., 3, 3]
+    kmat[..., -1, -1] = 1
+    return rtmat, kmat
+
+
+def _check_cameras(what, bodies, rtk):
+    if not (torch.is_tensor(bodies) and torch.is_tensor(rtk) and bodies.dim() >= 2 and bodies.shape[-1] == 7 and rtk.dim() >= 2
+            and tuple(rtk.shape[-2:]) == (4, 4) and tuple(bodies.shape[:-2]) == tuple(rtk.shape[:-2])):
+        raise ValueError("%s: bodies (..., K, 7) and rtk (..., 4, 4) with equal leading shapes; got %s and %s" % (
+            what, tuple(getattr(bodies, "shape", ())), tuple(getattr(rtk, "shape", ()))))
+
+
+def project_bodies(bodies, rtk):
+    """Body origins (..., K, 7) through the pinhole cameras rtk (..., 4, 4) -> pixels (..., K, 2)   dp_utils.py:200-214.
+    One HIP launch (``pd_pose_op`` PD_POSE_PROJECT; the camera of a leading index serves its K bodies) and one for the gradients of
+    BOTH operands; float32 GPU tensors only.  No clamp: a point in the camera plane gives inf / NaN, as in the reference."""
+    _check_cameras("project_bodies", bodies, rtk)
+    _need_gpu("project_bodies", bodies, rtk)
+    return _PoseOpHip.apply(3, rtk, bodies)
+
+
+def project_points(bodies, rtk, body_index, points):
+    """Body-fixed keypoints: point m = points[m] (M, 3) in the frame of body body_index[m] (M,) of bodies (..., K, 7), through rtk
+    (..., 4, 4) -> pixels (..., M, 2) (``pd_pose_op`` PD_POSE_PROJECT_POINT).  Differentiable in bodies, rtk and points."""
+    _check_cameras("project_points", bodies, rtk)
+    if not (torch.is_tensor(body_index) and torch.is_tensor(points) and body_index.dim() == 1 and tuple(points.shape) == (body_index.numel(), 3)):
+        raise ValueError("project_points: body_index (M,) and points (M, 3); got %s and %s" % (
+            tuple(getattr(body_index, "shape", ())), tuple(getattr(points, "shape", ()))))
+    _need_gpu("project_points", bodies, rtk, points)
+    sel = bodies.index_select(-2, body_index.to(device=bodies.device, dtype=torch.long))
+    return _PoseOpHip.apply(4, rtk, torch.cat([sel, points.expand(sel.shape[:-1] + (3,))], -1))
+
+
+def reproj_loss(sim_2d, target_2d, rtk):
+    """Mean pixel distance of the keypoints of each (env, frame) in units of the focal length: (..., K, 2) x 2, rtk (..., 4, 4) -> (...)
+    -- the 2D term the reference leaves commented out (dp_model.py:781-792)."""
+    return (sim_2d - target_2d).norm(2, -1).mean(-1) / rtk[..., 3, 0]
 
 
 def compute_com(body_q, part_com, part_mass):

@@ -608,12 +608,16 @@ def reduce_loss(table, clip=False, want_scale=True):
     return reduced, scale
 
 
-POSE_COMPOSE_DELTA, POSE_ROTATE_FRAME, POSE_ROTATE_VEL = 0, 1, 2
-_POSE_DIMS = {POSE_COMPOSE_DELTA: (7, 6, 7), POSE_ROTATE_FRAME: (7, 7, 7), POSE_ROTATE_VEL: (7, 6, 6)}
+POSE_COMPOSE_DELTA, POSE_ROTATE_FRAME, POSE_ROTATE_VEL, POSE_PROJECT, POSE_PROJECT_POINT = 0, 1, 2, 3, 4
+_POSE_DIMS = {POSE_COMPOSE_DELTA: (7, 6, 7), POSE_ROTATE_FRAME: (7, 7, 7), POSE_ROTATE_VEL: (7, 6, 6),
+              POSE_PROJECT: (16, 7, 2), POSE_PROJECT_POINT: (16, 10, 2)}
 
 
 def _pose_n(op, a, b):
+    """-> (n, the entry's a_broadcast, floats per output element).  Shapes are checked before any tensor is touched."""
     na, nb_, no = _POSE_DIMS[op]
+    if op in (POSE_PROJECT, POSE_PROJECT_POINT):
+        return _project_n(op, a, b) + (no,)
     if b.shape[-1] != nb_ or a.shape[-1] != na:
         raise ValueError("pose op %d: operands must end in %d and %d floats; got %s and %s" % (op, na, nb_, tuple(a.shape), tuple(b.shape)))
     n = b.numel() // nb_
@@ -623,12 +627,41 @@ def _pose_n(op, a, b):
     return n, bcast, no
 
 
+def _project_n(op, cam, b):
+    """The projection ops: cam (..., 16) or (..., 4, 4), b (..., g..., 7 or 10) whose leading dimensions START with the camera's -> (n, group
+    size g): camera row i // g serves element i (g = 0: a row per element)."""
+    nb_ = _POSE_DIMS[op][1]
+    if cam.dim() >= 2 and tuple(cam.shape[-2:]) == (4, 4):
+        lead = tuple(cam.shape[:-2])
+    elif cam.dim() >= 1 and cam.shape[-1] == 16:
+        lead = tuple(cam.shape[:-1])
+    else:
+        raise ValueError("pose op %d: the camera operand must be (..., 16) or (..., 4, 4); got %s" % (op, tuple(cam.shape)))
+    if b.dim() < 1 or b.shape[-1] != nb_:
+        raise ValueError("pose op %d: the second operand must end in %d floats; got %s" % (op, nb_, tuple(b.shape)))
+    els = tuple(b.shape[:-1])
+    if els[: len(lead)] != lead:
+        raise ValueError("pose op %d: cameras %s do not lead the elements %s (one camera per leading index, shared by what follows)" % (
+            op, lead, els))
+    n, g = 1, 1
+    for d in els:
+        n *= d
+    for d in els[len(lead):]:
+        g *= d
+    return n, (0 if len(els) == len(lead) or n == 0 else g)   # no element: no group to form, whichever dimension is the empty one
+
+
 def pose_op(op, a, b):
     """``pd_pose_op``: compose_delta(a = target (..., 7), b = delta (..., 6)), rotate_frame(a = global (7,) or (..., 7),
-    b = target (..., 7)) or rotate_frame_vel(a = global, b = (..., 6)) in one launch; float32 contiguous GPU tensors."""
+    b = target (..., 7)) or rotate_frame_vel(a = global, b = (..., 6)) in one launch; float32 contiguous GPU tensors.
+    POSE_PROJECT / POSE_PROJECT_POINT: a = cameras (..., 16) or (..., 4, 4), b = poses (..., 7) / poses and body-frame points (..., 10) whose
+    leading dimensions start with the cameras' -> pixels (..., 2); the group size the entry takes is derived from the two shapes."""
     n, bcast, no = _pose_n(op, a, b)
     out = torch.empty(b.shape[:-1] + (no,), device=b.device, dtype=torch.float32)
-    _check_rc("pd_pose_op", lib().pd_pose_op(op, n, _dev(a, "a"), int(bcast), _dev(b, "b"), _dev(out, "out"), _stream()))
+    na = _POSE_DIMS[op][0]
+    if n == 0 and op in (POSE_PROJECT, POSE_PROJECT_POINT):   # cameras without elements (K = 0, M = 0, no frames): nothing to launch
+        return out
+    _check(lib().pd_pose_op(op, n, _ptr(a, "a", None if bcast else n * na), int(bcast), _ptr(b, "b"), _ptr(out, "out"), _stream()))
     return out
 
 
@@ -668,16 +701,24 @@ def linear_wgrad(g, x, want_bias=True):
 
 
 def pose_op_vjp(op, a, b, g_out, need_a=True, need_b=True):
-    """``pd_pose_op_vjp``: (g_a, g_b) for the upstream gradient g_out; g_a is already summed when ``a`` was broadcast."""
+    """``pd_pose_op_vjp``: (g_a, g_b) for the upstream gradient g_out; g_a is already summed when ``a`` was broadcast (ops 0-2) or served a
+    group of elements (the projection ops: summed per camera, as column sums of the rows regrouped [g, cameras * 16] -- a copy and one
+    ``pd_colsum`` launch, fixed order, no torch reduction, so it replays in a captured graph like the rest)."""
     n, bcast, no = _pose_n(op, a, b)
     na = _POSE_DIMS[op][0]
+    if n == 0 and op in (POSE_PROJECT, POSE_PROJECT_POINT):   # cameras that served no element get a zero gradient
+        return (torch.zeros_like(a) if need_a else None), (torch.empty_like(b) if need_b else None)
     g_a = torch.empty(b.shape[:-1] + (na,), device=b.device, dtype=torch.float32) if need_a else None
     g_b = torch.empty_like(b) if need_b else None
-    null = ctypes.c_void_p(0)
-    _check_rc("pd_pose_op_vjp", lib().pd_pose_op_vjp(op, n, _dev(a, "a"), int(bcast), _dev(b, "b"), _dev(g_out, "g_out", n * no),
-                                                     _dev(g_a, "g_a") if need_a else null, _dev(g_b, "g_b") if need_b else null, _stream()))
+    _check(lib().pd_pose_op_vjp(op, n, _ptr(a, "a", None if bcast else n * na), int(bcast), _ptr(b, "b"), _ptr(g_out, "g_out", n * no),
+                                _ptr(g_a, "g_a"), _ptr(g_b, "g_b"), _stream()))
     if need_a:
-        g_a = colsum(g_a.reshape(-1, na)).reshape(a.shape) if bcast else g_a.reshape(a.shape)
+        if op in (POSE_PROJECT, POSE_PROJECT_POINT):
+            if bcast > 1:   # [cameras, g, 16] -> [g, cameras * 16]: each camera's g rows are the rows of its 16 columns (one camera: as is)
+                g_a = colsum(g_a.reshape(-1, bcast, na).transpose(0, 1).reshape(bcast, -1))
+            g_a = g_a.reshape(a.shape)
+        else:
+            g_a = colsum(g_a.reshape(-1, na)).reshape(a.shape) if bcast else g_a.reshape(a.shape)
     return g_a, g_b
 
 

@@ -25,7 +25,8 @@ import torch.nn as nn
 from . import robots, sim
 from .dataloader import mocap_tensors, bullet2gl, parse_amp
 from .dp_model import ForwardKinematics, ForwardWarp, ForwardWarpTrajLossFK, convert_ppr_warp
-from .dp_utils import compose_delta, reduce_loss, reduce_loss_masked, rotate_frame, rotate_frame_vel, se3_loss
+from .dp_utils import (compose_delta, project_bodies, reduce_loss, reduce_loss_masked, reproj_loss, rotate_frame, rotate_frame_vel,
+                       se3_loss)
 from .geom_utils import fid_reindex
 from .grad_guard import GradHistory
 from .time_mlp import TimeMLPWrapper, interp_wt, match_param_name
@@ -175,6 +176,26 @@ class phys_model(nn.Module):
         else:
             self.env = self._make_env(num_envs)  # the trajectory store lives in the autograd ctx, not in per-step States
             setattr(self, env_name, self.env)
+
+    def set_cameras(self, rtk_seq, target_2d_seq=None):
+        """Cameras of the 2D keypoint term (opts["traj_2d_wt"] > 0): rtk_seq [total_frames, 4, 4] -- rows 0-2 [R|t] world -> view, row 3
+        (fx, fy, cx, cy), one per DATA frame (dp_utils.parse_rtk) -- and optionally the observed keypoints target_2d_seq
+        [total_frames, n_links, 2].  forward() gathers both at the data frames of each window, the frames target_position is made at
+        (indices outside the clip take its first / last frame).  Without target_2d_seq the targets are the projections of
+        target_position (detached).  ``set_cameras(None)`` removes them.  A captured iteration read the previous tensors by address: it is
+        dropped, and iteration() captures again."""
+        self._graph = None
+        if rtk_seq is None:
+            self._rtk_seq = self._target_2d_seq = None
+            return
+        rtk_seq = torch.as_tensor(rtk_seq, dtype=torch.float32).to(self.device).contiguous()
+        if rtk_seq.dim() != 3 or tuple(rtk_seq.shape[1:]) != (4, 4) or rtk_seq.shape[0] != self.total_frames:
+            raise ValueError("set_cameras: rtk_seq must be [%d, 4, 4] (one camera per data frame); got %s" % (self.total_frames, tuple(rtk_seq.shape)))
+        if target_2d_seq is not None:
+            target_2d_seq = torch.as_tensor(target_2d_seq, dtype=torch.float32).to(self.device).contiguous()
+            if tuple(target_2d_seq.shape) != (self.total_frames, self.n_links, 2):
+                raise ValueError("set_cameras: target_2d_seq must be [%d, %d, 2]; got %s" % (self.total_frames, self.n_links, tuple(target_2d_seq.shape)))
+        self._rtk_seq, self._target_2d_seq = rtk_seq, target_2d_seq
 
     # -------------------------------------------------------------- optimiser
     def get_lr_dict(self):
@@ -465,6 +486,21 @@ class phys_model(nn.Module):
         qd_init = convert_ppr_warp(qd_init)  # quirk (i): flat vector
         res_fin = None if res_fin is None else convert_ppr_warp(res_fin)
         F_ = self.frames_per_wdw
+        # the 2D keypoint term (off at weight 0: nothing of it is evaluated, differentiable_states stays unset) needs the simulated states
+        # differentiable: the fused Functions below return them so on this opt-in and add their incoming gradients to the adjoint's seeds
+        use_2d = float(self.opts.get("traj_2d_wt", 0.0) or 0.0) > 0
+        if use_2d:
+            if getattr(self, "_rtk_seq", None) is None:
+                raise RuntimeError("traj_2d_wt = %g needs cameras: call set_cameras(rtk_seq) first" % self.opts["traj_2d_wt"])
+            if "_diff_states_before_2d" not in self.__dict__:   # what the user had (a term of their own on the states), to give back
+                self._diff_states_before_2d = self.__dict__.get("differentiable_states")
+            self.differentiable_states = True
+        elif "_diff_states_before_2d" in self.__dict__:   # the weight is back at 0: undo only what forward() itself did
+            before = self.__dict__.pop("_diff_states_before_2d")
+            if before is None:
+                self.__dict__.pop("differentiable_states", None)
+            else:
+                self.differentiable_states = before
         # loss_traj is the ONE term that back-propagates through the rollout (dp_model.py:777-779; the others use sim_position.detach()).
         # fuse_traj_loss (default): the rollout evaluates it where the frame poses are produced and the adjoint seeds itself
         # (dp_model.ForwardWarpTrajLoss, C ABI pd_rollout_*_traj_loss); False: the reference's sequence
@@ -501,6 +537,17 @@ class phys_model(nn.Module):
         loss_dict["pos_state"] = reduce_loss_masked(loss_pos, outseq_idx)
         loss_vel = se3_loss(queried_velocity, sim_velocity.detach()).mean(-1)
         loss_dict["vel_state"] = reduce_loss_masked(loss_vel, outseq_idx)
+        if use_2d:
+            # loss_traj_2d = reduce_loss(|project(sim) - project(target)|.mean(bodies) / focal, outseq entries zeroed), clip=False
+            # (dp_model.py:781-792 of the reference, its unfinished TODO); the one other term that back-propagates through the rollout
+            frames = self._frames_of(steps_fr, 1).round().long().clamp(0, self.total_frames - 1)
+            rtk = self._rtk_seq[frames]  # [n, F, 4, 4]
+            if self._target_2d_seq is not None:
+                target_2d = self._target_2d_seq[frames]
+            else:
+                target_2d = project_bodies(target_position.detach(), rtk)
+            loss_2d = reproj_loss(project_bodies(sim_position, rtk), target_2d, rtk)
+            loss_dict["traj_2d"] = reduce_loss_masked(loss_2d, outseq_idx)
         # (absent controls are all zeros: the mean square is the 0.0 it was)
         zero = lambda: torch.zeros((), dtype=torch.float32, device=ref_ja.device)
         loss_dict["reg_torque"] = zero() if torques is None else _mean_sq(torques)

@@ -44,6 +44,9 @@ def get_opts(argv=None):
     ap.add_argument("--reg_res_f_wt", type=float, default=0.0)
     ap.add_argument("--reg_foot_wt", type=float, default=0.0)
     ap.add_argument("--reg_root_wt", type=float, default=0.0)
+    ap.add_argument("--traj_2d_wt", type=float, default=0.0, help="weight of the 2D keypoint reprojection term (needs --cameras)")
+    ap.add_argument("--cameras", default=None, help=".npz with rtk [frames, 4, 4] (rows 0-2 [R|t], row 3 fx fy cx cy) and optionally "
+                    "target_2d [frames, bodies, 2]: the cameras / observed keypoints of the 2D term (phys_model.set_cameras)")
     ap.add_argument("--num_envs", type=int, default=10, help="envs per training iteration (main.py:86 of the reference)")
     ap.add_argument("--frames_per_wdw", type=int, default=24)
     ap.add_argument("--urdf_root", default=None, help="directory with laikago/laikago.urdf etc. (default: compiled templates)")
@@ -69,10 +72,23 @@ def refuse_unbuilt_flags(opts):
                                   "-- lab4d path, out of scope here; refused rather than silently ignored" % opts["reg_root_wt"])
 
 
+def read_cameras(path):
+    """The --cameras file -> (rtk [frames, 4, 4], target_2d [frames, bodies, 2] or None), the arguments of phys_model.set_cameras
+    (which checks the shapes against the clip)."""
+    import numpy as np
+
+    with np.load(path) as cams:
+        if "rtk" not in cams.files:
+            raise KeyError("--cameras %s: no array 'rtk' (found: %s)" % (path, ", ".join(cams.files) or "nothing"))
+        return cams["rtk"], (cams["target_2d"] if "target_2d" in cams.files else None)
+
+
 def main(argv=None):
     opts = get_opts(argv)
     loader = DataLoader(opts)
     model = phys_model(opts, loader, urdf_root=opts["urdf_root"]).cuda()
+    if opts["cameras"]:
+        model.set_cameras(*read_cameras(opts["cameras"]))
     model.train()
     train(model, opts)
 
