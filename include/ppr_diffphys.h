@@ -338,9 +338,35 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * i / g serves element i (g = bodies per (env, frame); g = n: one camera for all).  n % g != 0 (or g < 0) is refused with
  * a pd_last_error text before anything is launched or written.  The VJP writes g_a [n][16] per element, row 3 included
  * (the caller sums over each group), and g_b [n][7] (quaternion entries 0) or [n][10]; either may be NULL.
+ *
+ * Ground-contact wrench of body states (eval_body_contacts, diffphys/integrator_euler.py:93-179, as a function of ONE state and the
+ * materials; the contact materials' gradients and a differentiable grf are built on it -- DESIGN.md section 8):
+ *   PD_POSE_GROUND_WRENCH  b = body states [n][13] = (p, q xyzw, w, v): a wp_pos row followed by a wp_vel row, the layout of a resumed
+ *                          rollout's state.  a_broadcast = nb (a group size, as above): element i is body i % nb of state set i / nb;
+ *                          nb < 1 or n % nb != 0 is refused before anything is launched.  a = ONE contact table for all elements ->
+ *                          out [n][6] = the element's contribution to body_f, -sum_c (r_c x f_c, f_c) over the body's touching
+ *                          candidates, torque first; zeros for a body without candidates.  Per candidate the arithmetic and the touch
+ *                          decision are the rollout kernels' own (csrc/pd_device.h contact_point_fwd / contact_point_adj on a record
+ *                          staged like theirs); one wavefront per element sums its candidates in a fixed order (no atomics).
+ *                          VJP: g_out [n][6]; g_b [n][13] the raw partials (quaternion entries not projected); g_a [n][nmat][4] the
+ *                          gradient of the material rows (ke, kd, kf, mu) PER ELEMENT (the caller sums); either may be NULL, not both.
+ * The contact table: a 16-byte-aligned float buffer built on the host (hip_backend.contact_table is the one builder), small integers
+ * stored as floats (nc <= 65 535 and nmat <= 255 are exact):
+ *   [0..3]                     nb, nc, nmat, 0
+ *   [4 .. 4 + 4 nmat)          the material rows (ke, kd, kf, mu)
+ *   then 12 floats per body    com.xyz, first candidate, candidate count, bounding sphere of the body's candidates (centre.xyz,
+ *                              radius), largest dist, |centre| + radius, the material index that ALL of the body's candidates
+ *                              share or -1 (mixed: the material VJP then sweeps once per row)  -- the sphere serves an early-out
+ *                              that never drops a touching candidate (bound on the lowest height minus 1 000 roundings of its terms)
+ *   then 4 floats per candidate (x, y, z, dist), grouped by body, in template order inside a body
+ *   then 1 float per candidate its material index, padded with zeros to a multiple of 4 floats
+ * The host cannot validate a device buffer: a table of another model (other nb, nc or nmat than the operands were sized for) is the
+ * caller's error, like a numeric-policy mismatch of the rollouts.
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
- * leaves its reason in pd_last_error. */
-enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4 };
+ * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH is a new op code of the two entries: no symbol or signature changed, the
+ * version stays 9. */
+enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
+       PD_POSE_GROUND_WRENCH = 5 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

@@ -515,6 +515,32 @@ PD_DEV bool contact_point_adj_rest(const ContactPre &C, float4 P, float4 mat, v3
   return true;
 }
 
+// The MATERIAL half of contact_point_adj: the adjoint of the candidate's (ke, kd, kf, mu) for the same (g_t, g_f) -- four products on
+// quantities the state adjoint above forms on its way (contact_point_adj_pre holds them; the height c and fn + fd are formed again from
+// the same operands, so "touching", the Coulomb branch and the clamp are the state adjoint's own).  adj_fnfd is taken AFTER the
+// -mu adj_m branch, as the ke / kd terms of the state adjoint take it.  Used by the ground-wrench op (pd_pose.hip); the rollout
+// adjoints return nothing for the materials.  Returns false (and zeros) when the point is above ground.
+PD_DEV bool contact_point_adj_materials(const float *r, float4 cv, float4 P, float4 mat, v3 g_t, v3 g_f, float4 &adj_mat) {
+  adj_mat = make_float4(0.f, 0.f, 0.f, 0.f);
+  const ContactPre C = contact_point_adj_pre(r, cv, P, mat);
+  if (!C.touch) return false;
+  const float ke = mat.x, kd = mat.y, mu = mat.w;
+  const float c = contact_height(cv, P);
+  const float vn0 = fminf(C.vn, 0.0f);
+  const float fnfd = c * ke + vn0 * kd * C.stepc;
+  v3 adj_t = -g_t, adj_fc = -g_f, adj_r = V3(0, 0, 0);
+  adj_cross(C.rr, C.fc, adj_r, adj_fc, adj_t);
+  const v3 adj_fr = clamp3_pass(C.f_raw, adj_fc, 500.0f);
+  float adj_fnfd = adj_fr.y;
+  const float adj_m = dot(adj_fr, C.nvt);
+  if (!C.a_lt_b) adj_fnfd += -mu * adj_m;
+  adj_mat.x = adj_fnfd * c;
+  adj_mat.y = adj_fnfd * vn0 * C.stepc;
+  adj_mat.z = C.a_lt_b ? adj_m * length(C.vt) : 0.0f;
+  adj_mat.w = C.a_lt_b ? 0.0f : -adj_m * fnfd;
+  return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Joint PD + attachment forces for joint i == child body i (integrator_euler.py:289-451).
 PD_DEV float joint_force(float q, float qd, float target, float ke, float kd, float act, float lo, float up, float lke,

@@ -15,6 +15,7 @@
 // (p, axis-angle); matrices row-major; quaternion_to_matrix divides by |q|^2 (mocap quaternions arrive un-normalised).
 #include <hip/hip_runtime.h>
 #include "../../include/ppr_diffphys.h"
+#include "pd_device.h"  // PD_POSE_GROUND_WRENCH: the rollout kernels' own per-candidate contact code (contact_point_fwd / _adj / _adj_materials)
 
 // pd_host.hip: sets the text pd_last_error() returns, returns 1 (library-internal: hidden, no part of the C ABI)
 __attribute__((visibility("hidden"))) int pd_set_error(const char *msg);
@@ -111,7 +112,7 @@ __device__ __forceinline__ void compose_out7(const T *Ra, const T *pa, const T *
 }
 
 enum { OP_COMPOSE_DELTA = PD_POSE_COMPOSE_DELTA, OP_ROTATE_FRAME = PD_POSE_ROTATE_FRAME, OP_ROTATE_VEL = PD_POSE_ROTATE_VEL,
-       OP_PROJECT = PD_POSE_PROJECT, OP_PROJECT_POINT = PD_POSE_PROJECT_POINT };
+       OP_PROJECT = PD_POSE_PROJECT, OP_PROJECT_POINT = PD_POSE_PROJECT_POINT };  // (PD_POSE_GROUND_WRENCH has kernels of its own, below)
 
 template <int OP> struct Shape;
 template <> struct Shape<OP_COMPOSE_DELTA> { static constexpr int NA = 7, NB = 6, NO = 7; };  // a = target pose, b = delta (p, axis-angle)
@@ -267,6 +268,143 @@ __global__ __launch_bounds__(256) void k_foot_height_vjp(int n, int nb, const fl
   for (int k = 0; k < 7; ++k) g_body_q[(size_t)i * 7 + k] = o[k];
 }
 
+// ---- PD_POSE_GROUND_WRENCH: the ground-contact contribution to body_f, G(state, materials) = -sum_c (r_c x f_c, f_c) over the body's
+// touching candidates (integrator_euler.py:93-179), and its vector-Jacobian products.  The contact wrench of a step is a function of that
+// step's state and of the materials alone (semi-implicit Euler) and enters body_f additively, so this one op, fully parallel over saved
+// states, gives d loss / d materials = sum_t <g_res_f[t], dG/dmaterials> and a differentiable grf = res_f + G without touching a rollout
+// kernel.  Per candidate it runs pd_device.h's contact_point_* on a record and cull vector staged as the forward kernels stage them
+// (stage_record; rc and the cull vector through rotm): the rollout's values and its touch decision, candidate by candidate.
+// Mapping: one wavefront per element (= body of a state set), four per workgroup; lanes stride over the body's candidates, per-lane
+// partial sums, then a fixed-order xor butterfly across the wave.  No atomics, no LDS, no barrier: the same bits on every run.
+// Contact table: include/ppr_diffphys.h (hip_backend.contact_table builds it).
+enum { GW_HEAD = 4, GW_BODY = 12 };
+struct GwTable { int nmat; const float4 *mats, *pts; const float *body, *pmat; };
+__device__ __forceinline__ GwTable gw_table(const float *t) {
+  GwTable T;
+  const int nb = (int)t[0], nc = (int)t[1];
+  T.nmat = (int)t[2];
+  T.mats = (const float4 *)(t + GW_HEAD);
+  T.body = t + GW_HEAD + 4 * T.nmat;
+  T.pts = (const float4 *)(T.body + GW_BODY * nb);
+  T.pmat = (const float *)(T.pts + nc);
+  return T;
+}
+__device__ __forceinline__ float wave_sum(float x) {  // every lane ends with the same sum, formed in the same order
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+  return x;
+}
+// Stages element i: the 17-float record and the cull vector of its state row, the candidate range of its body.  Returns false when no
+// candidate can touch: the body has none, or its bounding sphere (centre, radius, largest dist; in the table) is provably above y = 0 --
+// the lowest height over the sphere, p_y + row1 . centre - |row1| radius - max dist, beyond a slack 1 000 times the rounding of its
+// terms.  A NaN / inf state fails the comparison and is swept.
+__device__ __forceinline__ bool gw_stage(const GwTable &T, int body, const float *x, float *rec, float4 &cv, int &first, int &count, int &umat) {
+  const float *B = T.body + GW_BODY * body;
+  const BodyState s = load_state0(x, 0);
+  float Rm[9];
+  rotm(s.r, Rm);
+  cv = stage_record(rec, &cv, 0, s, mat_vec(Rm, ld3(B)), Rm);
+  first = (int)B[3]; count = (int)B[4]; umat = (int)B[11];  // umat: the one material of all the body's candidates, or -1 (mixed)
+  if (count <= 0) return false;
+  const float len = sqrtf(cv.y * cv.y + cv.z * cv.z + cv.w * cv.w);
+  const float ylow = cv.x + (cv.y * B[5] + cv.z * B[6] + cv.w * B[7]) - 1.001f * len * B[8] - B[9];
+  return !(ylow > 1e-4f * (1.0f + fabsf(cv.x) + len * B[10] + fabsf(B[9])));
+}
+
+__global__ __launch_bounds__(256) void k_ground_wrench_fwd(int n, int nb, const float *__restrict__ tab, const float *__restrict__ state,
+                                                           float *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const GwTable T = gw_table(tab);
+  float rec[PD_REC];
+  float4 cv;
+  int first, count, umat;
+  float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (gw_stage(T, (int)(i % nb), state + (size_t)i * PD_ADJ, rec, cv, first, count, umat)) {
+    for (int k = lane; k < count; k += 64) {
+      const int c = first + k;
+      ContactOut o;
+      if (contact_point_fwd(rec, cv, T.pts[c], T.mats[(int)T.pmat[c]], o)) {  // body_f -= (t, f)   (:179)
+        acc[0] -= o.t.x; acc[1] -= o.t.y; acc[2] -= o.t.z; acc[3] -= o.f.x; acc[4] -= o.f.y; acc[5] -= o.f.z;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[j] = wave_sum(acc[j]);
+  }
+  if (lane < 6) {
+    float v = acc[0];
+#pragma unroll
+    for (int j = 1; j < 6; ++j) v = lane == j ? acc[j] : v;
+    out[(size_t)i * 6 + lane] = v;
+  }
+}
+
+// g_b [n][13]: the raw partials of <g_out, G> with respect to the state row (quaternion entries not projected); g_a [n][nmat][4]: with
+// respect to the material rows, per element.  Either may be NULL.  The two are separate sweeps, so the bits of one do not depend on
+// whether the other was asked for; a body may mix materials: one masked sweep and one reduction per material row (a body of one material,
+// which the table names, sweeps once).
+__global__ __launch_bounds__(256) void k_ground_wrench_vjp(int n, int nb, const float *__restrict__ tab, const float *__restrict__ state,
+                                                           const float *__restrict__ g_out, float *__restrict__ g_a, float *__restrict__ g_b) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const GwTable T = gw_table(tab);
+  float rec[PD_REC];
+  float4 cv;
+  int first, count, umat;
+  const bool sweep = gw_stage(T, (int)(i % nb), state + (size_t)i * PD_ADJ, rec, cv, first, count, umat);
+  const v3 g_t = ld3(g_out + (size_t)i * 6), g_f = ld3(g_out + (size_t)i * 6 + 3);
+  if (g_b) {
+    float acc[PD_ADJ];
+#pragma unroll
+    for (int j = 0; j < PD_ADJ; ++j) acc[j] = 0.f;
+    if (sweep) {
+      for (int k = lane; k < count; k += 64) {
+        const int c = first + k;
+        BodyAdj o;
+        if (contact_point_adj(rec, cv, T.pts[c], T.mats[(int)T.pmat[c]], g_t, g_f, o)) {
+          float t[PD_ADJ];
+          adj_store(t, o);
+#pragma unroll
+          for (int j = 0; j < PD_ADJ; ++j) acc[j] += t[j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < PD_ADJ; ++j) acc[j] = wave_sum(acc[j]);
+    }
+    if (lane < PD_ADJ) {
+      float v = acc[0];
+#pragma unroll
+      for (int j = 1; j < PD_ADJ; ++j) v = lane == j ? acc[j] : v;
+      g_b[(size_t)i * PD_ADJ + lane] = v;
+    }
+  }
+  if (g_a) {
+    float *ga = g_a + (size_t)i * T.nmat * 4;
+    if (!sweep) {
+      for (int j = lane; j < T.nmat * 4; j += 64) ga[j] = 0.f;
+      return;
+    }
+    for (int m = 0; m < T.nmat; ++m) {
+      if (umat >= 0 && m != umat) {  // a body of ONE material (the usual case): the other rows are zero without a sweep
+        if (lane < 4) ga[4 * m + lane] = 0.f;
+        continue;
+      }
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      for (int k = lane; k < count; k += 64) {
+        const int c = first + k;
+        float4 am;
+        if ((int)T.pmat[c] == m && contact_point_adj_materials(rec, cv, T.pts[c], T.mats[m], g_t, g_f, am)) {
+          a0 += am.x; a1 += am.y; a2 += am.z; a3 += am.w;
+        }
+      }
+      a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
+      if (lane < 4) ga[4 * m + lane] = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
+    }
+  }
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -281,8 +419,27 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
   return 2;
 }
 
+// a = the contact table, a_bcast = nb (the group size g: element i is body i % g of state set i / g), b = state rows [n][13]
+int launch_ground_wrench(int n, const float *tab, int nb, const float *state, float *out, const float *g_out, float *g_a, float *g_b,
+                         hipStream_t st) {
+  if (nb <= 0 || n % nb != 0)  // before the n == 0 return, like the projection ops: a bad group size is refused at every n
+    return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
+  if (n == 0) return 0;
+  if (!tab || !state) return pd_set_error("pd_pose_op: a NULL operand");
+  if ((size_t)tab & 15) return pd_set_error("pd_pose_op: the contact table a_dev must be 16-byte aligned");
+  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+  if (out)
+    hipLaunchKernelGGL(k_ground_wrench_fwd, grid, block, 0, st, n, nb, tab, state, out);
+  else
+    hipLaunchKernelGGL(k_ground_wrench_vjp, grid, block, 0, st, n, nb, tab, state, g_out, g_a, g_b);
+  if (hipGetLastError() == hipSuccess) return 0;
+  pd_set_error("pd_pose_op: the kernel launch failed");
+  return 2;
+}
+
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || op > PD_POSE_PROJECT_POINT) return pd_set_error("pd_pose_op: n < 0 or an unknown op");
+  if (n < 0 || op < 0 || op > PD_POSE_GROUND_WRENCH) return pd_set_error("pd_pose_op: n < 0 or an unknown op");
+  if (op == PD_POSE_GROUND_WRENCH) return launch_ground_wrench(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
   const bool project = op >= PD_POSE_PROJECT;
   if (project && (a_bcast < 0 || (a_bcast > 0 && n % a_bcast != 0)))  // before the n == 0 return: a bad group size is refused at every n
     return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the camera group size a_broadcast");

@@ -319,6 +319,91 @@ class ForwardWarp(torch.autograd.Function):
         return _grad_tuple(g, (g["q_init"], g["qd_init"]), torques, res_f, refs, inertia, inv_inertia, ctx.mass_shape, refs.device) + (None,)
 
 
+_MATERIAL_CHUNK_BYTES = 64 << 20  # per-element material gradients of one step chunk of ForwardWarpContact.backward
+
+
+def material_gradient(dm, table, nmat, ws, bs, nsteps, g_res_f):
+    """d loss / d shape_materials [nmat, 4] of a rollout from what its launches left: the saved states (workspace ``ws``) and the adjoint's
+    g_res_f [T, bs*nb, 6], which is the adjoint of body_f.  The contact wrench of step t is a function G of state t and the materials
+    alone and enters body_f additively, so the gradient is sum_t <g_res_f[t], dG(state_t, materials)/dmaterials>: the ground-wrench
+    VJP on the saved states in chunks of steps (temporaries bounded whatever T), each chunk's elements summed by ``colsum`` into a row,
+    the rows by one more ``colsum`` -- fixed order throughout.  Raw: the caller applies the boundary's remove_nan."""
+    N = bs * dm.nb
+    body_q, body_qd, _, _ = dm.saved_trajectory(ws, bs, nsteps)
+    per = max(1, _MATERIAL_CHUNK_BYTES // max(1, N * nmat * 16))
+    rows = []
+    for t0 in range(0, nsteps, per):
+        t1 = min(nsteps, t0 + per)
+        state = torch.cat([body_q[t0:t1], body_qd[t0:t1]], dim=-1).view(-1, 13)
+        _, g_m = hip_backend.ground_wrench_vjp(table, dm.nb, nmat, state, g_res_f[t0:t1].reshape(-1, 6), need_state=False)
+        rows.append(hip_backend.colsum(g_m.view(-1, nmat * 4)))
+    if not rows:
+        return torch.zeros(nmat, 4, dtype=torch.float32, device=ws.device)
+    return (rows[0] if len(rows) == 1 else hip_backend.colsum(torch.stack(rows))).view(nmat, 4)
+
+
+class ForwardWarpContact(torch.autograd.Function):
+    """ForwardWarp with the ground-contact materials as a twelfth, differentiable input (contact system identification):
+
+        wp_pos, wp_vel = ForwardWarpContact.apply(<the 11 inputs of ForwardWarp>, shape_materials [nmat, 4], self)
+
+    shape_materials holds the rows (ke, kd, kf, mu) of ``self.env``'s materials.  Outputs, side outputs on ``self`` and the eleven other
+    gradients are ForwardWarp's.
+    Forward: the rows are read to the host ONCE -- a synchronising copy of 4 nmat floats -- and, when they differ from the env's,
+    ``env.set_shape_materials`` installs them: the device model is then rebuilt (a materials update costs a model build; the C ABI has
+    no entry that re-binds them).  Because of both, the call raises under stream capture.  Then the saving rollout, unchanged.
+    Backward: the adjoint launch with g_res_f asked for (dropped afterwards when res_f itself needs no gradient), then
+    :func:`material_gradient` -- the ground-wrench op's VJP over the saved trajectory, fully parallel over steps -- and the boundary's
+    remove_nan.  No rollout kernel knows about materials.
+    ``self.checkpoint_steps`` set: raises -- the checkpointed adjoint keeps no full trajectory; accumulating per segment is not built."""
+
+    @staticmethod
+    def forward(ctx, q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_mass, body_inv_mass, body_inertia,
+                body_inv_inertia, shape_materials, self):
+        if int(getattr(self, "checkpoint_steps", None) or 0):
+            raise NotImplementedError("ForwardWarpContact: checkpoint_steps is set -- the material gradient needs the whole saved trajectory; "
+                                      "unset it (segment-wise accumulation is not implemented)")
+        if not (torch.is_tensor(shape_materials) and shape_materials.is_cuda):
+            raise TypeError("ForwardWarpContact: shape_materials must be a GPU tensor [nmat, 4]")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ForwardWarpContact cannot be captured: it reads shape_materials to the host and may rebuild the device model")
+        env = self.env
+        M = shape_materials.detach().to(torch.float32).cpu().numpy()  # the one synchronising copy: 4 nmat floats
+        if M.shape != tuple(np.shape(env.t_shape_materials)) or not np.array_equal(M, env.t_shape_materials):
+            env.set_shape_materials(M)
+        dm = hip_backend.device_model(env)
+        bs, nsteps = int(self.num_envs), len(self.steps_idx)
+        frame2step = [int(s) for s in self.frame2step]
+        c = _f32c
+        inp = [c(t) for t in (q_init, qd_init, torques, res_f, refs, target_ke, target_kd, body_inv_mass, body_inertia,
+                              body_inv_inertia)]
+        wp_pos, wp_vel, grf, jaf, ws = dm.rollout_forward(bs, nsteps, self.dt, *inp, frame2step=frame2step, **_save_kw(ctx))
+        ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
+        # the table of THIS call's materials: a later set_shape_materials on the env does not reach a pending backward
+        ctx.table = hip_backend.env_contact_table(env, wp_pos.device) if ctx.needs_input_grad[11] else None
+        ctx.nmat = int(M.shape[0])
+        ctx.save_for_backward(ws, *inp)
+        ctx.mass_shape = body_mass.shape
+        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
+        return wp_pos, wp_vel
+
+    @staticmethod
+    def backward(ctx, adj_body_qs, adj_body_qd):
+        ws, q_init, qd_init, torques, res_f, refs, ke, kd, inv_m, inertia, inv_inertia = ctx.saved_tensors
+        bs, nsteps, dt, frame2step = ctx.meta
+        asked = grads_wanted(ctx.needs_input_grad)
+        need_m = ctx.needs_input_grad[11]
+        want = hip_backend.grad_want(asked + (("res_f",) if need_m else ()))
+        g = ctx.dm.rollout_backward(bs, nsteps, dt, q_init, qd_init, torques, refs, ke, kd, inv_m, inertia, inv_inertia, frame2step, ws,
+                                    adj_body_qs.to(torch.float32).contiguous(), adj_body_qd.to(torch.float32).contiguous(), want=want)
+        g_m = None
+        if need_m:
+            g_m = _remove_nan(material_gradient(ctx.dm, ctx.table, ctx.nmat, ws, bs, nsteps, g["res_f"]))
+            if "res_f" not in asked:
+                g = {k: v for k, v in g.items() if k != "res_f"}
+        return _grad_tuple(g, (g["q_init"], g["qd_init"]), torques, res_f, refs, inertia, inv_inertia, ctx.mass_shape, refs.device) + (g_m, None)
+
+
 class ForwardWarpState(torch.autograd.Function):
     """ForwardWarp started from a BODY state instead of joint coordinates:
 

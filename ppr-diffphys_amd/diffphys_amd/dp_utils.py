@@ -200,6 +200,57 @@ def reproj_loss(sim_2d, target_2d, rtk):
     return (sim_2d - target_2d).norm(2, -1).mean(-1) / rtk[..., 3, 0]
 
 
+class _GroundWrenchHip(torch.autograd.Function):
+    """The ground-contact wrench of body states as ONE HIP launch, its vector-Jacobian product as one more (``pd_pose_op`` /
+    ``pd_pose_op_vjp``, PD_POSE_GROUND_WRENCH), the material gradient summed by ``pd_colsum``."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_qd, materials, env):
+        from . import hip_backend
+
+        nb = int(env.nb)
+        table = hip_backend.env_contact_table(env, body_q.device)
+        nmat = hip_backend._table_dims(table)[2]
+        if materials is not None:
+            table = hip_backend.with_materials(table, nmat, materials)
+        state = torch.cat([body_q.detach().reshape(-1, 7), body_qd.detach().reshape(-1, 6)], dim=1)
+        ctx.table, ctx.nb, ctx.nmat = table, nb, nmat
+        ctx.save_for_backward(state)
+        return hip_backend.ground_wrench(table, nb, state).view(body_q.shape[:-1] + (6,))
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import hip_backend
+
+        (state,) = ctx.saved_tensors
+        need_state = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        g_s, g_m = hip_backend.ground_wrench_vjp(ctx.table, ctx.nb, ctx.nmat, state, g.to(torch.float32).contiguous().view(-1, 6),
+                                                 need_state=need_state, need_materials=ctx.needs_input_grad[2])
+        lead = g.shape[:-1]
+        g_q = g_s[:, :7].reshape(lead + (7,)) if ctx.needs_input_grad[0] else None
+        g_qd = g_s[:, 7:].reshape(lead + (6,)) if ctx.needs_input_grad[1] else None
+        if g_m is not None:
+            g_m = hip_backend.colsum(g_m.view(-1, ctx.nmat * 4)).view(ctx.nmat, 4)
+        return g_q, g_qd, g_m, None
+
+
+def ground_wrench(body_q, body_qd, env, materials=None):
+    """Each body's ground-contact contribution to body_f (eval_body_contacts, integrator_euler.py:93-179 of the reference, as a function of
+    the state): body_q (..., nb, 7) poses (p, q xyzw) and body_qd (..., nb, 6) twists in Warp order (w, v) -- wp_pos / wp_vel rows
+    reshaped to (..., nb, .) -- -> (..., nb, 6) wrenches (torque, force), zeros for a body that touches nothing.  One HIP launch with the
+    rollout kernels' own per-candidate arithmetic; differentiable in body_q, body_qd (raw partials; the quaternion entries are not
+    projected) and in ``materials`` [nmat, 4] = (ke, kd, kf, mu) rows, a float32 GPU tensor that stands in for the env's rows.
+    materials=None: the env's materials, no material gradient.  The differentiable ground-reaction force of a rollout frame is
+    ``res_f[frame2step[f]] + ground_wrench(wp_pos[f], wp_vel[f], env)``.  float32 GPU tensors only."""
+    _need_gpu("ground_wrench", body_q, body_qd, *(() if materials is None else (materials,)))
+    nb = int(env.nb)
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
+            and body_q.shape[:-2] == body_qd.shape[:-2]):
+        raise ValueError("ground_wrench: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
+            nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+    return _GroundWrenchHip.apply(body_q, body_qd, materials, env)
+
+
 def compute_com(body_q, part_com, part_mass):
     """mass-weighted COM of one articulation (numpy)   dp_utils.py:86-90"""
     from scipy.spatial.transform import Rotation as R
