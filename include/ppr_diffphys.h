@@ -362,11 +362,41 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  *   then 1 float per candidate its material index, padded with zeros to a multiple of 4 floats
  * The host cannot validate a device buffer: a table of another model (other nb, nc or nmat than the operands were sized for) is the
  * caller's error, like a numeric-policy mismatch of the rollouts.
+ *
+ * Joint coordinates of body states -- the inverse of pd_fk_forward (Warp's eval_ik; the numbers the joint pass of a step measures,
+ * diffphys/integrator_euler.py:326-445, as outputs -- DESIGN.md section 8):
+ *   PD_POSE_JOINT_COORDS   b = body states [n][13] and a_broadcast = nb as for PD_POSE_GROUND_WRENCH (nb < 1 or n % nb != 0 is refused at
+ *                          every n; nb <= 256).  a = ONE joint table for all elements -> out [n / nb][nq + nqd], set-major: joint_q [nq]
+ *                          then joint_qd [nqd] of each state set, the layouts pd_fk_forward takes.  With the joint frame X_wj = X_parent
+ *                          X_p (X_p alone and w_p = v_p = 0 for a body without parent), r_err = conj(q_wj) q_c, w_err = w_c - w_p:
+ *                            FREE      q = (R_wj^-1 (p_c - p_wj), r_err),  qd = (R_wj^-1 w_err, R_wj^-1 (v_c - v_p - w_err x com))
+ *                            REVOLUTE  q = the twist angle of r_err about the axis (integrator_euler.py:394-400, through atan2: the
+ *                                      default numeric policy; the literal-acos policy is not offered for this op),
+ *                                      qd = w_err . R_wj axis
+ *                            COMPOUND  q = quat_decompose(conj(q_off) r_err q_off) (:411-416); the measured rates m_k = (R_wj R_off a_k)
+ *                                      . w_err on the axes a_k of :418-427; rate mode 0 ("measured", what the PD controller sees):
+ *                                      qd = m; rate mode 1 ("generalized", the inverse of pd_fk_forward): qd = G^-1 m, G_kj = a_k . a_j
+ *                                      (only a_0 . a_2 is off the diagonal; singular at |q_1| = pi / 2)
+ *                            FIXED     no coordinates
+ *                          One lane per element; every output float is written by exactly one lane (floats of out that belong to no
+ *                          joint do not exist: nq and nqd are the sums of the joints' widths).
+ *                          VJP: g_out [n / nb][nq + nqd] -> g_b [n][13], the raw partials (quaternion entries not projected).  A body's
+ *                          coordinates depend on its own row and on its parent's: whole state sets share a workgroup, every lane leaves
+ *                          the parent-side adjoint of its joint in LDS and, after one barrier, adds its children's in the table's child
+ *                          order to its own -- no atomics, the same bits on every run.  The table has no gradient: a non-NULL g_a is
+ *                          refused.
+ * The joint table: a 16-byte-aligned float buffer built on the host (hip_backend.joint_table is the one builder), integers stored as
+ * floats:
+ *   [0..3]                     nb, nq, nqd, rate mode (0 measured, 1 generalized)
+ *   then 24 floats per body    parent (-1: none), joint type, q_start, qd_start, X_p (p.xyz, q.xyzw), axis.xyz, the quaternion of X_c
+ *                              (xyzw), com.xyz, number of children, 0, 0
+ *   then 8 floats per body     its children in template order, -1 padded (a body with more than 8 children is refused by the builder)
+ * As with the contact table, a table of another model is the caller's error.
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
- * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH is a new op code of the two entries: no symbol or signature changed, the
- * version stays 9. */
+ * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH and PD_POSE_JOINT_COORDS are new op codes of the two entries: no symbol or
+ * signature changed, the version stays 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
-       PD_POSE_GROUND_WRENCH = 5 };
+       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

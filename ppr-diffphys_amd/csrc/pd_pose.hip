@@ -15,7 +15,8 @@
 // (p, axis-angle); matrices row-major; quaternion_to_matrix divides by |q|^2 (mocap quaternions arrive un-normalised).
 #include <hip/hip_runtime.h>
 #include "../../include/ppr_diffphys.h"
-#include "pd_device.h"  // PD_POSE_GROUND_WRENCH: the rollout kernels' own per-candidate contact code (contact_point_fwd / _adj / _adj_materials)
+#include "pd_device.h"  // PD_POSE_GROUND_WRENCH: the rollout kernels' own per-candidate contact code (contact_point_fwd / _adj / _adj_materials);
+                        // PD_POSE_JOINT_COORDS: twist_angle, quat_decompose_cols / _adj and the quaternion adjoints
 
 // pd_host.hip: sets the text pd_last_error() returns, returns 1 (library-internal: hidden, no part of the C ABI)
 __attribute__((visibility("hidden"))) int pd_set_error(const char *msg);
@@ -112,7 +113,7 @@ __device__ __forceinline__ void compose_out7(const T *Ra, const T *pa, const T *
 }
 
 enum { OP_COMPOSE_DELTA = PD_POSE_COMPOSE_DELTA, OP_ROTATE_FRAME = PD_POSE_ROTATE_FRAME, OP_ROTATE_VEL = PD_POSE_ROTATE_VEL,
-       OP_PROJECT = PD_POSE_PROJECT, OP_PROJECT_POINT = PD_POSE_PROJECT_POINT };  // (PD_POSE_GROUND_WRENCH has kernels of its own, below)
+       OP_PROJECT = PD_POSE_PROJECT, OP_PROJECT_POINT = PD_POSE_PROJECT_POINT };  // (PD_POSE_GROUND_WRENCH and PD_POSE_JOINT_COORDS have kernels of their own, below)
 
 template <int OP> struct Shape;
 template <> struct Shape<OP_COMPOSE_DELTA> { static constexpr int NA = 7, NB = 6, NO = 7; };  // a = target pose, b = delta (p, axis-angle)
@@ -405,6 +406,200 @@ __global__ __launch_bounds__(256) void k_ground_wrench_vjp(int n, int nb, const 
   }
 }
 
+// ---- PD_POSE_JOINT_COORDS: joint coordinates (joint_q, joint_qd) of body states, the inverse of k_fk (Warp's eval_ik), and its
+// vector-Jacobian product.  For body i with parent par the joint frame is X_wj = X_par X_p[i] (X_p[i] alone, w_p = v_p = 0, without a
+// parent); r_err = conj(q_wj) q_c and w_err = w_c - w_p are the joint pass's (joint_ctx, pd_device.h; integrator_euler.py:326-372).
+//   FREE      q = (R_wj^-1 (p_c - p_wj), r_err), qd = (R_wj^-1 w_err, R_wj^-1 (v_c - v_p - w_err x com)): fk_joint solved for its inputs
+//   REVOLUTE  q = twist_angle (pd_math.h: :394-400 through atan2), qd = w_err . R_wj axis   -- what joint_fwd measures
+//   COMPOUND  q = quat_decompose(conj(q_off) r_err q_off); measured rates m_k = (R_wj R_off a_k) . w_err on the axis chain of :418-427 --
+//             what joint_fwd measures.  Rate mode 0 (measured): qd = m.  The a_k are not orthogonal (a_0 . a_1 = a_1 . a_2 = 0,
+//             a_0 . a_2 = s = a_2.x), so m is not the generalised velocity of fk_joint_local's w_jc = sum a_k qd_k; rate mode 1
+//             (generalized) solves the Gram system: qd_1 = m_1, (qd_0, qd_2) = ((m_0 - s m_2), (m_2 - s m_0)) / (1 - s^2) -- singular at
+//             |q_1| = pi / 2 (gimbal lock), where the result is inf / NaN like any division by zero here.
+//   FIXED     no coordinates
+// Default numeric policy only: this translation unit is compiled once, with PD_POLICY 0; the literal-acos policy is not offered.
+// Forward: one lane per element (= body of a state set); it reads its own row and its parent's, nothing is chained.
+// VJP: a body's coordinates depend on its own row and on its parent's, so a parent receives up to JC_MAXCH contributions.  Whole state
+// sets share a workgroup (256 / nb sets of nb lanes); every lane leaves the parent-side adjoint of its joint in an LDS slot and, after ONE
+// barrier, adds its children's slots to its own-side adjoint in the table's child order (a parent gathers its
+// children's in fixed order).  No atomics: the same bits on every run.  Joint table: include/ppr_diffphys.h (hip_backend.joint_table).
+enum { JC_HEAD = 4, JC_BODY = 24, JC_MAXCH = 8, JC_MAXNB = 256 };
+struct JcJoint {  // what the forward pass and the adjoint share
+  int type, parent, qs, qds;
+  v3 p_pj, axis, com;
+  qt q_pj, q_off;
+  v3 pp, w_p, v_p, p_wj, w_err;
+  qt qp, q_wj, r_err;
+};
+// A table the call was not sized for must not send a lane out of bounds (the host cannot validate a device buffer): a parent index
+// outside the set reads no row, and a joint whose coordinates do not lie inside [0, nq) x [0, nqd) -- or any joint of a table built for
+// another nb -- is taken as FIXED: nothing of it is read or written.
+__device__ __forceinline__ JcJoint jc_joint(const float *tab, int nb, int nq, int nqd, int body, const BodyState &s, const float *set_rows) {
+  JcJoint J;
+  J.pp = V3(0, 0, 0); J.w_p = J.pp; J.v_p = J.pp; J.qp = Q4(0, 0, 0, 1);
+  if ((int)tab[0] != nb) {  // not this call's table: no row of it is read
+    J.parent = -1; J.type = PD_JOINT_FIXED; J.qs = J.qds = 0;
+    J.p_pj = J.pp; J.axis = J.pp; J.com = J.pp; J.q_pj = J.qp; J.q_off = J.qp;
+    J.p_wj = J.pp; J.q_wj = J.qp; J.r_err = s.r; J.w_err = s.w;
+    return J;
+  }
+  const float *B = tab + JC_HEAD + JC_BODY * body;
+  J.parent = (int)B[0]; J.type = (int)B[1]; J.qs = (int)B[2]; J.qds = (int)B[3];
+  J.p_pj = ld3(B + 4); J.q_pj = ld4(B + 7); J.axis = ld3(B + 11); J.q_off = ld4(B + 14); J.com = ld3(B + 18);
+  J.p_wj = J.p_pj; J.q_wj = J.q_pj;
+  const int wq = J.type == PD_JOINT_FREE ? 7 : J.type == PD_JOINT_COMPOUND ? 3 : 1, wqd = wq == 7 ? 6 : wq;
+  if (J.qs < 0 || J.qs + wq > nq || J.qds < 0 || J.qds + wqd > nqd) J.type = PD_JOINT_FIXED;
+  if (J.parent >= nb) J.parent = -1;
+  if (J.parent >= 0) {
+    const BodyState P = load_state0(set_rows, (size_t)J.parent);
+    J.pp = P.p; J.qp = P.r; J.w_p = P.w; J.v_p = P.v;
+    J.p_wj = P.p + qrot(P.r, J.p_pj);
+    J.q_wj = qmul(P.r, J.q_pj);
+  }
+  J.r_err = qmul(qconj(J.q_wj), s.r);
+  J.w_err = s.w - J.w_p;
+  return J;
+}
+struct JcCompound {  // the compound joint's forward pass, kept for its adjoint
+  qt qa, q_pc, q_0, q_1, q10, q_w;
+  v3 c0, c1, c2, a1, a2, u;
+  float ang[3], m[3], qd[3], s, id;
+};
+__device__ __forceinline__ void jc_compound(const JcJoint &J, bool generalized, JcCompound &C) {
+  C.qa = qmul(qconj(J.q_off), J.r_err);
+  C.q_pc = qmul(C.qa, J.q_off);
+  quat_decompose_cols(C.q_pc, C.ang, C.c0, C.c1, C.c2);
+  C.q_0 = q_axis_angle(V3(1, 0, 0), C.ang[0]);  // the axis chain of integrator_euler.py:418-427
+  C.a1 = qrot(C.q_0, V3(0, 1, 0));
+  C.q_1 = q_axis_angle(C.a1, C.ang[1]);
+  C.q10 = qmul(C.q_1, C.q_0);
+  C.a2 = qrot(C.q10, V3(0, 0, 1));
+  C.q_w = qmul(J.q_wj, J.q_off);
+  C.u = qrot_inv(C.q_w, J.w_err);  // (R a) . w = a . (R^T w) for the linear map of ANY quaternion (pd_math.h rotm): m_k = a_k . u
+  C.m[0] = C.u.x; C.m[1] = dot(C.a1, C.u); C.m[2] = dot(C.a2, C.u);
+  C.s = C.a2.x; C.id = 1.0f;
+  C.qd[0] = C.m[0]; C.qd[1] = C.m[1]; C.qd[2] = C.m[2];
+  if (generalized) {
+    C.id = 1.0f / (1.0f - C.s * C.s);
+    C.qd[0] = (C.m[0] - C.s * C.m[2]) * C.id;
+    C.qd[2] = (C.m[2] - C.s * C.m[0]) * C.id;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_joint_coords_fwd(int n, int nb, const float *__restrict__ tab, const float *__restrict__ state,
+                                                          float *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int set = (int)(i / nb), body = (int)(i - (long long)set * nb);
+  const int nq = (int)tab[1], nqd = (int)tab[2];
+  const bool generalized = tab[3] != 0.0f;
+  const float *rows = state + (size_t)set * nb * PD_ADJ;
+  const BodyState s = load_state0(rows, (size_t)body);
+  const JcJoint J = jc_joint(tab, nb, nq, nqd, body, s, rows);
+  float *q = out + (size_t)set * (nq + nqd) + J.qs, *qd = out + (size_t)set * (nq + nqd) + nq + J.qds;
+  if (J.type == PD_JOINT_FREE) {
+    const v3 x = qrot_inv(J.q_wj, s.p - J.p_wj), wl = qrot_inv(J.q_wj, J.w_err);
+    const v3 vl = qrot_inv(J.q_wj, (s.v - J.v_p) - cross(J.w_err, J.com));
+    q[0] = x.x; q[1] = x.y; q[2] = x.z; q[3] = J.r_err.x; q[4] = J.r_err.y; q[5] = J.r_err.z; q[6] = J.r_err.w;
+    qd[0] = wl.x; qd[1] = wl.y; qd[2] = wl.z; qd[3] = vl.x; qd[4] = vl.y; qd[5] = vl.z;
+  } else if (J.type == PD_JOINT_REVOLUTE) {
+    q[0] = twist_angle(dot(qvec(J.r_err), J.axis), J.r_err.w, length(J.axis));
+    qd[0] = dot(J.w_err, qrot(J.q_wj, J.axis));
+  } else if (J.type == PD_JOINT_COMPOUND) {
+    JcCompound C;
+    jc_compound(J, generalized, C);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { q[k] = C.ang[k]; qd[k] = C.qd[k]; }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_joint_coords_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ state,
+                                                          const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float slot[256 * PD_ADJ];  // lane -> the parent-side adjoint of its joint (odd stride: distinct banks)
+  const int per_wg = 256 / nb;           // whole state sets per workgroup
+  const int set_l = (int)threadIdx.x / nb, body = (int)threadIdx.x - set_l * nb;
+  const long long set = (long long)blockIdx.x * per_wg + set_l;
+  const bool active = set_l < per_wg && set < nsets;
+  const int nq = (int)tab[1], nqd = (int)tab[2];
+  const bool generalized = tab[3] != 0.0f;
+  BodyAdj own = adj_zero(), par = adj_zero();
+  if (active) {
+    const float *rows = state + (size_t)set * nb * PD_ADJ;
+    const BodyState s = load_state0(rows, (size_t)body);
+    const JcJoint J = jc_joint(tab, nb, nq, nqd, body, s, rows);
+    const float *gq = g_out + (size_t)set * (nq + nqd) + J.qs, *gqd = g_out + (size_t)set * (nq + nqd) + nq + J.qds;
+    qt adj_r_err = Q4(0, 0, 0, 0), adj_q_wj = adj_r_err;
+    v3 adj_w_err = V3(0, 0, 0), adj_p_wj = adj_w_err;
+    if (J.type == PD_JOINT_FREE) {
+      v3 adj_d = V3(0, 0, 0), adj_l = adj_d;
+      adj_qrot_inv(J.q_wj, s.p - J.p_wj, adj_q_wj, adj_d, ld3(gq));
+      own.p += adj_d; adj_p_wj -= adj_d;
+      adj_r_err += ld4(gq + 3);
+      adj_qrot_inv(J.q_wj, J.w_err, adj_q_wj, adj_w_err, ld3(gqd));
+      adj_qrot_inv(J.q_wj, (s.v - J.v_p) - cross(J.w_err, J.com), adj_q_wj, adj_l, ld3(gqd + 3));
+      own.v += adj_l; par.v -= adj_l;
+      adj_cross_a(J.com, adj_w_err, -adj_l);
+    } else if (J.type == PD_JOINT_REVOLUTE) {
+      float dq_dda, dq_dw;
+      (void)twist_angle(dot(qvec(J.r_err), J.axis), J.r_err.w, length(J.axis), dq_dda, dq_dw);
+      const float adj_da = gq[0] * dq_dda;
+      adj_r_err.x += J.axis.x * adj_da; adj_r_err.y += J.axis.y * adj_da; adj_r_err.z += J.axis.z * adj_da;
+      adj_r_err.w += gq[0] * dq_dw;
+      adj_w_err += qrot(J.q_wj, J.axis) * gqd[0];
+      adj_qrot_q(J.q_wj, J.axis, adj_q_wj, J.w_err * gqd[0]);
+    } else if (J.type == PD_JOINT_COMPOUND) {
+      JcCompound C;
+      jc_compound(J, generalized, C);
+      float gm[3] = {gqd[0], gqd[1], gqd[2]}, g_s = 0.0f;
+      if (generalized) {  // qd_0 = (m_0 - s m_2) id, qd_2 = (m_2 - s m_0) id, id = 1 / (1 - s^2)
+        g_s = (gqd[0] * (2.0f * C.s * C.qd[0] - C.m[2]) + gqd[2] * (2.0f * C.s * C.qd[2] - C.m[0])) * C.id;
+        gm[0] = (gqd[0] - C.s * gqd[2]) * C.id;
+        gm[2] = (gqd[2] - C.s * gqd[0]) * C.id;
+      }
+      const v3 adj_u = V3(gm[0], 0, 0) + C.a1 * gm[1] + C.a2 * gm[2];
+      v3 adj_a1 = C.u * gm[1], adj_a2 = C.u * gm[2];
+      adj_a2.x += g_s;
+      qt adj_q_w = Q4(0, 0, 0, 0);
+      adj_qrot_inv(C.q_w, J.w_err, adj_q_w, adj_w_err, adj_u);
+      adj_qmul_a(J.q_off, adj_q_wj, adj_q_w);
+      float adj_ang[3] = {gq[0], gq[1], gq[2]};
+      qt adj_q10 = Q4(0, 0, 0, 0), adj_q_1 = adj_q10, adj_q_0 = adj_q10;
+      adj_qrot_q(C.q10, V3(0, 0, 1), adj_q10, adj_a2);
+      adj_qmul(C.q_1, C.q_0, adj_q_1, adj_q_0, adj_q10);
+      adj_q_axis_angle(C.a1, C.ang[1], adj_a1, adj_ang[1], adj_q_1);
+      adj_qrot_q(C.q_0, V3(0, 1, 0), adj_q_0, adj_a1);
+      adj_q_axis_angle_ang(V3(1, 0, 0), C.ang[0], adj_ang[0], adj_q_0);
+      qt adj_q_pc = Q4(0, 0, 0, 0), adj_qa = adj_q_pc;
+      quat_decompose_adj(C.q_pc, C.c0, C.c1, C.c2, adj_ang, adj_q_pc);
+      adj_qmul_a(J.q_off, adj_qa, adj_q_pc);
+      adj_qmul_b(qconj(J.q_off), adj_r_err, adj_qa);
+    }
+    own.w += adj_w_err; par.w -= adj_w_err;
+    qt adj_cq = Q4(0, 0, 0, 0);
+    adj_qmul(qconj(J.q_wj), s.r, adj_cq, own.r, adj_r_err);
+    adj_q_wj += qconj(adj_cq);
+    if (J.parent >= 0) {
+      adj_qmul_a(J.q_pj, par.r, adj_q_wj);
+      par.p += adj_p_wj;
+      adj_qrot_q(J.qp, J.p_pj, par.r, adj_p_wj);
+    }
+  }
+  adj_store(slot + threadIdx.x * PD_ADJ, par);
+  __syncthreads();
+  if (!active) return;
+  const float *B = tab + JC_HEAD + JC_BODY * body, *ch = tab + JC_HEAD + JC_BODY * nb + JC_MAXCH * body;
+  const int nch = (int)tab[0] == nb ? min((int)B[21], (int)JC_MAXCH) : 0;
+  for (int k = 0; k < nch; ++k) {
+    const int c = (int)ch[k];
+    if (c >= 0 && c < nb) adj_add_from(own, slot + (set_l * nb + c) * PD_ADJ);
+  }
+  float o[PD_ADJ];
+  adj_store(o, own);
+  float *dst = g_b + ((size_t)set * nb + body) * PD_ADJ;
+#pragma unroll
+  for (int k = 0; k < PD_ADJ; ++k) dst[k] = o[k];
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -437,9 +632,31 @@ int launch_ground_wrench(int n, const float *tab, int nb, const float *state, fl
   return 2;
 }
 
+// a = the joint table, a_bcast = nb (the group size, as for the ground wrench), b = state rows [n][13]; out / g_out [n / nb][nq + nqd]
+int launch_joint_coords(int n, const float *tab, int nb, const float *state, float *out, const float *g_out, float *g_a, float *g_b,
+                        hipStream_t st) {
+  if (nb <= 0 || n % nb != 0)  // before the n == 0 return: a bad group size is refused at every n
+    return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
+  if (nb > JC_MAXNB) return pd_set_error("pd_pose_op: PD_POSE_JOINT_COORDS serves at most 256 bodies per state set");
+  if (g_a) return pd_set_error("pd_pose_op_vjp: PD_POSE_JOINT_COORDS has no gradient for its joint table -- g_a_dev must be NULL");
+  if (n == 0) return 0;
+  if (!tab || !state) return pd_set_error("pd_pose_op: a NULL operand");
+  if ((size_t)tab & 15) return pd_set_error("pd_pose_op: the joint table a_dev must be 16-byte aligned");
+  if (out) {
+    hipLaunchKernelGGL(k_joint_coords_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, nb, tab, state, out);
+  } else {
+    const int nsets = n / nb, per_wg = 256 / nb;
+    hipLaunchKernelGGL(k_joint_coords_vjp, dim3((unsigned)((nsets + per_wg - 1) / per_wg)), dim3(256), 0, st, nsets, nb, tab, state, g_out, g_b);
+  }
+  if (hipGetLastError() == hipSuccess) return 0;
+  pd_set_error("pd_pose_op: the kernel launch failed");
+  return 2;
+}
+
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || op > PD_POSE_GROUND_WRENCH) return pd_set_error("pd_pose_op: n < 0 or an unknown op");
+  if (n < 0 || op < 0 || op > PD_POSE_JOINT_COORDS) return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   if (op == PD_POSE_GROUND_WRENCH) return launch_ground_wrench(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
+  if (op == PD_POSE_JOINT_COORDS) return launch_joint_coords(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
   const bool project = op >= PD_POSE_PROJECT;
   if (project && (a_bcast < 0 || (a_bcast > 0 && n % a_bcast != 0)))  // before the n == 0 return: a bad group size is refused at every n
     return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the camera group size a_broadcast");

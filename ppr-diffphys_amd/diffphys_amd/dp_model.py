@@ -104,6 +104,45 @@ class ForwardKinematics(torch.autograd.Function):
         return post(gq, dm.nq), post(gqd, dm.nqd), None
 
 
+class InverseKinematics(torch.autograd.Function):
+    """body_q [bs,T,nb,7], body_qd [bs,T,nb,6], env, rates -> rj_q [T,bs,nq], rj_qd [T,bs,nqd]: the joint coordinates of body states, the
+    inverse of :class:`ForwardKinematics` in its own shapes (Warp's eval_ik; ``pd_pose_op`` PD_POSE_JOINT_COORDS, one launch forward and
+    one for the vector-Jacobian product).  body_qd is in Warp order (w, v), as ForwardKinematics returns it and wp_vel holds it.
+    rates="generalized": joint_qd are the generalised velocities (``ForwardKinematics.apply(*InverseKinematics.apply(bq, bqd, env),
+    env)[:2]`` gives (bq, bqd) back, up to the gimbal lock of a compound joint at |second angle| = pi / 2); rates="measured": the
+    rates the PD controller of a step sees (they differ for COMPOUND joints only).  float32 GPU tensors, or an error: no CPU
+    fallback.  The gradients are the raw partials (quaternion entries not projected), nothing is scrubbed."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_qd, env, rates="generalized"):
+        nb = int(env.nb)
+        for t in (body_q, body_qd):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+                raise TypeError("InverseKinematics needs float32 GPU tensors (the product path has no CPU fallback); got %s" % (
+                    "%s on %s" % (t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+        if not (body_q.dim() == 4 and tuple(body_q.shape[2:]) == (nb, 7) and body_qd.dim() == 4 and tuple(body_qd.shape[2:]) == (nb, 6)
+                and body_q.shape[:2] == body_qd.shape[:2]):
+            raise ValueError("InverseKinematics: body_q [bs, T, %d, 7] and body_qd [bs, T, %d, 6]; got %s and %s" % (
+                nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+        table = hip_backend.env_joint_table(env, body_q.device, rates)
+        bs, T = int(body_q.shape[0]), int(body_q.shape[1])
+        state = torch.cat([body_q.detach().permute(1, 0, 2, 3).reshape(-1, 7), body_qd.detach().permute(1, 0, 2, 3).reshape(-1, 6)], dim=1)
+        ctx.table, ctx.nb, ctx.shape = table, nb, (bs, T)
+        ctx.save_for_backward(state)
+        q, qd = hip_backend.joint_coords(table, nb, state)
+        return q.reshape(T, bs, -1), qd.reshape(T, bs, -1)
+
+    @staticmethod
+    def backward(ctx, g_q, g_qd):
+        (state,) = ctx.saved_tensors
+        bs, T = ctx.shape
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        flat = lambda g: g.to(torch.float32).reshape(T * bs, -1).contiguous()
+        g_s = hip_backend.joint_coords_vjp(ctx.table, ctx.nb, state, flat(g_q), flat(g_qd)).view(T, bs, ctx.nb, 13).permute(1, 0, 2, 3)
+        return (g_s[..., :7] if ctx.needs_input_grad[0] else None), (g_s[..., 7:] if ctx.needs_input_grad[1] else None), None, None
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).
@@ -175,13 +214,15 @@ def _view(g, name, like):
     return g[name].view_as(like) if name in g else None
 
 
-def _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf):
+def _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf, wp_vel=None):
     """The side outputs on ``self`` that phys_model.query() consumes (dp_model.py:855-860).  A frame at state `nsteps` has no force
-    snapshot in the reference (:1225-1228 append for step in steps_idx only): keep its list lengths."""
+    snapshot in the reference (:1225-1228 append for step in steps_idx only): keep its list lengths.  ``sim_vels``: env 0's frame twists
+    beside ``sim_trajs`` (query(joint_coords=True) needs both halves of the state)."""
     has_f = [f for f, s in enumerate(frame2step) if s < nsteps]
     self.grfs = [grf[f] for f in has_f]
     self.jafs = [jaf[f] for f in has_f]
     self.sim_trajs = HostFrames(wp_pos[:, : dm.nb])
+    self.sim_vels = None if wp_vel is None else HostFrames(wp_vel[:, : dm.nb])
 
 
 def _grad_tuple(g, init, torques, res_f, refs, inertia, inv_inertia, mass_shape, device):
@@ -298,7 +339,7 @@ class ForwardWarp(torch.autograd.Function):
         ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
         ctx.save_for_backward(ws, *inp)
         ctx.mass_shape = body_mass.shape
-        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
+        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf, wp_vel)
         return wp_pos, wp_vel
 
     @staticmethod
@@ -384,7 +425,7 @@ class ForwardWarpContact(torch.autograd.Function):
         ctx.nmat = int(M.shape[0])
         ctx.save_for_backward(ws, *inp)
         ctx.mass_shape = body_mass.shape
-        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
+        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf, wp_vel)
         return wp_pos, wp_vel
 
     @staticmethod
@@ -430,7 +471,7 @@ class ForwardWarpState(torch.autograd.Function):
         ctx.dm, ctx.meta = dm, (bs, nsteps, float(self.dt), frame2step)
         ctx.save_for_backward(ws, state0, *inp)
         ctx.mass_shape, ctx.q0_shape, ctx.qd0_shape = body_mass.shape, body_q0.shape, body_qd0.shape
-        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
+        _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf, wp_vel)
         return wp_pos, wp_vel
 
     @staticmethod
@@ -520,7 +561,7 @@ def _traj_loss_forward(ctx, rollout_inputs, target_position, outseq_idx, self, q
     ctx.fk_shapes = None if fk is None else (tuple(tl["fk_body_q"].shape), tuple(tl["fk_body_qd"].shape))
     ctx.save_for_backward(ws, *inp, *(fk or ()))
     ctx.mass_shape, ctx.tgt_shape = body_mass.shape, target_position.shape
-    _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf)
+    _publish(self, dm, frame2step, nsteps, wp_pos, grf, jaf, wp_vel)
     self.traj_loss_info = tl["reduced"]
     # self.differentiable_states (absent / False: the states come back detached, as they always did): wp_pos / wp_vel are differentiable
     # outputs and their incoming gradients join the adjoint's own seeds (_traj_loss_backward).  Gradients nobody sent stay None then.

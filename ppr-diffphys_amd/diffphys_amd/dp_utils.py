@@ -251,6 +251,26 @@ def ground_wrench(body_q, body_qd, env, materials=None):
     return _GroundWrenchHip.apply(body_q, body_qd, materials, env)
 
 
+def joint_coords(body_q, body_qd, env, rates="generalized"):
+    """The joint coordinates of body states -- the inverse of forward kinematics (Warp's eval_ik): body_q (..., nb, 7) poses (p, q xyzw)
+    and body_qd (..., nb, 6) twists in Warp order (w, v) -- wp_pos / wp_vel rows reshaped to (..., nb, .) -- -> (joint_q (..., nq),
+    joint_qd (..., nqd)) in the layouts ``ForwardKinematics`` takes.  rates="generalized": the generalised velocities (FK of the result
+    gives the state back); rates="measured": the rates a step's PD controller sees; they differ for COMPOUND joints only, and the
+    generalised ones are singular at |second angle| = pi / 2.  One HIP launch (``dp_model.InverseKinematics``), differentiable in
+    body_q and body_qd (raw partials; the quaternion entries are not projected).  float32 GPU tensors only."""
+    from .dp_model import InverseKinematics
+
+    _need_gpu("joint_coords", body_q, body_qd)
+    nb = int(env.nb)
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
+            and body_q.shape[:-2] == body_qd.shape[:-2]):
+        raise ValueError("joint_coords: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
+            nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+    lead = tuple(body_q.shape[:-2])
+    q, qd = InverseKinematics.apply(body_q.reshape(-1, 1, nb, 7), body_qd.reshape(-1, 1, nb, 6), env, rates)
+    return q.reshape(lead + (q.shape[-1],)), qd.reshape(lead + (qd.shape[-1],))
+
+
 def compute_com(body_q, part_com, part_mass):
     """mass-weighted COM of one articulation (numpy)   dp_utils.py:86-90"""
     from scipy.spatial.transform import Rotation as R

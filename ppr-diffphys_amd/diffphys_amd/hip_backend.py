@@ -863,6 +863,137 @@ def env_contact_table(env, device):
     return cache[key]
 
 
+POSE_JOINT_COORDS = 6
+_JC_HEAD, _JC_BODY, _JC_MAXCH = 4, 24, 8   # floats of the joint table's header / per body, children kept per body (include/ppr_diffphys.h)
+_JC_RATES = {"measured": 0, "generalized": 1}
+_JC_WIDTH = {1: (1, 1), 3: (0, 0), 4: (7, 6), 5: (3, 3)}   # joint type -> (coordinates, rates): REVOLUTE, FIXED, FREE, COMPOUND
+
+
+def joint_table_layout(nb):
+    """Float offsets of the joint table's blocks -> dict(bodies, children, floats)."""
+    bodies = _JC_HEAD
+    children = bodies + _JC_BODY * nb
+    return dict(bodies=bodies, children=children, floats=children + _JC_MAXCH * nb)
+
+
+def _jc_rate_mode(rates):
+    if rates not in _JC_RATES:
+        raise ValueError("joint_coords: rates must be 'generalized' or 'measured'; got %r" % (rates,))
+    return _JC_RATES[rates]
+
+
+def joint_table_host(tpl, rates="generalized"):
+    """The joint table of PD_POSE_JOINT_COORDS as a float32 numpy array (layout: include/ppr_diffphys.h): a header (nb, nq, nqd, rate
+    mode), per body its parent, joint type, coordinate starts, joint_X_p, axis, the quaternion of joint_X_c, com and child count, then
+    each body's children (at most 8) in template order.  Every joint's coordinates must lie inside [0, nq) and [0, nqd)."""
+    mode = _jc_rate_mode(rates)
+    nb, nq, nqd = int(tpl["nb"]), int(tpl["nq"]), int(tpl["nqd"])
+    if not 1 <= nb <= 256:
+        raise ValueError("joint_table: %d bodies; the op serves 1 .. 256" % nb)
+    ty = np.asarray(tpl["joint_type"], dtype=np.int64).reshape(nb)
+    par = np.asarray(tpl["joint_parent"], dtype=np.int64).reshape(nb)
+    qs = np.asarray(tpl["joint_q_start"], dtype=np.int64).reshape(-1)[:nb]
+    qds = np.asarray(tpl["joint_qd_start"], dtype=np.int64).reshape(-1)[:nb]
+    L = joint_table_layout(nb)
+    t = np.zeros(L["floats"], np.float32)
+    t[:4] = (nb, nq, nqd, mode)
+    body = t[L["bodies"]: L["children"]].reshape(nb, _JC_BODY)
+    kids = t[L["children"]:].reshape(nb, _JC_MAXCH)
+    kids[:] = -1
+    for b in range(nb):
+        if int(ty[b]) not in _JC_WIDTH:
+            raise ValueError("joint_table: body %d has joint type %d; REVOLUTE, FIXED, FREE and COMPOUND joints only" % (b, ty[b]))
+        wq, wqd = _JC_WIDTH[int(ty[b])]
+        if not (-1 <= par[b] < nb and par[b] != b):
+            raise ValueError("joint_table: body %d has parent %d" % (b, par[b]))
+        if wq and not (0 <= qs[b] and qs[b] + wq <= nq and 0 <= qds[b] and qds[b] + wqd <= nqd):
+            raise ValueError("joint_table: the coordinates of body %d (q %d + %d, qd %d + %d) leave [0, %d) x [0, %d)" % (
+                b, qs[b], wq, qds[b], wqd, nq, nqd))
+        ch = np.flatnonzero(par == b)   # template order
+        if len(ch) > _JC_MAXCH:
+            raise ValueError("joint_table: body %d has %d children; at most %d" % (b, len(ch), _JC_MAXCH))
+        kids[b, :len(ch)] = ch
+        body[b, 21] = len(ch)
+    body[:, 0], body[:, 1], body[:, 2], body[:, 3] = par, ty, qs, qds
+    body[:, 4:11] = np.asarray(tpl["joint_X_p"], dtype=np.float32).reshape(nb, 7)
+    body[:, 11:14] = np.asarray(tpl["joint_axis"], dtype=np.float32).reshape(nb, 3)
+    body[:, 14:18] = np.asarray(tpl["joint_X_c"], dtype=np.float32).reshape(nb, 7)[:, 3:]
+    body[:, 18:21] = np.asarray(tpl["body_com"], dtype=np.float32).reshape(nb, 3)
+    return t
+
+
+def _joint_dims(table):
+    return getattr(table, "_pd_joint_dims", None)
+
+
+def joint_table(tpl, rates="generalized", device="cuda"):
+    """The joint table operand of ``joint_coords`` for a template dict, as a float32 tensor on ``device``; its dimensions (nb, nq, nqd)
+    travel with the tensor."""
+    t = torch.from_numpy(joint_table_host(tpl, rates)).to(device)
+    t._pd_joint_dims = (int(tpl["nb"]), int(tpl["nq"]), int(tpl["nqd"]))
+    return t
+
+
+def env_joint_table(env, device, rates="generalized"):
+    """The joint table of a :class:`diffphys_amd.sim.Model`, cached on the model per (device, rates)."""
+    _jc_rate_mode(rates)
+    cache = getattr(env, "_joint_table", None)
+    if cache is None:
+        cache = env._joint_table = {}
+    key = (str(torch.device(device)), rates)
+    if key not in cache:
+        cache[key] = joint_table(env.template(), rates, device)
+    return cache[key]
+
+
+def _jc_check(table, nb, state):
+    """Shapes of a joint-coordinates call -> (n, nq, nqd).  The dimensions come from the table tensor joint_table made (the library
+    cannot validate a device buffer, so a bare tensor is refused)."""
+    dims = _joint_dims(table)
+    if dims is None:
+        raise ValueError("joint_coords: the table must come from hip_backend.joint_table (it carries nb, nq and nqd)")
+    if state.dim() != 2 or state.shape[1] != 13:
+        raise ValueError("joint_coords: state must be [n, 13] = (p, q xyzw, w, v) rows; got %s" % (tuple(state.shape),))
+    n = int(state.shape[0])
+    if nb < 1 or n % nb:
+        raise ValueError("joint_coords: %d state rows are no multiple of nb = %d" % (n, nb))
+    if dims[0] != nb:
+        raise ValueError("joint_coords: the joint table is one of nb = %d; the call says nb = %d" % (dims[0], nb))
+    _dev(table, "table")
+    if n:
+        _dev(state, "state")
+        if state.device != table.device:
+            raise ValueError("joint_coords: state on %s, the table on %s" % (state.device, table.device))
+    return n, dims[1], dims[2]
+
+
+def joint_coords(table, nb, state):
+    """``pd_pose_op`` PD_POSE_JOINT_COORDS: state [n, 13] = (p, q xyzw, w, v) rows, n a multiple of nb (row i is body i % nb of set
+    i // nb) -> (joint_q [n / nb, nq], joint_qd [n / nb, nqd]), views of ONE [n / nb, nq + nqd] buffer -- the inverse of ``fk_forward``
+    (rates as the table was built: "generalized" or "measured")."""
+    n, nq, nqd = _jc_check(table, int(nb), state)
+    out = torch.empty(n // int(nb), nq + nqd, device=state.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_JOINT_COORDS, n, _dev(table, "table"), int(nb), _ptr(state, "state"), _ptr(out, "out"), _stream()))
+    return out[:, :nq], out[:, nq:]
+
+
+def joint_coords_vjp(table, nb, state, g_q, g_qd):
+    """``pd_pose_op_vjp`` PD_POSE_JOINT_COORDS: g_q [n / nb, nq], g_qd [n / nb, nqd] -> g_state [n, 13], the raw partials (quaternion
+    entries not projected).  Fixed summation order: the same bits on every call."""
+    n, nq, nqd = _jc_check(table, int(nb), state)
+    sets = n // int(nb)
+    for g, w, name in ((g_q, nq, "g_q"), (g_qd, nqd, "g_qd")):
+        if not torch.is_tensor(g) or tuple(g.shape) != (sets, w):
+            raise ValueError("joint_coords_vjp: %s must be a [%d, %d] tensor; got %s" % (name, sets, w, tuple(getattr(g, "shape", ()))))
+        if not (g.is_cuda and g.dtype is torch.float32):
+            raise TypeError("joint_coords_vjp: %s must be a float32 GPU tensor; got %s on %s" % (name, g.dtype, g.device))
+    g_out = torch.cat([g_q, g_qd], dim=1)
+    g_b = torch.empty(n, 13, device=state.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_JOINT_COORDS, n, _dev(table, "table"), int(nb), _ptr(state, "state"),
+                                _ptr(g_out, "g_out", sets * (nq + nqd)), None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
 def _dev_int(t, name):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
         raise TypeError("%s must be a contiguous int32 GPU tensor" % name)

@@ -663,7 +663,7 @@ class phys_model(nn.Module):
                     out["total_loss"].backward()
             torch.cuda.current_stream().wait_stream(side)
             st = dict(graph=graph, fs=g_fs, noise=g_noise, out=out, nan=self._pending_nan, grads=[(p, p.grad) for p in params if p.grad is not None],
-                      side=dict(grfs=self.grfs, jafs=self.jafs, sim=self.sim_trajs._dev, tgt=self.target_trajs._dev, pid=self.pid_ref._dev,
+                      side=dict(grfs=self.grfs, jafs=self.jafs, sim=self.sim_trajs._dev, vel=self.sim_vels._dev, tgt=self.target_trajs._dev, pid=self.pid_ref._dev,
                                 info=self.traj_loss_info), shape=(n, self.frames_per_wdw), weights=weights, env=self.env, replays=0,
                       absent=bool(self.absent_zero_controls))   # (the graph holds the static zero buffers and their memsets, or does not)
             if validate:
@@ -735,17 +735,20 @@ class phys_model(nn.Module):
         from .dp_model import HostFrames
         self.grfs, self.jafs, self.traj_loss_info = side["grfs"], side["jafs"], side["info"]
         self.sim_trajs, self.target_trajs, self.pid_ref = HostFrames(side["sim"]), HostFrames(side["tgt"]), HostFrames(side["pid"])
+        self.sim_vels = HostFrames(side["vel"])
         return st["out"]
 
     @torch.no_grad()
-    def query(self, img_size=None):
+    def query(self, img_size=None, joint_coords=False):
         """Env 0 of the last forward(), frame by frame, in the reference's keys (dp_model.py:843-902): the simulated, target and
         control-reference robots POSED -- the reference hands trimesh objects to its renderer (articulate_robot_rbrt:
         collision-mesh vertices rotated and translated by each body's pose); here each is the array of those posed vertices
         [F, n_vertices, 3] (the collision vertices of all bodies in template order = the contact candidates, `vertex_body`
         says which body each belongs to; triangle indices, colours and force arrows are the renderer's and out of scope) --
         plus the centre of mass of the target (`com_k`) and simulated (`com`) robot per frame (dp_utils.py:86-90 with the env's
-        template masses, as the reference), `max_w`, the raw body poses (`*_poses` [F, nb, 7]) and the frame forces."""
+        template masses, as the reference), `max_w`, the raw body poses (`*_poses` [F, nb, 7]) and the frame forces.
+        joint_coords=True adds `sim_joint_q` [F, nq] / `sim_joint_qd` [F, nqd]: the joint coordinates of `sim_poses` and the frame twists
+        (dp_utils.joint_coords, generalised rates; one small launch on the env's device) -- comparable with ref_ja, the PD targets."""
         sim = np.stack(list(self.sim_trajs), 0).astype(np.float64)
         tgt = np.stack(list(self.target_trajs), 0).astype(np.float64)
         ref = np.stack(list(self.pid_ref), 0).astype(np.float64)
@@ -779,4 +782,13 @@ class phys_model(nn.Module):
         data["max_w"] = float(3 * np.abs(rest[:, [0, 2]]).max())
         if img_size is not None:
             data["img_size"] = img_size
+        if joint_coords:
+            from .dp_utils import joint_coords as _joint_coords
+
+            vels = getattr(self, "sim_vels", None)
+            if vels is None:
+                raise RuntimeError("query(joint_coords=True): the last forward() left no frame twists (sim_vels)")
+            up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
+            jq, jqd = _joint_coords(up(self.sim_trajs), up(vels), self.env)
+            data["sim_joint_q"], data["sim_joint_qd"] = jq.cpu().numpy(), jqd.cpu().numpy()
         return data
