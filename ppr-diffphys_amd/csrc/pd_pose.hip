@@ -361,10 +361,17 @@ __global__ __launch_bounds__(256) void k_ground_wrench_vjp(int n, int nb, const 
 #pragma unroll
     for (int j = 0; j < PD_ADJ; ++j) acc[j] = 0.f;
     if (sweep) {
+      // The state row is taken as it is, so its quaternion need not be unit -- and then qrot_inv(q, rc), from which contact_point_adj
+      // recovers the body-frame centre of mass (the rollouts' states are normalised every step), is not com: the two-piece form with
+      // the table's own com instead, so that g_b is the gradient of what the forward kernel computes for ANY row.
+      const v3 com = ld3(T.body + GW_BODY * (int)(i % nb));
       for (int k = lane; k < count; k += 64) {
         const int c = first + k;
+        const float4 P = T.pts[c], M = T.mats[(int)T.pmat[c]];
+        ContactPre pre = contact_point_adj_pre(rec, cv, P, M);
+        pre.com = com;
         BodyAdj o;
-        if (contact_point_adj(rec, cv, T.pts[c], T.mats[(int)T.pmat[c]], g_t, g_f, o)) {
+        if (contact_point_adj_rest(pre, P, M, g_t, g_f, o)) {
           float t[PD_ADJ];
           adj_store(t, o);
 #pragma unroll

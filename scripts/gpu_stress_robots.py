@@ -10,6 +10,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "ppr-diffphys_amd"), os.path.join(ROOT,
 import numpy as np, torch
 from diffphys_amd import hip_backend, sim
 from diffphys_amd.import_urdf import parse_urdf
+from generated_robots import make_urdf   # the generator (shared with the state-op tests)
 from helpers import build_template, own_trajectory_check, relmax
 from oracle.ref_c import RefC
 
@@ -20,41 +21,6 @@ FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd"
 BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 tmp = tempfile.mkdtemp()
 
-
-def make_urdf(kinds, n_joints, rotated, branchy):
-    def coll():
-        o = "%.3f %.3f %.3f" % tuple(rng.uniform(-0.03, 0.03, 3))
-        if rng.rand() < 0.6:
-            return '<collision><origin xyz="%s"/><geometry><box size="%.3f %.3f %.3f"/></geometry></collision>' % ((o,) + tuple(rng.uniform(0.04, 0.1, 3)))
-        return '<collision><origin xyz="%s"/><geometry><sphere radius="%.3f"/></geometry></collision>' % (o, rng.uniform(0.02, 0.05))
-    links = ['<link name="base">%s</link>' % coll()]
-    joints, bodies = [], ["base"]
-    for i in range(n_joints):
-        par = bodies[rng.randint(len(bodies))] if branchy else bodies[-1]
-        kind = kinds[rng.randint(len(kinds))]
-        xyz = "%.3f %.3f %.3f" % tuple(rng.uniform(-0.12, 0.12, 3))
-        rpy = "%.3f %.3f %.3f" % tuple(rng.uniform(-0.6, 0.6, 3)) if rotated else "0 0 0"
-        ax = rng.randn(3); ax /= np.linalg.norm(ax)
-        if not rotated:
-            ax = np.eye(3)[rng.randint(3)] * (1 if rng.rand() < 0.5 else -1)
-        axs = "%.4f %.4f %.4f" % tuple(ax)
-        if kind == "rev":
-            links.append('<link name="L%d">%s</link>' % (i, coll()))
-            joints.append('<joint name="j%d" type="continuous"><parent link="%s"/><child link="L%d"/><axis xyz="%s"/><origin xyz="%s" rpy="%s"/><limit effort="1" velocity="1"/></joint>' % (i, par, i, axs, xyz, rpy))
-            bodies.append("L%d" % i)
-        elif kind == "fix":
-            links.append('<link name="F%d">%s</link>' % (i, coll()))
-            joints.append('<joint name="j%d" type="fixed"><parent link="%s"/><child link="F%d"/><origin xyz="%s" rpy="%s"/></joint>' % (i, par, i, xyz, rpy))
-            bodies.append("F%d" % i)
-        else:
-            links.append('<link name="c%d_R"/><link name="c%d_P"/><link name="c%d_Y">%s</link>' % (i, i, i, coll()))
-            joints.append('<joint name="c%d_R" type="revolute"><parent link="%s"/><child link="c%d_R"/><axis xyz="1 0 0"/><origin xyz="%s" rpy="%s"/><limit lower="-1.5" upper="1.5" effort="1" velocity="1"/></joint>'
-                          '<joint name="c%d_P" type="revolute"><parent link="c%d_R"/><child link="c%d_P"/><axis xyz="0 1 0"/></joint>'
-                          '<joint name="c%d_Y" type="revolute"><parent link="c%d_P"/><child link="c%d_Y"/><axis xyz="0 0 1"/></joint>' % (i, par, i, xyz, rpy, i, i, i, i, i, i))
-            bodies.append("c%d_Y" % i)
-    return '<?xml version="1.0"?>\n<robot name="r">\n' + "\n".join(links) + "\n" + "\n".join(joints) + "\n</robot>\n"
-
-
 bad = 0
 for r in range(nrob):
     flavour = rng.randint(5)
@@ -63,7 +29,7 @@ for r in range(nrob):
     n_joints = int(rng.choice([1, 2, 3, 5, 8, 12, 15, 20, 30, 39]))
     branchy = rng.rand() < 0.7
     path = os.path.join(tmp, "r%d.urdf" % r)
-    open(path, "w").write(make_urdf(kinds, n_joints, rotated, branchy))
+    open(path, "w").write(make_urdf(rng, kinds, n_joints, rotated, branchy))
     b = sim.ModelBuilder()
     limit_ke = float(rng.choice([0.0, 40.0]))
     parse_urdf(path, b, xform=sim.transform((0, 0.3, 0), sim.quat_identity()), floating=True, density=1000.0, armature=0.002, stiffness=30.0, damping=0.3,

@@ -140,9 +140,15 @@ RECORDED = {"human": (3.7e-7, 2.5e-6), "quad": (5.3e-7, 2.5e-6)}
 
 @pytest.mark.parametrize("name", ["laikago", "laikago_toes", "human", "quad"])
 def test_restatement_inverts_eval_fk(name):
+    bar = tuple(4 * r for r in RECORDED[name]) if name in RECORDED else (1e-12, 1e-12)
+    restatement_against_eval_fk(load_tpl(name), name, *bar)
+
+
+def restatement_against_eval_fk(tpl, name, bar_q, bar_qd):
+    """IK(FK(q, qd)) in float64 on 64 random coordinate sets, and the measured rates against eval_body_joints' axes (shared with
+    tests/test_state_ops_generated_host.py, which runs it on generated robots)."""
     from oracle import ref_torch as rt
 
-    tpl = load_tpl(name)
     T = oracle_template(tpl)
     S = 64
     q, qd = (torch.as_tensor(a) for a in random_coords(tpl, S, seed=11))
@@ -150,10 +156,7 @@ def test_restatement_inverts_eval_fk(name):
     jq, jqd = joint_coords(T, bq, bqd, "generalized")
     e_q, e_qd = float((jq - q).abs().max()), float((jqd - qd).abs().max())
     print("%s: IK(FK) max |dq| %.2e, max |dqd| %.2e (generalized)" % (name, e_q, e_qd))
-    if name in RECORDED:
-        assert e_q <= 4 * RECORDED[name][0] and e_qd <= 4 * RECORDED[name][1], (e_q, e_qd)
-    else:
-        assert e_q <= 1e-12 and e_qd <= 1e-12, (e_q, e_qd)
+    assert e_q <= bar_q and e_qd <= bar_qd, (e_q, e_qd)
     mq, mqd = joint_coords(T, bq, bqd, "measured")
     assert torch.equal(mq, jq)
     comp = [i for i in range(T.nb) if T.joint_type[i] == rt.JOINT_COMPOUND]
@@ -193,6 +196,15 @@ def test_restatement_gives_the_numbers_the_joint_pass_acts_on(name):
     allq, allqd = rt.rollout(T, *t, nsteps, [0], inp["dt"], return_all=True)
     bq, bqd = allq[nsteps], allqd[nsteps]
     assert float((bq - allq[0]).abs().max()) > 1e-4   # it moved
+    assert restatement_against_the_joint_pass(T, bq, bqd) >= 12
+
+
+def restatement_against_the_joint_pass(T, bq, bqd):
+    """The restatement's measured coordinates of float64 states [bs, nb, 7], [bs, nb, 6] against the lines of eval_body_joints, for
+    every REVOLUTE and COMPOUND joint -> their number (shared with tests/test_state_ops_generated_host.py)."""
+    from oracle import ref_torch as rt
+
+    bs = bq.shape[0]
     jq, jqd = joint_coords(T, bq, bqd, "measured")
     seen = 0
     for i in range(T.nb):
@@ -217,4 +229,5 @@ def test_restatement_gives_the_numbers_the_joint_pass_acts_on(name):
             angles = rt.quat_decompose(rt.q_mul(rt.q_mul(rt.q_mul(rt.q_conj(q_off), rt.q_conj(q_p)), q_c), q_off))
             assert float((jq[:, qs: qs + 3] - angles).abs().max()) <= 1e-12
         seen += 1
-    assert seen == sum(ty in (rt.JOINT_REVOLUTE, rt.JOINT_COMPOUND) for ty in T.joint_type) and seen >= 12
+    assert seen == sum(ty in (rt.JOINT_REVOLUTE, rt.JOINT_COMPOUND) for ty in T.joint_type)
+    return seen
