@@ -392,11 +392,37 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  *                              (xyzw), com.xyz, number of children, 0, 0
  *   then 8 floats per body     its children in template order, -1 padded (a body with more than 8 children is refused by the builder)
  * As with the contact table, a table of another model is the caller's error.
+ *
+ * Whole-body (centroidal) quantities of body states -- total mass, centre of mass and its velocity, linear momentum, angular momentum
+ * about the centre of mass, kinetic and potential energy, per state set:
+ *   PD_POSE_CENTROIDAL     b = rows [n][23] = (p, q xyzw, w, v, m, I row-major 3x3): a state row as for PD_POSE_GROUND_WRENCH (v the
+ *                          velocity of the body's centre of mass, w the world angular velocity), the body's mass and its body-frame
+ *                          inertia about its centre of mass (the rollouts' body_inertia).  a_broadcast = nb as above (nb < 1 or
+ *                          n % nb != 0 is refused at every n; nb <= 256).  a = ONE mass table for all elements -> out [n / nb][16] =
+ *                          (M, c.xyz, c_dot.xyz, P.xyz, L.xyz, T, V, 0) of each state set, with x_i = p_i + R(q_i) com_i,
+ *                          wb_i = R(q_i)^T w_i (R(q) the map of the quaternion AS IT IS, not normalised, as in the two ops above):
+ *                            M = sum m_i     c = sum m_i x_i / M     P = sum m_i v_i     c_dot = P / M
+ *                            L = sum [ R(q_i) I_i wb_i + m_i (x_i - c) x (v_i - c_dot) ]       (about the centre of mass)
+ *                            T = sum [ m_i |v_i|^2 / 2 + wb_i . I_i wb_i / 2 ]                 V = -sum m_i gravity . x_i
+ *                          Whole state sets share a workgroup, a lane per body; two fixed-order tree reductions per set in LDS (first
+ *                          M, c, c_dot, P; L is then formed relative to c and c_dot), no atomics: a set's bits depend neither on the
+ *                          run nor on n nor on the set's place in the launch.
+ *                          VJP: g_out [n / nb][16] (entry 15 is ignored) -> g_b [n][23], the raw partials with respect to the state,
+ *                          the mass and the nine inertia entries (no symmetry assumed, quaternion entries not projected).  The table
+ *                          has no gradient: a non-NULL g_a is refused, at every n.
+ * The mass table: a 16-byte-aligned float buffer built on the host (hip_backend.mass_table is the one builder):
+ *   [0..3]                     nb, 0, 0, 0
+ *   [4..7]                     gravity.xyz, 0
+ *   then 4 floats per body     com.xyz, 0
+ * A table whose nb is not the call's a_broadcast is not read beyond its first float: out / g_b are then written as zeros.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
- * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH and PD_POSE_JOINT_COORDS are new op codes of the two entries: no symbol or
- * signature changed, the version stays 9. */
+ * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS and PD_POSE_CENTROIDAL are new op codes of the two
+ * entries: no symbol or signature changed, the version stays 9.  The enum has a gap: codes 7 and 8 are NOT assigned and are refused as
+ * "unknown op" -- callers and tests of version 9 rely on that refusal, so the next op took 9 and the two stay free for as long as the
+ * version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
-       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6 };
+       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

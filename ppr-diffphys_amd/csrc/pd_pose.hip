@@ -607,6 +607,154 @@ __global__ __launch_bounds__(256) void k_joint_coords_vjp(int nsets, int nb, con
   for (int k = 0; k < PD_ADJ; ++k) dst[k] = o[k];
 }
 
+// ---- PD_POSE_CENTROIDAL: the whole-body quantities of a state set -- total mass M, centre of mass c and its velocity c_dot, linear
+// momentum P, angular momentum L ABOUT c, kinetic energy T and potential energy V -- and their vector-Jacobian product with respect to
+// the state rows, the masses and the body-frame inertias.  Per body i (row = p, q xyzw, w, v, m, I row-major; com_i, gravity: the table):
+//   x_i = p_i + qrot(q_i, com_i)      wb_i = qrot_inv(q_i, w_i)      (quaternions as they are, like the two ops above)
+//   M = sum m_i    c = sum m_i x_i / M    P = sum m_i v_i    c_dot = P / M
+//   L = sum [ qrot(q_i, I_i wb_i) + m_i (x_i - c) x (v_i - c_dot) ]
+//   T = sum [ m_i |v_i|^2 / 2 + wb_i . I_i wb_i / 2 ]             V = -sum m_i gravity . x_i
+// Mapping (k_joint_coords_vjp's): 256 / nb whole state sets per workgroup, a lane per body.  Two stages: (m, m x, m v) per lane into LDS,
+// reduced per set; after the barrier every body reads its set's M, c, c_dot and forms its share of (L, T, V) RELATIVE to them (the
+// one-pass form sum m x x v - M c x c_dot cancels two terms of size M |c| |c_dot|: 250 ulps at 50 m); second reduction; lane 0 of the set
+// stores the 16 floats.  Reduction: a strided tree over the next power of two >= nb on the index of the body INSIDE its set -- depth
+// log2, a fixed order that depends on nb alone, so a set's bits do not depend on the run, on n or on where the set sits in the launch.
+// No atomics.  LDS slots have odd strides (7 and 5 floats: distinct banks).  The VJP repeats stage one and evaluates the closed-form
+// adjoint per body; the orbital term's derivative through c and c_dot vanishes (sum m_i (x_i - c) = sum m_i (v_i - c_dot) = 0), the one
+// through m_i does not.  The inertia is taken as ANY 3x3 matrix (raw partials: no symmetry assumed).
+// Mass table: include/ppr_diffphys.h (hip_backend.mass_table builds it).  A table of another nb: zeros are written, no row of it is read.
+enum { CT_HEAD = 8, CT_BODY = 4, CT_ROW = 23, CT_OUT = 16, CT_MAXNB = 256, CT_S1 = 7, CT_S2 = 5 };
+struct CtBody { qt q; v3 w, v, x; float m, I[9]; };
+struct CtTotals { float M; v3 c, cd, P; };
+__device__ __forceinline__ CtBody ct_load(const float *tab, int body, const float *r) {
+  CtBody B;
+  B.q = ld4(r + 3); B.w = ld3(r + 7); B.v = ld3(r + 10); B.m = r[13];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) B.I[k] = r[14 + k];
+  B.x = ld3(r) + qrot(B.q, ld3(tab + CT_HEAD + CT_BODY * body));
+  return B;
+}
+// Adds the W-float slots of each set's bodies into the slot of its body 0: lane `body` takes the slot `off` above its own while that one
+// is inside the set.  Every lane of the workgroup passes every barrier (the trip count depends on nb alone).
+template <int W>
+__device__ __forceinline__ void ct_reduce(float *slot, int nb, int body, bool in_set) {
+  int p2 = 1;
+  while (p2 < nb) p2 <<= 1;
+  for (int off = p2 >> 1; off > 0; off >>= 1) {
+    __syncthreads();
+    if (in_set && body < off && body + off < nb) {
+      float *mine = slot + threadIdx.x * W;
+      const float *other = slot + (threadIdx.x + off) * W;
+#pragma unroll
+      for (int k = 0; k < W; ++k) mine[k] += other[k];
+    }
+  }
+  __syncthreads();
+}
+// Stage one, shared by the two kernels: the lane's (m, m x, m v) into its slot, the per-set reduction, the set's totals.
+__device__ __forceinline__ CtTotals ct_stage1(float *s1, int nb, int set_l, int body, bool in_set, bool active, const CtBody &B) {
+  float *mine = s1 + threadIdx.x * CT_S1;
+  const v3 mx = active ? B.x * B.m : V3(0, 0, 0), mv = active ? B.v * B.m : V3(0, 0, 0);
+  mine[0] = active ? B.m : 0.0f;
+  mine[1] = mx.x; mine[2] = mx.y; mine[3] = mx.z; mine[4] = mv.x; mine[5] = mv.y; mine[6] = mv.z;
+  ct_reduce<CT_S1>(s1, nb, body, in_set);
+  CtTotals S;
+  S.M = 0.0f; S.c = V3(0, 0, 0); S.cd = S.c; S.P = S.c;
+  if (active) {
+    const float *t = s1 + set_l * nb * CT_S1;
+    S.M = t[0]; S.P = ld3(t + 4);
+    S.c = V3(t[1] / S.M, t[2] / S.M, t[3] / S.M);
+    S.cd = V3(S.P.x / S.M, S.P.y / S.M, S.P.z / S.M);
+  }
+  return S;
+}
+
+__global__ __launch_bounds__(256) void k_centroidal_fwd(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                        float *__restrict__ out) {
+  __shared__ float s1[256 * CT_S1], s2[256 * CT_S2];
+  const int per_wg = 256 / nb;  // whole state sets per workgroup
+  const int set_l = (int)threadIdx.x / nb, body = (int)threadIdx.x - set_l * nb;
+  const long long set = (long long)blockIdx.x * per_wg + set_l;
+  const bool in_set = set_l < per_wg, active = in_set && set < nsets;
+  if ((int)tab[0] != nb) {  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
+    if (active && body == 0)
+      for (int k = 0; k < CT_OUT; ++k) out[(size_t)set * CT_OUT + k] = 0.0f;
+    return;
+  }
+  CtBody B;
+  if (active) B = ct_load(tab, body, rows + ((size_t)set * nb + body) * CT_ROW);
+  const CtTotals S = ct_stage1(s1, nb, set_l, body, in_set, active, B);
+  float *mine = s2 + threadIdx.x * CT_S2;
+#pragma unroll
+  for (int k = 0; k < CT_S2; ++k) mine[k] = 0.0f;
+  if (active) {
+    const v3 g = ld3(tab + 4);
+    const v3 wb = qrot_inv(B.q, B.w), h = mat_vec(B.I, wb);
+    const v3 l = qrot(B.q, h) + cross(B.x - S.c, B.v - S.cd) * B.m;
+    mine[0] = l.x; mine[1] = l.y; mine[2] = l.z;
+    mine[3] = 0.5f * B.m * dot(B.v, B.v) + 0.5f * dot(wb, h);
+    mine[4] = -B.m * dot(g, B.x);
+  }
+  ct_reduce<CT_S2>(s2, nb, body, in_set);
+  if (active && body == 0) {
+    float *o = out + (size_t)set * CT_OUT;
+    o[0] = S.M;
+    o[1] = S.c.x; o[2] = S.c.y; o[3] = S.c.z;
+    o[4] = S.cd.x; o[5] = S.cd.y; o[6] = S.cd.z;
+    o[7] = S.P.x; o[8] = S.P.y; o[9] = S.P.z;
+#pragma unroll
+    for (int k = 0; k < CT_S2; ++k) o[10 + k] = mine[k];
+    o[15] = 0.0f;
+  }
+}
+
+// g_b [n][23]: the raw partials of <g_out, out> with respect to (p, q, w, v, m, I) of every body.
+__global__ __launch_bounds__(256) void k_centroidal_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                        const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float s1[256 * CT_S1];
+  const int per_wg = 256 / nb;
+  const int set_l = (int)threadIdx.x / nb, body = (int)threadIdx.x - set_l * nb;
+  const long long set = (long long)blockIdx.x * per_wg + set_l;
+  const bool in_set = set_l < per_wg, active = in_set && set < nsets;
+  float *dst = g_b + ((size_t)set * nb + body) * CT_ROW;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {
+    if (active)
+      for (int k = 0; k < CT_ROW; ++k) dst[k] = 0.0f;
+    return;
+  }
+  CtBody B;
+  if (active) B = ct_load(tab, body, rows + ((size_t)set * nb + body) * CT_ROW);
+  const CtTotals S = ct_stage1(s1, nb, set_l, body, in_set, active, B);
+  if (!active) return;
+  const float *go = g_out + (size_t)set * CT_OUT;
+  const float gM = go[0], gT = go[13], gV = go[14], iM = 1.0f / S.M;
+  const v3 gc = ld3(go + 1), gcd = ld3(go + 4), gP = ld3(go + 7), gL = ld3(go + 10);
+  const v3 grav = ld3(tab + 4), com = ld3(tab + CT_HEAD + CT_BODY * body);
+  const v3 rx = B.x - S.c, rv = B.v - S.cd;
+  // x_i: through c, the orbital term and V;  v_i: through c_dot, P, the orbital term and T;  m_i: through all seven
+  const v3 adj_x = (gc * iM + cross(rv, gL) - grav * gV) * B.m;
+  const v3 adj_v = (gcd * iM + gP + cross(gL, rx) + B.v * gT) * B.m;
+  const float adj_m = gM + (dot(gc, rx) + dot(gcd, rv)) * iM + dot(gP, B.v) + dot(gL, cross(rx, rv)) + 0.5f * gT * dot(B.v, B.v) - gV * dot(grav, B.x);
+  qt adj_q = Q4(0, 0, 0, 0);
+  adj_qrot_q(B.q, com, adj_q, adj_x);  // x = p + qrot(q, com)
+  // spin = qrot(q, h), h = I wb, wb = qrot_inv(q, w); T's rotational half wb . I wb / 2
+  const v3 wb = qrot_inv(B.q, B.w), h = mat_vec(B.I, wb);
+  const v3 adj_h = qrot_inv(B.q, gL);
+  adj_qrot_q(B.q, h, adj_q, gL);
+  const v3 adj_wb = matT_vec(B.I, adj_h) + (h + matT_vec(B.I, wb)) * (0.5f * gT);
+  v3 adj_w = V3(0, 0, 0);
+  adj_qrot_inv(B.q, B.w, adj_q, adj_w, adj_wb);
+  const v3 ai = adj_h + wb * (0.5f * gT);  // d / d I[j][k] = ai_j wb_k
+  dst[0] = adj_x.x; dst[1] = adj_x.y; dst[2] = adj_x.z;
+  dst[3] = adj_q.x; dst[4] = adj_q.y; dst[5] = adj_q.z; dst[6] = adj_q.w;
+  dst[7] = adj_w.x; dst[8] = adj_w.y; dst[9] = adj_w.z;
+  dst[10] = adj_v.x; dst[11] = adj_v.y; dst[12] = adj_v.z;
+  dst[13] = adj_m;
+  dst[14] = ai.x * wb.x; dst[15] = ai.x * wb.y; dst[16] = ai.x * wb.z;
+  dst[17] = ai.y * wb.x; dst[18] = ai.y * wb.y; dst[19] = ai.y * wb.z;
+  dst[20] = ai.z * wb.x; dst[21] = ai.z * wb.y; dst[22] = ai.z * wb.z;
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -660,8 +808,32 @@ int launch_joint_coords(int n, const float *tab, int nb, const float *state, flo
   return 2;
 }
 
+// a = the mass table, a_bcast = nb (the group size, as for the two ops above), b = rows [n][23] = (state, mass, inertia);
+// out / g_out [n / nb][16], g_b [n][23]
+int launch_centroidal(int n, const float *tab, int nb, const float *rows, float *out, const float *g_out, float *g_a, float *g_b,
+                      hipStream_t st) {
+  if (nb <= 0 || n % nb != 0)  // before the n == 0 return: a bad group size is refused at every n
+    return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
+  if (nb > CT_MAXNB) return pd_set_error("pd_pose_op: PD_POSE_CENTROIDAL serves at most 256 bodies per state set");
+  if (g_a) return pd_set_error("pd_pose_op_vjp: PD_POSE_CENTROIDAL has no gradient for its mass table -- g_a_dev must be NULL");
+  if (n == 0) return 0;
+  if (!tab || !rows) return pd_set_error("pd_pose_op: a NULL operand");
+  if ((size_t)tab & 15) return pd_set_error("pd_pose_op: the mass table a_dev must be 16-byte aligned");
+  const int nsets = n / nb, per_wg = 256 / nb;
+  const dim3 grid((unsigned)((nsets + per_wg - 1) / per_wg)), block(256);
+  if (out)
+    hipLaunchKernelGGL(k_centroidal_fwd, grid, block, 0, st, nsets, nb, tab, rows, out);
+  else
+    hipLaunchKernelGGL(k_centroidal_vjp, grid, block, 0, st, nsets, nb, tab, rows, g_out, g_b);
+  if (hipGetLastError() == hipSuccess) return 0;
+  pd_set_error("pd_pose_op: the kernel launch failed");
+  return 2;
+}
+
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || op > PD_POSE_JOINT_COORDS) return pd_set_error("pd_pose_op: n < 0 or an unknown op");
+  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL))  // (codes 7 and 8 are not assigned: include/ppr_diffphys.h)
+    return pd_set_error("pd_pose_op: n < 0 or an unknown op");
+  if (op == PD_POSE_CENTROIDAL) return launch_centroidal(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
   if (op == PD_POSE_GROUND_WRENCH) return launch_ground_wrench(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
   if (op == PD_POSE_JOINT_COORDS) return launch_joint_coords(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
   const bool project = op >= PD_POSE_PROJECT;

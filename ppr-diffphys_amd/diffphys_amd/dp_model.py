@@ -143,6 +143,46 @@ class InverseKinematics(torch.autograd.Function):
         return (g_s[..., :7] if ctx.needs_input_grad[0] else None), (g_s[..., 7:] if ctx.needs_input_grad[1] else None), None, None
 
 
+class Centroidal(torch.autograd.Function):
+    """body_q (..., nb, 7), body_qd (..., nb, 6) in Warp order (w, v), body_mass (..., nb), body_inertia (..., nb, 3, 3), env ->
+    (..., 16) = (M, c, c_dot, P, L about c, T, V, 0) per state set: the whole-body quantities of body states (``pd_pose_op``
+    PD_POSE_CENTROIDAL, one launch forward and one for the vector-Jacobian product).  All four tensors carry the SAME leading shape:
+    broadcasting shared masses is the caller's (``dp_utils.centroidal`` does it with expand, so that autograd sums their gradient).
+    float32 GPU tensors, or an error: no CPU fallback.  The gradients are the raw partials (quaternion entries not projected, no
+    symmetry assumed for the inertia), nothing is scrubbed."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_qd, body_mass, body_inertia, env):
+        nb = int(env.nb)
+        for t in (body_q, body_qd, body_mass, body_inertia):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+                raise TypeError("Centroidal needs float32 GPU tensors (the product path has no CPU fallback); got %s" % (
+                    "%s on %s" % (t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_qd.shape) == lead + (nb, 6)
+                and tuple(body_mass.shape) == lead + (nb,) and tuple(body_inertia.shape) == lead + (nb, 3, 3)):
+            raise ValueError("Centroidal: body_q (..., %d, 7), body_qd (..., %d, 6), body_mass (..., %d) and body_inertia (..., %d, 3, 3) "
+                             "with equal leading shapes; got %s, %s, %s and %s" % (
+                                 nb, nb, nb, nb, tuple(body_q.shape), tuple(body_qd.shape), tuple(body_mass.shape), tuple(body_inertia.shape)))
+        table = hip_backend.env_mass_table(env, body_q.device)
+        rows = torch.cat([body_q.detach().reshape(-1, 7), body_qd.detach().reshape(-1, 6), body_mass.detach().reshape(-1, 1),
+                          body_inertia.detach().reshape(-1, 9)], dim=1)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows)
+        return hip_backend.centroidal(table, nb, rows).view(lead + (16,))
+
+    @staticmethod
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:4]):
+            return None, None, None, None, None
+        lead, nb = ctx.lead, ctx.nb
+        g_r = hip_backend.centroidal_vjp(ctx.table, nb, rows, g.to(torch.float32).reshape(-1, 16).contiguous())
+        need = ctx.needs_input_grad
+        return (g_r[:, :7].reshape(lead + (nb, 7)) if need[0] else None, g_r[:, 7:13].reshape(lead + (nb, 6)) if need[1] else None,
+                g_r[:, 13].reshape(lead + (nb,)) if need[2] else None, g_r[:, 14:].reshape(lead + (nb, 3, 3)) if need[3] else None, None)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

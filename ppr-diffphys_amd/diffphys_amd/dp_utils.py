@@ -1,5 +1,7 @@
 """Loss / frame utilities around the simulator boundary.
 Same names and semantics as /root/reference/diffphys/dp_utils.py (cited per function)."""
+from typing import NamedTuple
+
 import torch
 
 from .dataloader import bullet2gl  # noqa: F401  (re-exported like the reference's dp_utils)
@@ -269,6 +271,47 @@ def joint_coords(body_q, body_qd, env, rates="generalized"):
     lead = tuple(body_q.shape[:-2])
     q, qd = InverseKinematics.apply(body_q.reshape(-1, 1, nb, 7), body_qd.reshape(-1, 1, nb, 6), env, rates)
     return q.reshape(lead + (q.shape[-1],)), qd.reshape(lead + (qd.shape[-1],))
+
+
+class CentroidalState(NamedTuple):
+    """What :func:`centroidal` returns: views of one (..., 16) tensor."""
+    mass: torch.Tensor              # (...)     M = sum m_i
+    com: torch.Tensor               # (..., 3)  c = sum m_i x_i / M
+    com_vel: torch.Tensor           # (..., 3)  c_dot = P / M
+    momentum: torch.Tensor          # (..., 3)  P = sum m_i v_i
+    angular_momentum: torch.Tensor  # (..., 3)  L about c
+    kinetic: torch.Tensor           # (...)     T
+    potential: torch.Tensor         # (...)     V = -sum m_i gravity . x_i
+
+
+def centroidal(body_q, body_qd, body_mass, body_inertia, env):
+    """The whole-body quantities of body states, per state set: body_q (..., nb, 7) poses (p, q xyzw) and body_qd (..., nb, 6) twists in
+    Warp order (w, v; v the velocity of the body's centre of mass) -- wp_pos / wp_vel rows reshaped to (..., nb, .) --, body_mass
+    broadcastable to (..., nb) and body_inertia (body frame, about the body's centre of mass: the rollouts' ``body_inertia``)
+    broadcastable to (..., nb, 3, 3) -> :class:`CentroidalState` (mass, com, com_vel, momentum, angular_momentum about the centre of
+    mass, kinetic, potential), views of one (..., 16) tensor.  The bodies' centres of mass and gravity are the env's.  One HIP launch
+    (``dp_model.Centroidal``), differentiable in the first four arguments (raw partials; quaternions are taken as they are); shared
+    masses are broadcast HERE, outside the Function, so autograd sums their gradient over the state sets.  float32 GPU tensors only."""
+    from .dp_model import Centroidal
+
+    _need_gpu("centroidal", body_q, body_qd, body_mass, body_inertia)
+    nb = int(env.nb)
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
+            and body_q.shape[:-2] == body_qd.shape[:-2]):
+        raise ValueError("centroidal: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
+            nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+    lead = tuple(body_q.shape[:-2])
+    def fits(t, shape):
+        try:
+            return tuple(torch.broadcast_shapes(tuple(t.shape), shape)) == shape
+        except RuntimeError:
+            return False
+
+    if not (fits(body_mass, lead + (nb,)) and fits(body_inertia, lead + (nb, 3, 3)) and tuple(body_inertia.shape[-2:]) == (3, 3)):
+        raise ValueError("centroidal: body_mass must broadcast to %s and body_inertia to %s; got %s and %s" % (
+            lead + (nb,), lead + (nb, 3, 3), tuple(body_mass.shape), tuple(body_inertia.shape)))
+    out = Centroidal.apply(body_q, body_qd, body_mass.expand(lead + (nb,)), body_inertia.expand(lead + (nb, 3, 3)), env)
+    return CentroidalState(out[..., 0], out[..., 1:4], out[..., 4:7], out[..., 7:10], out[..., 10:13], out[..., 13], out[..., 14])
 
 
 def compute_com(body_q, part_com, part_mass):

@@ -994,6 +994,98 @@ def joint_coords_vjp(table, nb, state, g_q, g_qd):
     return g_b
 
 
+POSE_CENTROIDAL = 9   # (codes 7 and 8 are not assigned: include/ppr_diffphys.h)
+_CT_HEAD, _CT_BODY, _CT_ROW, _CT_OUT = 8, 4, 23, 16   # floats of the mass table's header / per body, of an operand row, of an output row
+
+
+def mass_table_layout(nb):
+    """Float offsets of the mass table's blocks -> dict(gravity, bodies, floats)."""
+    return dict(gravity=4, bodies=_CT_HEAD, floats=_CT_HEAD + _CT_BODY * nb)
+
+
+def mass_table_host(tpl):
+    """The mass table of PD_POSE_CENTROIDAL as a float32 numpy array (layout: include/ppr_diffphys.h): (nb, 0, 0, 0), (gravity, 0), then
+    (com, 0) per body.  Masses and inertias are operands of the op, not part of the table: they carry gradients."""
+    nb = int(tpl["nb"])
+    if not 1 <= nb <= 256:
+        raise ValueError("mass_table: %d bodies; the op serves 1 .. 256" % nb)
+    L = mass_table_layout(nb)
+    t = np.zeros(L["floats"], np.float32)
+    t[0] = nb
+    t[L["gravity"]: L["gravity"] + 3] = np.asarray(tpl["gravity"], dtype=np.float32).reshape(3)
+    t[L["bodies"]:].reshape(nb, _CT_BODY)[:, :3] = np.asarray(tpl["body_com"], dtype=np.float32).reshape(nb, 3)
+    return t
+
+
+def _mass_dims(table):
+    return getattr(table, "_pd_mass_dims", None)
+
+
+def mass_table(tpl, device="cuda"):
+    """The mass table operand of ``centroidal`` for a template dict, as a float32 tensor on ``device``; its nb travels with the tensor."""
+    t = torch.from_numpy(mass_table_host(tpl)).to(device)
+    t._pd_mass_dims = (int(tpl["nb"]),)
+    return t
+
+
+def env_mass_table(env, device):
+    """The mass table of a :class:`diffphys_amd.sim.Model`, cached on the model per device."""
+    cache = getattr(env, "_mass_table", None)
+    if cache is None:
+        cache = env._mass_table = {}
+    key = str(torch.device(device))
+    if key not in cache:
+        cache[key] = mass_table(env.template(), device)
+    return cache[key]
+
+
+def _ct_check(table, nb, rows):
+    """Shapes of a centroidal call -> n.  nb comes with the table tensor mass_table made (the library cannot validate a device buffer, so
+    a bare tensor is refused)."""
+    dims = _mass_dims(table)
+    if dims is None:
+        raise ValueError("centroidal: the table must come from hip_backend.mass_table (it carries nb)")
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != _CT_ROW:
+        raise ValueError("centroidal: rows must be [n, 23] = (p, q xyzw, w, v, m, I row-major) rows; got %s" % (
+            tuple(getattr(rows, "shape", ())),))
+    n = int(rows.shape[0])
+    if nb < 1 or n % nb:
+        raise ValueError("centroidal: %d rows are no multiple of nb = %d" % (n, nb))
+    if dims[0] != nb:
+        raise ValueError("centroidal: the mass table is one of nb = %d; the call says nb = %d" % (dims[0], nb))
+    _dev(table, "table")
+    if n:
+        _dev(rows, "rows")
+        if rows.device != table.device:
+            raise ValueError("centroidal: rows on %s, the table on %s" % (rows.device, table.device))
+    return n
+
+
+def centroidal(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_CENTROIDAL: rows [n, 23] = (p, q xyzw, w, v, m, I row-major) per body, n a multiple of nb (row i is body
+    i % nb of set i // nb) -> [n / nb, 16] = (M, c, c_dot, P, L about c, T, V, 0) per state set.  Fixed summation order: a set's bits
+    depend neither on the call nor on the other sets."""
+    n = _ct_check(table, int(nb), rows)
+    out = torch.empty(n // int(nb), _CT_OUT, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_CENTROIDAL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def centroidal_vjp(table, nb, rows, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_CENTROIDAL: g_out [n / nb, 16] -> g_rows [n, 23], the raw partials with respect to the state, the mass
+    and the nine inertia entries of every body."""
+    n = _ct_check(table, int(nb), rows)
+    sets = n // int(nb)
+    if not torch.is_tensor(g_out) or tuple(g_out.shape) != (sets, _CT_OUT):
+        raise ValueError("centroidal_vjp: g_out must be a [%d, %d] tensor; got %s" % (sets, _CT_OUT, tuple(getattr(g_out, "shape", ()))))
+    if not (g_out.is_cuda and g_out.dtype is torch.float32):
+        raise TypeError("centroidal_vjp: g_out must be a float32 GPU tensor; got %s on %s" % (g_out.dtype, g_out.device))
+    g_b = torch.empty(n, _CT_ROW, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_CENTROIDAL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", sets * _CT_OUT),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
 def _dev_int(t, name):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
         raise TypeError("%s must be a contiguous int32 GPU tensor" % name)

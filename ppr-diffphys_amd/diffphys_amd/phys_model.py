@@ -739,7 +739,7 @@ class phys_model(nn.Module):
         return st["out"]
 
     @torch.no_grad()
-    def query(self, img_size=None, joint_coords=False):
+    def query(self, img_size=None, joint_coords=False, centroidal=False):
         """Env 0 of the last forward(), frame by frame, in the reference's keys (dp_model.py:843-902): the simulated, target and
         control-reference robots POSED -- the reference hands trimesh objects to its renderer (articulate_robot_rbrt:
         collision-mesh vertices rotated and translated by each body's pose); here each is the array of those posed vertices
@@ -748,7 +748,10 @@ class phys_model(nn.Module):
         plus the centre of mass of the target (`com_k`) and simulated (`com`) robot per frame (dp_utils.py:86-90 with the env's
         template masses, as the reference), `max_w`, the raw body poses (`*_poses` [F, nb, 7]) and the frame forces.
         joint_coords=True adds `sim_joint_q` [F, nq] / `sim_joint_qd` [F, nqd]: the joint coordinates of `sim_poses` and the frame twists
-        (dp_utils.joint_coords, generalised rates; one small launch on the env's device) -- comparable with ref_ja, the PD targets."""
+        (dp_utils.joint_coords, generalised rates; one small launch on the env's device) -- comparable with ref_ja, the PD targets.
+        centroidal=True adds `sim_centroidal`, a dict of arrays per frame -- mass [F], com, com_vel, momentum, angular_momentum [F, 3],
+        kinetic, potential [F] -- of `sim_poses` and the frame twists with the LEARNED body_mass and norm_body_inertia x body_mass
+        (dp_utils.centroidal; `com` / `com_k` above keep the template masses, as the reference)."""
         sim = np.stack(list(self.sim_trajs), 0).astype(np.float64)
         tgt = np.stack(list(self.target_trajs), 0).astype(np.float64)
         ref = np.stack(list(self.pid_ref), 0).astype(np.float64)
@@ -791,4 +794,15 @@ class phys_model(nn.Module):
             up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
             jq, jqd = _joint_coords(up(self.sim_trajs), up(vels), self.env)
             data["sim_joint_q"], data["sim_joint_qd"] = jq.cpu().numpy(), jqd.cpu().numpy()
+        if centroidal:
+            from .dp_utils import centroidal as _centroidal
+
+            vels = getattr(self, "sim_vels", None)
+            if vels is None:
+                raise RuntimeError("query(centroidal=True): the last forward() left no frame twists (sim_vels)")
+            up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
+            mass = self.body_mass.detach().to(self.device, torch.float32)
+            inertia = self.norm_body_inertia.detach().to(self.device, torch.float32) * mass[:, None, None]
+            cs = _centroidal(up(self.sim_trajs), up(vels), mass, inertia, self.env)
+            data["sim_centroidal"] = {k: v.cpu().numpy() for k, v in cs._asdict().items()}
         return data
