@@ -232,24 +232,52 @@ struct FkLocals {
   qt q_jc, q0, q1, q2, q_wj;
 };
 
+// fk_joint's arithmetic is PINNED: explicit fused multiply-adds in a fixed order (the one the compiler gives each expression on its own), every intermediate behind a register barrier, so that no
+// instantiation's surroundings decide which products -ffp-contract=fast fuses.  k_fk (pd_fk_forward) and the eval_fk of every rollout kernel
+// then give the same bits from the same joint coordinates: a zero-step rollout IS pd_fk_forward, bit for bit
+// (tests/test_gpu_rollout_generated.py; before, the two were an ulp apart on every robot).  FK runs once per launch: the barriers cost nothing
+// that shows.
+PD_DEV float fk_pin(float x) { asm volatile("" : "+v"(x)); return x; }
+PD_DEV v3 fk_pin(v3 a) { return V3(fk_pin(a.x), fk_pin(a.y), fk_pin(a.z)); }
+PD_DEV qt fk_pin(qt q) { return Q4(fk_pin(q.x), fk_pin(q.y), fk_pin(q.z), fk_pin(q.w)); }
+PD_DEV v3 fk_cross(v3 a, v3 b) {
+  return fk_pin(V3(__builtin_fmaf(a.y, b.z, -(a.z * b.y)), __builtin_fmaf(a.z, b.x, -(a.x * b.z)), __builtin_fmaf(a.x, b.y, -(a.y * b.x))));
+}
+PD_DEV v3 fk_qrot(qt q, v3 v) {  // qrot: v (2 w^2 - 1) + (u x v) 2 w + u 2 (u . v)
+  const v3 u = qvec(q), c = fk_cross(u, v);
+  const float s = fk_pin(__builtin_fmaf(2.0f * q.w, q.w, -1.0f)), tw = 2.0f * q.w;
+  const float d2 = fk_pin(2.0f * __builtin_fmaf(u.z, v.z, __builtin_fmaf(u.x, v.x, u.y * v.y)));
+  return fk_pin(V3(__builtin_fmaf(u.x, d2, __builtin_fmaf(v.x, s, c.x * tw)), __builtin_fmaf(u.y, d2, __builtin_fmaf(v.y, s, c.y * tw)),
+                   __builtin_fmaf(u.z, d2, __builtin_fmaf(v.z, s, c.z * tw))));
+}
+PD_DEV qt fk_qmul(qt a, qt b) {
+  return fk_pin(Q4(__builtin_fmaf(-a.z, b.y, __builtin_fmaf(a.y, b.z, __builtin_fmaf(a.w, b.x, b.w * a.x))),
+                   __builtin_fmaf(-a.x, b.z, __builtin_fmaf(a.z, b.x, __builtin_fmaf(a.w, b.y, b.w * a.y))),
+                   __builtin_fmaf(-a.y, b.x, __builtin_fmaf(a.x, b.y, __builtin_fmaf(a.w, b.z, b.w * a.z))),
+                   __builtin_fmaf(-a.z, b.z, __builtin_fmaf(-a.y, b.y, __builtin_fmaf(a.w, b.w, -(a.x * b.x))))));
+}
+PD_DEV qt fk_axis_angle(v3 axis, float ang) { return fk_pin(q_axis_angle(axis, ang)); }
+
 template <int JT>
 PD_DEV void fk_joint_local(const BodyConst &c, const float *jq, const float *jqd, FkLocals &L) {
   L.p_jc = V3(0, 0, 0); L.w_jc = V3(0, 0, 0); L.v_jc = V3(0, 0, 0); L.q_jc = Q4(0, 0, 0, 1);
   L.a0 = L.a1 = L.a2 = V3(0, 0, 0); L.q0 = L.q1 = L.q2 = Q4(0, 0, 0, 1);
   if ((JT & PD_JT_REVOLUTE) && c.type == PD_JOINT_REVOLUTE) {
-    L.q_jc = q_axis_angle(c.axis, jq[0]);
-    L.w_jc = c.axis * jqd[0];
+    L.q_jc = fk_axis_angle(c.axis, jq[0]);
+    L.w_jc = fk_pin(c.axis * jqd[0]);
   } else if (c.type == PD_JOINT_FREE) {
     L.p_jc = ld3(jq); L.q_jc = ld4(jq + 3); L.w_jc = ld3(jqd); L.v_jc = ld3(jqd + 3);
   } else if ((JT & PD_JT_COMPOUND) && c.type == PD_JOINT_COMPOUND) {
-    L.a0 = qrot(c.q_off, V3(1, 0, 0));
-    L.q0 = q_axis_angle(L.a0, jq[0]);
-    L.a1 = qrot(qmul(L.q0, c.q_off), V3(0, 1, 0));
-    L.q1 = q_axis_angle(L.a1, jq[1]);
-    L.a2 = qrot(qmul(L.q1, qmul(L.q0, c.q_off)), V3(0, 0, 1));
-    L.q2 = q_axis_angle(L.a2, jq[2]);
-    L.q_jc = qmul(L.q2, qmul(L.q1, L.q0));
-    L.w_jc = L.a0 * jqd[0] + L.a1 * jqd[1] + L.a2 * jqd[2];
+    L.a0 = fk_qrot(c.q_off, V3(1, 0, 0));
+    L.q0 = fk_axis_angle(L.a0, jq[0]);
+    L.a1 = fk_qrot(fk_qmul(L.q0, c.q_off), V3(0, 1, 0));
+    L.q1 = fk_axis_angle(L.a1, jq[1]);
+    L.a2 = fk_qrot(fk_qmul(L.q1, fk_qmul(L.q0, c.q_off)), V3(0, 0, 1));
+    L.q2 = fk_axis_angle(L.a2, jq[2]);
+    L.q_jc = fk_qmul(L.q2, fk_qmul(L.q1, L.q0));
+    const float j0 = jqd[0], j1 = jqd[1], j2 = jqd[2];
+    L.w_jc = fk_pin(V3(__builtin_fmaf(L.a2.x, j2, __builtin_fmaf(L.a0.x, j0, L.a1.x * j1)), __builtin_fmaf(L.a2.y, j2, __builtin_fmaf(L.a0.y, j0, L.a1.y * j1)),
+                       __builtin_fmaf(L.a2.z, j2, __builtin_fmaf(L.a0.z, j0, L.a1.z * j1))));
   }
 }
 
@@ -263,14 +291,14 @@ PD_DEV BodyState fk_joint(const BodyConst &c, const float *jq, const float *jqd,
   }
   FkLocals L;
   fk_joint_local<JT>(c, jq, jqd, L);
-  v3 p_wj = p_wp + qrot(q_wp, c.p_pj);
-  qt q_wj = qmul(q_wp, c.q_pj);
+  v3 p_wj = fk_pin(p_wp + fk_qrot(q_wp, c.p_pj));
+  qt q_wj = fk_qmul(q_wp, c.q_pj);
   BodyState s;
-  s.p = p_wj + qrot(q_wj, L.p_jc);
-  s.r = qmul(q_wj, L.q_jc);
-  v3 ang = qrot(q_wj, L.w_jc), lin = qrot(q_wj, L.v_jc);
-  s.w = w_wp + ang;
-  s.v = v_wp + (lin + cross(ang, c.com));
+  s.p = fk_pin(p_wj + fk_qrot(q_wj, L.p_jc));
+  s.r = fk_qmul(q_wj, L.q_jc);
+  v3 ang = fk_qrot(q_wj, L.w_jc), lin = fk_qrot(q_wj, L.v_jc);
+  s.w = fk_pin(w_wp + ang);
+  s.v = fk_pin(v_wp + fk_pin(lin + fk_cross(ang, c.com)));
   return s;
 }
 
@@ -1072,7 +1100,7 @@ PD_DEV BodyState integrate_fwd(const PdDevModel &m, const BodyConst &c, const Bo
                (clamp_pass(v1.y, -10.0f, 10.0f) == 0.0f ? 16u : 0u) | (clamp_pass(v1.z, -10.0f, 10.0f) == 0.0f ? 32u : 0u);
   }
   rotm(r1, R1);
-  rc_out = mat_vec(R1, c.com);
+  rc_out = rot_com(R1, c.com);  // (pinned: state 0 of a resumed launch forms the same bits from the stored quaternion)
   o.r = r1; o.p = x1 - rc_out;                                  // :90
   return o;
 }

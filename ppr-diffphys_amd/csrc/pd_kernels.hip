@@ -1181,7 +1181,7 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
       if (a.state0) s = load_state0(a.state0, idx);
       else s = fk_joint<JT>(c, a.q_init + (size_t)ec * m.nq + c.qstart, a.qd_init + (size_t)ec * m.nqd + c.qdstart, rec);
       rotm(s.r, Rm);
-      rc = mat_vec(Rm, c.com);
+      rc = rot_com(Rm, c.com);
       float4 cv = stage_record(rec, cull, b, s, rc, Rm);
       margin = sink_margin<JT, SPEC_STEPS>(m, c, s, a.dt);
       if (CULLW) margin98_n = c.sphere.w >= 0.0f ? 0.98f * margin : __builtin_inff();

@@ -292,6 +292,16 @@ PD_DEV void rotm_adj(qt q, const float *A, qt &adj_q) {
 PD_DEV v3 mat_vec(const float *M, v3 a) {
   return V3(M[0] * a.x + M[1] * a.y + M[2] * a.z, M[3] * a.x + M[4] * a.y + M[5] * a.z, M[6] * a.x + M[7] * a.y + M[8] * a.z);
 }
+// M com: the rotated centre-of-mass offset a forward rollout carries from step to step beside its state (integrate_fwd hands the new
+// state's on) and forms anew for state 0 of a launch.  Pinned like rot_row1: left to -ffp-contract=fast the two sites fused the three
+// products in different orders, and a launch RESUMED from a frame's rows then differed from the single launch by an ulp in every body whose
+// com has a non-zero x -- none of the shipped robots', every generated one's (tests/test_gpu_rollout_generated.py).  The order is the one
+// the compiler gives mat_vec on its own, so a com with x = 0 keeps its bits.
+PD_DEV v3 rot_com(const float *M, v3 a) {
+#pragma clang fp contract(off)
+  return V3(__builtin_fmaf(M[2], a.z, __builtin_fmaf(M[0], a.x, M[1] * a.y)), __builtin_fmaf(M[5], a.z, __builtin_fmaf(M[3], a.x, M[4] * a.y)),
+            __builtin_fmaf(M[8], a.z, __builtin_fmaf(M[6], a.x, M[7] * a.y)));
+}
 PD_DEV v3 matT_vec(const float *M, v3 a) {
   return V3(M[0] * a.x + M[3] * a.y + M[6] * a.z, M[1] * a.x + M[4] * a.y + M[7] * a.z, M[2] * a.x + M[5] * a.y + M[8] * a.z);
 }
