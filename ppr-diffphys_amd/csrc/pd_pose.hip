@@ -13,6 +13,7 @@
 //
 // Conventions (same as diffphys_amd/geom_utils.py): 7-vector = (p, q) with the quaternion's real part LAST; 6-vector =
 // (p, axis-angle); matrices row-major; quaternion_to_matrix divides by |q|^2 (mocap quaternions arrive un-normalised).
+#include <cstdio>
 #include <hip/hip_runtime.h>
 #include "../../include/ppr_diffphys.h"
 #include "pd_device.h"  // PD_POSE_GROUND_WRENCH: the rollout kernels' own per-candidate contact code (contact_point_fwd / _adj / _adj_materials);
@@ -431,6 +432,18 @@ __global__ __launch_bounds__(256) void k_ground_wrench_vjp(int n, int nb, const 
 // barrier, adds its children's slots to its own-side adjoint in the table's child order (a parent gathers its
 // children's in fixed order).  No atomics: the same bits on every run.  Joint table: include/ppr_diffphys.h (hip_backend.joint_table).
 enum { JC_HEAD = 4, JC_BODY = 24, JC_MAXCH = 8, JC_MAXNB = 256 };
+// Whole state sets per workgroup, a lane per body (k_joint_coords_vjp and the two centroidal kernels; nb <= 256): lane -> the set's index
+// in the workgroup and in the launch, the body inside the set.  in_set: the lane belongs to one of the 256 / nb sets the workgroup
+// places (the lanes past them idle); active: that set exists.
+struct SetLane { int set_l, body; long long set; bool in_set, active; };
+__device__ __forceinline__ SetLane set_lane(int nsets, int nb) {
+  SetLane L;
+  const int per_wg = 256 / nb;
+  L.set_l = (int)threadIdx.x / nb; L.body = (int)threadIdx.x - L.set_l * nb;
+  L.set = (long long)blockIdx.x * per_wg + L.set_l;
+  L.in_set = L.set_l < per_wg; L.active = L.in_set && L.set < nsets;
+  return L;
+}
 struct JcJoint {  // what the forward pass and the adjoint share
   int type, parent, qs, qds;
   v3 p_pj, axis, com;
@@ -523,10 +536,10 @@ __global__ __launch_bounds__(256) void k_joint_coords_fwd(int n, int nb, const f
 __global__ __launch_bounds__(256) void k_joint_coords_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ state,
                                                           const float *__restrict__ g_out, float *__restrict__ g_b) {
   __shared__ float slot[256 * PD_ADJ];  // lane -> the parent-side adjoint of its joint (odd stride: distinct banks)
-  const int per_wg = 256 / nb;           // whole state sets per workgroup
-  const int set_l = (int)threadIdx.x / nb, body = (int)threadIdx.x - set_l * nb;
-  const long long set = (long long)blockIdx.x * per_wg + set_l;
-  const bool active = set_l < per_wg && set < nsets;
+  const SetLane L = set_lane(nsets, nb);
+  const int set_l = L.set_l, body = L.body;
+  const long long set = L.set;
+  const bool active = L.active;
   const int nq = (int)tab[1], nqd = (int)tab[2];
   const bool generalized = tab[3] != 0.0f;
   BodyAdj own = adj_zero(), par = adj_zero();
@@ -672,10 +685,10 @@ __device__ __forceinline__ CtTotals ct_stage1(float *s1, int nb, int set_l, int 
 __global__ __launch_bounds__(256) void k_centroidal_fwd(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
                                                         float *__restrict__ out) {
   __shared__ float s1[256 * CT_S1], s2[256 * CT_S2];
-  const int per_wg = 256 / nb;  // whole state sets per workgroup
-  const int set_l = (int)threadIdx.x / nb, body = (int)threadIdx.x - set_l * nb;
-  const long long set = (long long)blockIdx.x * per_wg + set_l;
-  const bool in_set = set_l < per_wg, active = in_set && set < nsets;
+  const SetLane L = set_lane(nsets, nb);
+  const int set_l = L.set_l, body = L.body;
+  const long long set = L.set;
+  const bool in_set = L.in_set, active = L.active;
   if ((int)tab[0] != nb) {  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
     if (active && body == 0)
       for (int k = 0; k < CT_OUT; ++k) out[(size_t)set * CT_OUT + k] = 0.0f;
@@ -712,10 +725,10 @@ __global__ __launch_bounds__(256) void k_centroidal_fwd(int nsets, int nb, const
 __global__ __launch_bounds__(256) void k_centroidal_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
                                                         const float *__restrict__ g_out, float *__restrict__ g_b) {
   __shared__ float s1[256 * CT_S1];
-  const int per_wg = 256 / nb;
-  const int set_l = (int)threadIdx.x / nb, body = (int)threadIdx.x - set_l * nb;
-  const long long set = (long long)blockIdx.x * per_wg + set_l;
-  const bool in_set = set_l < per_wg, active = in_set && set < nsets;
+  const SetLane L = set_lane(nsets, nb);
+  const int set_l = L.set_l, body = L.body;
+  const long long set = L.set;
+  const bool in_set = L.in_set, active = L.active;
   float *dst = g_b + ((size_t)set * nb + body) * CT_ROW;  // (formed, not touched, by an inactive lane)
   if ((int)tab[0] != nb) {
     if (active)
@@ -769,62 +782,54 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
   return 2;
 }
 
-// a = the contact table, a_bcast = nb (the group size g: element i is body i % g of state set i / g), b = state rows [n][13]
-int launch_ground_wrench(int n, const float *tab, int nb, const float *state, float *out, const float *g_out, float *g_a, float *g_b,
-                         hipStream_t st) {
+// The tabled ops: a = the op's table, a_bcast = nb (the group size g: element i is body i % g of state set i / g), b = rows [n][13]
+// ([n][23] = (state, mass, inertia) for the centroidal op).  One launcher serves them; what differs per op is a row of TABLED:
+//   ground wrench      out / g_out [n][6], g_a [n][nmat][4]; any nb
+//   joint coordinates  out / g_out [n / nb][nq + nqd]; no g_a
+//   centroidal         out / g_out [n / nb][16], g_b [n][23]; no g_a
+enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
+struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
+constexpr TabledOp TABLED[] = {
+    {PD_POSE_GROUND_WRENCH, "PD_POSE_GROUND_WRENCH", "contact", 0, true, GEO_WAVE, GEO_WAVE},
+    {PD_POSE_JOINT_COORDS, "PD_POSE_JOINT_COORDS", "joint", JC_MAXNB, false, GEO_LANE, GEO_SETS},
+    {PD_POSE_CENTROIDAL, "PD_POSE_CENTROIDAL", "mass", CT_MAXNB, false, GEO_SETS, GEO_SETS},
+};
+
+template <class... A>
+int refuse(const char *fmt, A... args) {  // pd_set_error of a formatted message
+  char msg[160];
+  snprintf(msg, sizeof msg, fmt, args...);
+  return pd_set_error(msg);
+}
+
+int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const float *rows, float *out, const float *g_out, float *g_a,
+                  float *g_b, hipStream_t st) {
   if (nb <= 0 || n % nb != 0)  // before the n == 0 return, like the projection ops: a bad group size is refused at every n
     return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
-  if (n == 0) return 0;
-  if (!tab || !state) return pd_set_error("pd_pose_op: a NULL operand");
-  if ((size_t)tab & 15) return pd_set_error("pd_pose_op: the contact table a_dev must be 16-byte aligned");
-  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-  if (out)
-    hipLaunchKernelGGL(k_ground_wrench_fwd, grid, block, 0, st, n, nb, tab, state, out);
-  else
-    hipLaunchKernelGGL(k_ground_wrench_vjp, grid, block, 0, st, n, nb, tab, state, g_out, g_a, g_b);
-  if (hipGetLastError() == hipSuccess) return 0;
-  pd_set_error("pd_pose_op: the kernel launch failed");
-  return 2;
-}
-
-// a = the joint table, a_bcast = nb (the group size, as for the ground wrench), b = state rows [n][13]; out / g_out [n / nb][nq + nqd]
-int launch_joint_coords(int n, const float *tab, int nb, const float *state, float *out, const float *g_out, float *g_a, float *g_b,
-                        hipStream_t st) {
-  if (nb <= 0 || n % nb != 0)  // before the n == 0 return: a bad group size is refused at every n
-    return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
-  if (nb > JC_MAXNB) return pd_set_error("pd_pose_op: PD_POSE_JOINT_COORDS serves at most 256 bodies per state set");
-  if (g_a) return pd_set_error("pd_pose_op_vjp: PD_POSE_JOINT_COORDS has no gradient for its joint table -- g_a_dev must be NULL");
-  if (n == 0) return 0;
-  if (!tab || !state) return pd_set_error("pd_pose_op: a NULL operand");
-  if ((size_t)tab & 15) return pd_set_error("pd_pose_op: the joint table a_dev must be 16-byte aligned");
-  if (out) {
-    hipLaunchKernelGGL(k_joint_coords_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, nb, tab, state, out);
-  } else {
-    const int nsets = n / nb, per_wg = 256 / nb;
-    hipLaunchKernelGGL(k_joint_coords_vjp, dim3((unsigned)((nsets + per_wg - 1) / per_wg)), dim3(256), 0, st, nsets, nb, tab, state, g_out, g_b);
-  }
-  if (hipGetLastError() == hipSuccess) return 0;
-  pd_set_error("pd_pose_op: the kernel launch failed");
-  return 2;
-}
-
-// a = the mass table, a_bcast = nb (the group size, as for the two ops above), b = rows [n][23] = (state, mass, inertia);
-// out / g_out [n / nb][16], g_b [n][23]
-int launch_centroidal(int n, const float *tab, int nb, const float *rows, float *out, const float *g_out, float *g_a, float *g_b,
-                      hipStream_t st) {
-  if (nb <= 0 || n % nb != 0)  // before the n == 0 return: a bad group size is refused at every n
-    return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
-  if (nb > CT_MAXNB) return pd_set_error("pd_pose_op: PD_POSE_CENTROIDAL serves at most 256 bodies per state set");
-  if (g_a) return pd_set_error("pd_pose_op_vjp: PD_POSE_CENTROIDAL has no gradient for its mass table -- g_a_dev must be NULL");
+  if (T.max_nb && nb > T.max_nb) return refuse("pd_pose_op: %s serves at most %d bodies per state set", T.name, T.max_nb);
+  if (g_a && !T.has_g_a)  // before the n == 0 return, too
+    return refuse("pd_pose_op_vjp: %s has no gradient for its %s table -- g_a_dev must be NULL", T.name, T.table);
   if (n == 0) return 0;
   if (!tab || !rows) return pd_set_error("pd_pose_op: a NULL operand");
-  if ((size_t)tab & 15) return pd_set_error("pd_pose_op: the mass table a_dev must be 16-byte aligned");
-  const int nsets = n / nb, per_wg = 256 / nb;
-  const dim3 grid((unsigned)((nsets + per_wg - 1) / per_wg)), block(256);
-  if (out)
-    hipLaunchKernelGGL(k_centroidal_fwd, grid, block, 0, st, nsets, nb, tab, rows, out);
-  else
-    hipLaunchKernelGGL(k_centroidal_vjp, grid, block, 0, st, nsets, nb, tab, rows, g_out, g_b);
+  if ((size_t)tab & 15) return refuse("pd_pose_op: the %s table a_dev must be 16-byte aligned", T.table);
+  // What the kernel counts (its first argument) and how many of them a workgroup of 256 lanes serves: elements, or whole state sets
+  const Geometry geo = out ? T.fwd : T.vjp;
+  const int count = geo == GEO_SETS ? n / nb : n;
+  const int per_wg = geo == GEO_WAVE ? 4 : geo == GEO_LANE ? 256 : 256 / nb;
+  const dim3 grid((unsigned)((count + per_wg - 1) / per_wg)), block(256);
+  switch (T.op) {
+    case PD_POSE_GROUND_WRENCH:
+      if (out) hipLaunchKernelGGL(k_ground_wrench_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_ground_wrench_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_a, g_b);
+      break;
+    case PD_POSE_JOINT_COORDS:
+      if (out) hipLaunchKernelGGL(k_joint_coords_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_joint_coords_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
+    default:
+      if (out) hipLaunchKernelGGL(k_centroidal_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_centroidal_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+  }
   if (hipGetLastError() == hipSuccess) return 0;
   pd_set_error("pd_pose_op: the kernel launch failed");
   return 2;
@@ -833,9 +838,8 @@ int launch_centroidal(int n, const float *tab, int nb, const float *rows, float 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
   if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL))  // (codes 7 and 8 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
-  if (op == PD_POSE_CENTROIDAL) return launch_centroidal(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
-  if (op == PD_POSE_GROUND_WRENCH) return launch_ground_wrench(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
-  if (op == PD_POSE_JOINT_COORDS) return launch_joint_coords(n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
+  for (const TabledOp &T : TABLED)
+    if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
   const bool project = op >= PD_POSE_PROJECT;
   if (project && (a_bcast < 0 || (a_bcast > 0 && n % a_bcast != 0)))  // before the n == 0 return: a bad group size is refused at every n
     return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the camera group size a_broadcast");

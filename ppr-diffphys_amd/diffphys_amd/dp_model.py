@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import hip_backend
+from .dp_utils import _need_gpu, _state_rows
 
 
 def convert_ppr_warp(tensor):
@@ -116,17 +117,14 @@ class InverseKinematics(torch.autograd.Function):
     @staticmethod
     def forward(ctx, body_q, body_qd, env, rates="generalized"):
         nb = int(env.nb)
-        for t in (body_q, body_qd):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-                raise TypeError("InverseKinematics needs float32 GPU tensors (the product path has no CPU fallback); got %s" % (
-                    "%s on %s" % (t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+        _need_gpu("InverseKinematics", body_q, body_qd)
         if not (body_q.dim() == 4 and tuple(body_q.shape[2:]) == (nb, 7) and body_qd.dim() == 4 and tuple(body_qd.shape[2:]) == (nb, 6)
                 and body_q.shape[:2] == body_qd.shape[:2]):
             raise ValueError("InverseKinematics: body_q [bs, T, %d, 7] and body_qd [bs, T, %d, 6]; got %s and %s" % (
                 nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
         table = hip_backend.env_joint_table(env, body_q.device, rates)
         bs, T = int(body_q.shape[0]), int(body_q.shape[1])
-        state = torch.cat([body_q.detach().permute(1, 0, 2, 3).reshape(-1, 7), body_qd.detach().permute(1, 0, 2, 3).reshape(-1, 6)], dim=1)
+        state = _state_rows(body_q.permute(1, 0, 2, 3), body_qd.permute(1, 0, 2, 3))
         ctx.table, ctx.nb, ctx.shape = table, nb, (bs, T)
         ctx.save_for_backward(state)
         q, qd = hip_backend.joint_coords(table, nb, state)
@@ -154,10 +152,7 @@ class Centroidal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, body_q, body_qd, body_mass, body_inertia, env):
         nb = int(env.nb)
-        for t in (body_q, body_qd, body_mass, body_inertia):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-                raise TypeError("Centroidal needs float32 GPU tensors (the product path has no CPU fallback); got %s" % (
-                    "%s on %s" % (t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+        _need_gpu("Centroidal", body_q, body_qd, body_mass, body_inertia)
         lead = tuple(body_q.shape[:-2])
         if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_qd.shape) == lead + (nb, 6)
                 and tuple(body_mass.shape) == lead + (nb,) and tuple(body_inertia.shape) == lead + (nb, 3, 3)):
@@ -165,8 +160,7 @@ class Centroidal(torch.autograd.Function):
                              "with equal leading shapes; got %s, %s, %s and %s" % (
                                  nb, nb, nb, nb, tuple(body_q.shape), tuple(body_qd.shape), tuple(body_mass.shape), tuple(body_inertia.shape)))
         table = hip_backend.env_mass_table(env, body_q.device)
-        rows = torch.cat([body_q.detach().reshape(-1, 7), body_qd.detach().reshape(-1, 6), body_mass.detach().reshape(-1, 1),
-                          body_inertia.detach().reshape(-1, 9)], dim=1)
+        rows = _state_rows(body_q, body_qd, body_mass, body_inertia)
         ctx.table, ctx.nb, ctx.lead = table, nb, lead
         ctx.save_for_backward(rows)
         return hip_backend.centroidal(table, nb, rows).view(lead + (16,))

@@ -202,6 +202,21 @@ def reproj_loss(sim_2d, target_2d, rtk):
     return (sim_2d - target_2d).norm(2, -1).mean(-1) / rtk[..., 3, 0]
 
 
+def _check_states(what, body_q, body_qd, nb):
+    """body_q (..., nb, 7) and body_qd (..., nb, 6) with equal leading shapes, or a ValueError -> that leading shape."""
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
+            and body_q.shape[:-2] == body_qd.shape[:-2]):
+        raise ValueError("%s: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
+            what, nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+    return tuple(body_q.shape[:-2])
+
+
+def _state_rows(body_q, body_qd, *more):
+    """The operand rows of a state op, detached: [n, 13] = (p, q xyzw, w, v) from body_q (..., 7) and body_qd (..., 6), in their order;
+    ``more`` = (body_mass (...), body_inertia (..., 3, 3)) appends the ten columns of the centroidal op's [n, 23] rows."""
+    return torch.cat([t.detach().reshape(-1, w) for t, w in zip((body_q, body_qd) + more, (7, 6, 1, 9))], dim=1)
+
+
 class _GroundWrenchHip(torch.autograd.Function):
     """The ground-contact wrench of body states as ONE HIP launch, its vector-Jacobian product as one more (``pd_pose_op`` /
     ``pd_pose_op_vjp``, PD_POSE_GROUND_WRENCH), the material gradient summed by ``pd_colsum``."""
@@ -212,10 +227,10 @@ class _GroundWrenchHip(torch.autograd.Function):
 
         nb = int(env.nb)
         table = hip_backend.env_contact_table(env, body_q.device)
-        nmat = hip_backend._table_dims(table)[2]
+        nmat = hip_backend._table_tag(table)[1][2]
         if materials is not None:
             table = hip_backend.with_materials(table, nmat, materials)
-        state = torch.cat([body_q.detach().reshape(-1, 7), body_qd.detach().reshape(-1, 6)], dim=1)
+        state = _state_rows(body_q, body_qd)
         ctx.table, ctx.nb, ctx.nmat = table, nb, nmat
         ctx.save_for_backward(state)
         return hip_backend.ground_wrench(table, nb, state).view(body_q.shape[:-1] + (6,))
@@ -245,11 +260,7 @@ def ground_wrench(body_q, body_qd, env, materials=None):
     materials=None: the env's materials, no material gradient.  The differentiable ground-reaction force of a rollout frame is
     ``res_f[frame2step[f]] + ground_wrench(wp_pos[f], wp_vel[f], env)``.  float32 GPU tensors only."""
     _need_gpu("ground_wrench", body_q, body_qd, *(() if materials is None else (materials,)))
-    nb = int(env.nb)
-    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
-            and body_q.shape[:-2] == body_qd.shape[:-2]):
-        raise ValueError("ground_wrench: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
-            nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+    _check_states("ground_wrench", body_q, body_qd, int(env.nb))
     return _GroundWrenchHip.apply(body_q, body_qd, materials, env)
 
 
@@ -264,11 +275,7 @@ def joint_coords(body_q, body_qd, env, rates="generalized"):
 
     _need_gpu("joint_coords", body_q, body_qd)
     nb = int(env.nb)
-    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
-            and body_q.shape[:-2] == body_qd.shape[:-2]):
-        raise ValueError("joint_coords: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
-            nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
-    lead = tuple(body_q.shape[:-2])
+    lead = _check_states("joint_coords", body_q, body_qd, nb)
     q, qd = InverseKinematics.apply(body_q.reshape(-1, 1, nb, 7), body_qd.reshape(-1, 1, nb, 6), env, rates)
     return q.reshape(lead + (q.shape[-1],)), qd.reshape(lead + (qd.shape[-1],))
 
@@ -296,11 +303,8 @@ def centroidal(body_q, body_qd, body_mass, body_inertia, env):
 
     _need_gpu("centroidal", body_q, body_qd, body_mass, body_inertia)
     nb = int(env.nb)
-    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7) and tuple(body_qd.shape[-2:]) == (nb, 6)
-            and body_q.shape[:-2] == body_qd.shape[:-2]):
-        raise ValueError("centroidal: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
-            nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
-    lead = tuple(body_q.shape[:-2])
+    lead = _check_states("centroidal", body_q, body_qd, nb)
+
     def fits(t, shape):
         try:
             return tuple(torch.broadcast_shapes(tuple(t.shape), shape)) == shape

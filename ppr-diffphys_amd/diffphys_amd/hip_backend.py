@@ -722,6 +722,68 @@ def pose_op_vjp(op, a, b, g_out, need_a=True, need_b=True):
     return g_a, g_b
 
 
+# ---- The tabled state ops (ground wrench, joint coordinates, centroidal): each takes a device table compiled from a template.  They share
+# one tag on the table tensor, one per-model cache, one argument check and one gradient check; what differs is passed in.
+_ROWS = {13: ("state", "(p, q xyzw, w, v)"), 23: ("rows", "(p, q xyzw, w, v, m, I row-major)")}   # operand row width -> its name, its columns
+
+
+def _tagged(table, kind, dims):
+    """Marks a table tensor with what it is: its kind ("contact", "joint" or "mass") and its dimensions, which the library cannot read
+    back from a device buffer."""
+    table._pd_table = (kind, dims)
+    return table
+
+
+def _table_tag(table):
+    """-> (kind, dims) of a tensor contact_table / joint_table / mass_table made, or None."""
+    return getattr(table, "_pd_table", None)
+
+
+def _env_table(env, key, build):
+    """A device table of a :class:`diffphys_amd.sim.Model`, cached on the model under ``key`` = (kind, device, ...) and built from its
+    template on first use.  The model drops the cache with its device model, whenever the template changes (collide(),
+    set_shape_materials())."""
+    if env._contact_table is None:
+        env._contact_table = {}
+    if key not in env._contact_table:
+        env._contact_table[key] = build(env.template())
+    return env._contact_table[key]
+
+
+def _state_op_check(op, kind, width, table, nb, rows, bare=False):
+    """The argument check of the six state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
+    device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
+    tag = _table_tag(table)
+    if tag is None and not bare:
+        raise ValueError("%s: the table must come from hip_backend.%s_table (it carries its dimensions)" % (op, kind))
+    if tag is not None and tag[0] != kind:
+        raise ValueError("%s: a %s table; the op takes one from hip_backend.%s_table" % (op, tag[0], kind))
+    name, columns = _ROWS[width]
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != width:
+        raise ValueError("%s: %s must be [n, %d] = %s rows; got %s" % (op, name, width, columns, tuple(getattr(rows, "shape", ()))))
+    n = int(rows.shape[0])
+    if nb < 1 or n % nb:
+        raise ValueError("%s: %d %s rows are no multiple of nb = %d" % (op, n, name, nb))
+    dims = None if tag is None else tag[1]
+    if dims is not None and dims[0] != nb:
+        raise ValueError("%s: the %s table is one of nb = %d; the call says nb = %d" % (op, kind, dims[0], nb))
+    _dev(table, "table")
+    if n:
+        _dev(rows, name)
+        if rows.device != table.device:
+            raise ValueError("%s: %s on %s, the table on %s" % (op, name, rows.device, table.device))
+    return n, dims
+
+
+def _grad_check(op, name, g, r, c):
+    """An upstream gradient of a VJP entry: ``name`` must be a [r, c] float32 GPU tensor."""
+    if not torch.is_tensor(g) or tuple(g.shape) != (r, c):
+        raise ValueError("%s: %s must be a [%d, %d] tensor; got %s" % (op, name, r, c, tuple(getattr(g, "shape", ()))))
+    if not (g.is_cuda and g.dtype is torch.float32):
+        raise TypeError("%s: %s must be a float32 GPU tensor; got %s on %s" % (op, name, g.dtype, g.device))
+
+
 POSE_GROUND_WRENCH = 5
 _GW_HEAD, _GW_BODY = 4, 12   # floats of the contact table's header / per body (include/ppr_diffphys.h, PD_POSE_GROUND_WRENCH)
 
@@ -781,10 +843,6 @@ def contact_table_host(tpl):
     return t
 
 
-def _table_dims(table):
-    return getattr(table, "_pd_contact_dims", None)
-
-
 def with_materials(table, nmat, materials):
     """A copy of a device contact table with its material rows replaced by ``materials`` [nmat, 4] (a float32 GPU tensor; a device copy,
     no host round trip)."""
@@ -797,7 +855,7 @@ def with_materials(table, nmat, materials):
         raise TypeError("contact_table: materials must be a float32 GPU tensor; got %s on %s" % (m.dtype, m.device))
     out = table.clone()
     out[_GW_HEAD: _GW_HEAD + 4 * nmat].copy_(m.reshape(-1))
-    out._pd_contact_dims = _table_dims(table)
+    out._pd_table = _table_tag(table)
     return out
 
 
@@ -809,30 +867,15 @@ def contact_table(tpl, materials=None, device="cuda"):
     if materials is not None and not (torch.is_tensor(materials) and tuple(materials.shape) == (nmat, 4)):
         raise ValueError("contact_table: materials must be a [%d, 4] tensor (ke, kd, kf, mu per material); got %s" % (
             nmat, tuple(getattr(materials, "shape", ()))))
-    t = torch.from_numpy(contact_table_host(tpl)).to(device)
-    t._pd_contact_dims = (int(tpl["nb"]), len(np.asarray(tpl["contact_body"]).reshape(-1)), nmat)
+    t = _tagged(torch.from_numpy(contact_table_host(tpl)).to(device), "contact",
+                (int(tpl["nb"]), len(np.asarray(tpl["contact_body"]).reshape(-1)), nmat))
     return t if materials is None else with_materials(t, nmat, materials)
-
-
-def _gw_check(table, nb, nmat, state):
-    """Shapes of a ground-wrench call -> n.  The table's own dimensions travel with tensors contact_table made: a table of another model
-    is refused here where that can be seen (the library cannot validate a device buffer)."""
-    if state.dim() != 2 or state.shape[1] != 13:
-        raise ValueError("ground_wrench: state must be [n, 13] = (p, q xyzw, w, v) rows; got %s" % (tuple(state.shape),))
-    n = int(state.shape[0])
-    if nb < 1 or n % nb:
-        raise ValueError("ground_wrench: %d state rows are no multiple of nb = %d" % (n, nb))
-    dims = _table_dims(table)
-    if dims is not None and (dims[0] != nb or (nmat is not None and dims[2] != nmat)):
-        raise ValueError("ground_wrench: the contact table is one of nb = %d, nmat = %d; the call says nb = %d, nmat = %s" % (
-            dims[0], dims[2], nb, nmat))
-    return n
 
 
 def ground_wrench(table, nb, state):
     """``pd_pose_op`` PD_POSE_GROUND_WRENCH: state [n, 13] = (p, q xyzw, w, v) rows, n a multiple of nb (row i is body i % nb) -> [n, 6],
     each body's ground-contact contribution to body_f (torque first), the rollout kernels' arithmetic candidate by candidate."""
-    n = _gw_check(table, int(nb), None, state)
+    n, _ = _state_op_check("ground_wrench", "contact", 13, table, int(nb), state, bare=True)
     out = torch.empty(n, 6, device=state.device, dtype=torch.float32)
     _check(lib().pd_pose_op(POSE_GROUND_WRENCH, n, _dev(table, "table"), int(nb), _ptr(state, "state"), _ptr(out, "out"), _stream()))
     return out
@@ -841,7 +884,9 @@ def ground_wrench(table, nb, state):
 def ground_wrench_vjp(table, nb, nmat, state, g_out, need_state=True, need_materials=True):
     """``pd_pose_op_vjp`` PD_POSE_GROUND_WRENCH -> (g_state [n, 13] raw partials or None, g_materials [n, nmat, 4] PER ELEMENT or None --
     the caller sums, ``colsum(g.reshape(n, -1))``)."""
-    n = _gw_check(table, int(nb), int(nmat), state)
+    n, dims = _state_op_check("ground_wrench_vjp", "contact", 13, table, int(nb), state, bare=True)
+    if dims is not None and dims[2] != int(nmat):
+        raise ValueError("ground_wrench_vjp: the contact table is one of nmat = %d; the call says nmat = %d" % (dims[2], int(nmat)))
     if not (need_state or need_materials):
         return None, None
     g_b = torch.empty(n, 13, device=state.device, dtype=torch.float32) if need_state else None
@@ -852,15 +897,8 @@ def ground_wrench_vjp(table, nb, nmat, state, g_out, need_state=True, need_mater
 
 
 def env_contact_table(env, device):
-    """The contact table of a :class:`diffphys_amd.sim.Model`, cached on the model per device (dropped by collide() and
-    set_shape_materials())."""
-    cache = getattr(env, "_contact_table", None)
-    if cache is None:
-        cache = env._contact_table = {}
-    key = str(torch.device(device))
-    if key not in cache:
-        cache[key] = contact_table(env.template(), device=device)
-    return cache[key]
+    """The contact table of a :class:`diffphys_amd.sim.Model`, cached on the model per device."""
+    return _env_table(env, ("contact", str(torch.device(device))), lambda tpl: contact_table(tpl, device=device))
 
 
 POSE_JOINT_COORDS = 6
@@ -922,56 +960,23 @@ def joint_table_host(tpl, rates="generalized"):
     return t
 
 
-def _joint_dims(table):
-    return getattr(table, "_pd_joint_dims", None)
-
-
 def joint_table(tpl, rates="generalized", device="cuda"):
     """The joint table operand of ``joint_coords`` for a template dict, as a float32 tensor on ``device``; its dimensions (nb, nq, nqd)
     travel with the tensor."""
-    t = torch.from_numpy(joint_table_host(tpl, rates)).to(device)
-    t._pd_joint_dims = (int(tpl["nb"]), int(tpl["nq"]), int(tpl["nqd"]))
-    return t
+    return _tagged(torch.from_numpy(joint_table_host(tpl, rates)).to(device), "joint", (int(tpl["nb"]), int(tpl["nq"]), int(tpl["nqd"])))
 
 
 def env_joint_table(env, device, rates="generalized"):
     """The joint table of a :class:`diffphys_amd.sim.Model`, cached on the model per (device, rates)."""
     _jc_rate_mode(rates)
-    cache = getattr(env, "_joint_table", None)
-    if cache is None:
-        cache = env._joint_table = {}
-    key = (str(torch.device(device)), rates)
-    if key not in cache:
-        cache[key] = joint_table(env.template(), rates, device)
-    return cache[key]
-
-
-def _jc_check(table, nb, state):
-    """Shapes of a joint-coordinates call -> (n, nq, nqd).  The dimensions come from the table tensor joint_table made (the library
-    cannot validate a device buffer, so a bare tensor is refused)."""
-    dims = _joint_dims(table)
-    if dims is None:
-        raise ValueError("joint_coords: the table must come from hip_backend.joint_table (it carries nb, nq and nqd)")
-    if state.dim() != 2 or state.shape[1] != 13:
-        raise ValueError("joint_coords: state must be [n, 13] = (p, q xyzw, w, v) rows; got %s" % (tuple(state.shape),))
-    n = int(state.shape[0])
-    if nb < 1 or n % nb:
-        raise ValueError("joint_coords: %d state rows are no multiple of nb = %d" % (n, nb))
-    if dims[0] != nb:
-        raise ValueError("joint_coords: the joint table is one of nb = %d; the call says nb = %d" % (dims[0], nb))
-    _dev(table, "table")
-    if n:
-        _dev(state, "state")
-        if state.device != table.device:
-            raise ValueError("joint_coords: state on %s, the table on %s" % (state.device, table.device))
-    return n, dims[1], dims[2]
+    return _env_table(env, ("joint", str(torch.device(device)), rates), lambda tpl: joint_table(tpl, rates, device))
 
 
 def joint_coords(table, nb, state):
     """``pd_pose_op`` PD_POSE_JOINT_COORDS: state [n, 13] = (p, q xyzw, w, v) rows, n a multiple of nb (row i is body i % nb of set
     i // nb) -> (joint_q [n / nb, nq], joint_qd [n / nb, nqd]), views of ONE [n / nb, nq + nqd] buffer -- the inverse of ``fk_forward``
     (rates as the table was built: "generalized" or "measured")."""
-    n, nq, nqd = _jc_check(table, int(nb), state)
+    n, (_, nq, nqd) = _state_op_check("joint_coords", "joint", 13, table, int(nb), state)
     out = torch.empty(n // int(nb), nq + nqd, device=state.device, dtype=torch.float32)
     _check(lib().pd_pose_op(POSE_JOINT_COORDS, n, _dev(table, "table"), int(nb), _ptr(state, "state"), _ptr(out, "out"), _stream()))
     return out[:, :nq], out[:, nq:]
@@ -980,13 +985,10 @@ def joint_coords(table, nb, state):
 def joint_coords_vjp(table, nb, state, g_q, g_qd):
     """``pd_pose_op_vjp`` PD_POSE_JOINT_COORDS: g_q [n / nb, nq], g_qd [n / nb, nqd] -> g_state [n, 13], the raw partials (quaternion
     entries not projected).  Fixed summation order: the same bits on every call."""
-    n, nq, nqd = _jc_check(table, int(nb), state)
+    n, (_, nq, nqd) = _state_op_check("joint_coords_vjp", "joint", 13, table, int(nb), state)
     sets = n // int(nb)
-    for g, w, name in ((g_q, nq, "g_q"), (g_qd, nqd, "g_qd")):
-        if not torch.is_tensor(g) or tuple(g.shape) != (sets, w):
-            raise ValueError("joint_coords_vjp: %s must be a [%d, %d] tensor; got %s" % (name, sets, w, tuple(getattr(g, "shape", ()))))
-        if not (g.is_cuda and g.dtype is torch.float32):
-            raise TypeError("joint_coords_vjp: %s must be a float32 GPU tensor; got %s on %s" % (name, g.dtype, g.device))
+    _grad_check("joint_coords_vjp", "g_q", g_q, sets, nq)
+    _grad_check("joint_coords_vjp", "g_qd", g_qd, sets, nqd)
     g_out = torch.cat([g_q, g_qd], dim=1)
     g_b = torch.empty(n, 13, device=state.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_JOINT_COORDS, n, _dev(table, "table"), int(nb), _ptr(state, "state"),
@@ -1017,55 +1019,21 @@ def mass_table_host(tpl):
     return t
 
 
-def _mass_dims(table):
-    return getattr(table, "_pd_mass_dims", None)
-
-
 def mass_table(tpl, device="cuda"):
     """The mass table operand of ``centroidal`` for a template dict, as a float32 tensor on ``device``; its nb travels with the tensor."""
-    t = torch.from_numpy(mass_table_host(tpl)).to(device)
-    t._pd_mass_dims = (int(tpl["nb"]),)
-    return t
+    return _tagged(torch.from_numpy(mass_table_host(tpl)).to(device), "mass", (int(tpl["nb"]),))
 
 
 def env_mass_table(env, device):
     """The mass table of a :class:`diffphys_amd.sim.Model`, cached on the model per device."""
-    cache = getattr(env, "_mass_table", None)
-    if cache is None:
-        cache = env._mass_table = {}
-    key = str(torch.device(device))
-    if key not in cache:
-        cache[key] = mass_table(env.template(), device)
-    return cache[key]
-
-
-def _ct_check(table, nb, rows):
-    """Shapes of a centroidal call -> n.  nb comes with the table tensor mass_table made (the library cannot validate a device buffer, so
-    a bare tensor is refused)."""
-    dims = _mass_dims(table)
-    if dims is None:
-        raise ValueError("centroidal: the table must come from hip_backend.mass_table (it carries nb)")
-    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != _CT_ROW:
-        raise ValueError("centroidal: rows must be [n, 23] = (p, q xyzw, w, v, m, I row-major) rows; got %s" % (
-            tuple(getattr(rows, "shape", ())),))
-    n = int(rows.shape[0])
-    if nb < 1 or n % nb:
-        raise ValueError("centroidal: %d rows are no multiple of nb = %d" % (n, nb))
-    if dims[0] != nb:
-        raise ValueError("centroidal: the mass table is one of nb = %d; the call says nb = %d" % (dims[0], nb))
-    _dev(table, "table")
-    if n:
-        _dev(rows, "rows")
-        if rows.device != table.device:
-            raise ValueError("centroidal: rows on %s, the table on %s" % (rows.device, table.device))
-    return n
+    return _env_table(env, ("mass", str(torch.device(device))), lambda tpl: mass_table(tpl, device))
 
 
 def centroidal(table, nb, rows):
     """``pd_pose_op`` PD_POSE_CENTROIDAL: rows [n, 23] = (p, q xyzw, w, v, m, I row-major) per body, n a multiple of nb (row i is body
     i % nb of set i // nb) -> [n / nb, 16] = (M, c, c_dot, P, L about c, T, V, 0) per state set.  Fixed summation order: a set's bits
     depend neither on the call nor on the other sets."""
-    n = _ct_check(table, int(nb), rows)
+    n, _ = _state_op_check("centroidal", "mass", _CT_ROW, table, int(nb), rows)
     out = torch.empty(n // int(nb), _CT_OUT, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op(POSE_CENTROIDAL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
     return out
@@ -1074,12 +1042,9 @@ def centroidal(table, nb, rows):
 def centroidal_vjp(table, nb, rows, g_out):
     """``pd_pose_op_vjp`` PD_POSE_CENTROIDAL: g_out [n / nb, 16] -> g_rows [n, 23], the raw partials with respect to the state, the mass
     and the nine inertia entries of every body."""
-    n = _ct_check(table, int(nb), rows)
+    n, _ = _state_op_check("centroidal_vjp", "mass", _CT_ROW, table, int(nb), rows)
     sets = n // int(nb)
-    if not torch.is_tensor(g_out) or tuple(g_out.shape) != (sets, _CT_OUT):
-        raise ValueError("centroidal_vjp: g_out must be a [%d, %d] tensor; got %s" % (sets, _CT_OUT, tuple(getattr(g_out, "shape", ()))))
-    if not (g_out.is_cuda and g_out.dtype is torch.float32):
-        raise TypeError("centroidal_vjp: g_out must be a float32 GPU tensor; got %s on %s" % (g_out.dtype, g_out.device))
+    _grad_check("centroidal_vjp", "g_out", g_out, sets, _CT_OUT)
     g_b = torch.empty(n, _CT_ROW, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_CENTROIDAL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", sets * _CT_OUT),
                                 None, _ptr(g_b, "g_b"), _stream()))

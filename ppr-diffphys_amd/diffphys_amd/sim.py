@@ -659,8 +659,13 @@ class Model:
         self.t_contact_dist = np.zeros(0, np.float32)
         self.t_contact_material = np.zeros(0, np.int32)
         self.contact_count = 0
-        self._handle = None  # device-side template, owned by diffphys_amd.hip_backend
-        self._contact_table = None  # device contact table(s) of the ground-wrench op, owned by diffphys_amd.hip_backend
+        self._drop_device()
+
+    def _drop_device(self):
+        """Drops everything diffphys_amd.hip_backend compiled from :meth:`template`: whatever changes the template calls this, and the
+        next use rebuilds."""
+        self._handle = None  # device-side template (hip_backend.device_model)
+        self._contact_table = None  # device tables of the state ops -- contact, joint and mass -- by kind and device (hip_backend._env_table)
 
     # -- Warp-compatible surface ----------------------------------------------
     def state(self, requires_grad=False):
@@ -698,12 +703,11 @@ class Model:
         self.t_contact_dist = np.asarray(dist, dtype=np.float32)
         self.t_contact_material = np.asarray(mat, dtype=np.int32)
         self.contact_count = len(body) * self.num_envs
-        self._handle = None
-        self._contact_table = None
+        self._drop_device()
 
     def set_shape_materials(self, values):
         """Replaces the ground-contact material rows (ke, kd, kf, mu) -- [nmat, 4], the shape of ``t_shape_materials`` -- on the host and
-        drops the cached device model and contact table: the next ``hip_backend.device_model(env)`` builds a new model
+        drops the cached device model and the state ops' tables: the next ``hip_backend.device_model(env)`` builds a new model
         (``pd_model_create``; the C ABI has no entry that re-binds materials in place).  A materials update therefore costs a model
         build -- an upload and a few allocations: fine once per iteration of an identification loop, not capturable in a graph."""
         v = np.ascontiguousarray(np.asarray(values, dtype=np.float32))
@@ -712,8 +716,7 @@ class Model:
         self.t_shape_materials = v.copy()
         if self._shapes is not None:
             self._shapes["materials"] = self.t_shape_materials
-        self._handle = None
-        self._contact_table = None
+        self._drop_device()
 
     # -- template export --------------------------------------------------------
     def template(self):
@@ -771,8 +774,7 @@ class Model:
             setattr(m, "t_" + k, np.ascontiguousarray(tpl[k]))
         m._shapes = None
         m.contact_count = len(m.t_contact_body) * m.num_envs
-        m._handle = None
-        m._contact_table = None
+        m._drop_device()
         return m
 
     # -- tiled views the reference's host code reads ---------------------------

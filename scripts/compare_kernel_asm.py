@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""Do two source trees compile pd_kernels.hip to the same gfx950 kernels?  (no GPU needed)
+"""Do two source trees compile pd_kernels.hip and pd_pose.hip to the same gfx950 kernels?  (no GPU needed)
 
   python scripts/compare_kernel_asm.py TREE_A TREE_B [--work DIR] [--jobs N]
 
-For each of the six kernel objects of the library (segment width 16 / 32 / 64 x PD_POLICY 0 / 1) the script takes the compile command of
-the tree's own Makefile (`make -n`), turns it into `-S --cuda-device-only` and compares the two assembly files as MULTISETS of kernels:
+For each of the six rollout kernel objects of the library (segment width 16 / 32 / 64 x PD_POLICY 0 / 1) and for pd_pose (the pose and
+state ops) the script takes the compile command of the tree's own Makefile (`make -n`), turns it into `-S --cuda-device-only` and
+compares the two assembly files as MULTISETS of kernels:
   * the text of each kernel's body, with its own symbol name and the function index of local labels (.LBB<i>_<j>, .Lfunc_end<i>) taken
     out -- mangled names change when a template parameter goes, the instructions must not;
   * its code-object metadata: VGPR / AGPR / SGPR counts, both spill counts, static LDS, scratch size, max workgroup size.
-Equal multisets: no instantiation gained or lost, none compiled differently.  Exit status 0 when all six objects agree, 1 otherwise (the
+Equal multisets: no instantiation gained or lost, none compiled differently.  Exit status 0 when all seven objects agree, 1 otherwise (the
 kernels without a partner are listed by name).  Assembly is kept under --work (default: a temporary directory) and reused when neither
 the sources nor the command changed, so a second run against the same baseline compiles one side only.
 """
@@ -23,7 +24,7 @@ import subprocess
 import sys
 import tempfile
 
-OBJECTS = ["pd_kernels_16", "pd_kernels_32", "pd_kernels_64", "pd_kernels_lit_16", "pd_kernels_lit_32", "pd_kernels_lit_64"]
+OBJECTS = ["pd_kernels_16", "pd_kernels_32", "pd_kernels_64", "pd_kernels_lit_16", "pd_kernels_lit_32", "pd_kernels_lit_64", "pd_pose"]
 META = [".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".group_segment_fixed_size",
         ".private_segment_fixed_size", ".max_flat_workgroup_size"]
 
@@ -31,7 +32,7 @@ META = [".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr
 def compile_asm(tree, obj, work):
     csrc = pathlib.Path(tree) / "ppr-diffphys_amd" / "csrc"
     plan = subprocess.run(["make", "-n", "-B", f"build/{obj}.o"], cwd=csrc, check=True, capture_output=True, text=True).stdout
-    cmd = next(shlex.split(ln) for ln in plan.splitlines() if "pd_kernels.hip" in ln and " -c " in ln)
+    cmd = next(shlex.split(ln) for ln in plan.splitlines() if f"build/{obj}.o" in ln and " -c " in ln)
     out = pathlib.Path(work) / f"{obj}.s"
     cmd = [("-S" if w == "-c" else w) for w in cmd[:cmd.index("-o")]] + ["--cuda-device-only", "-o", str(out)]
     key = hashlib.sha256()
@@ -68,7 +69,7 @@ def main():
     ap.add_argument("tree_a")
     ap.add_argument("tree_b")
     ap.add_argument("--work", default=None, help="directory for the assembly files (kept and reused)")
-    ap.add_argument("--jobs", type=int, default=6)
+    ap.add_argument("--jobs", type=int, default=7)
     args = ap.parse_args()
     work = pathlib.Path(args.work or tempfile.mkdtemp(prefix="kernel_asm_"))
     sides = {"a": args.tree_a, "b": args.tree_b}

@@ -67,7 +67,7 @@ def test_mass_table_layout(name):
     body = t[8:].reshape(nb, 4)
     assert np.array_equal(body[:, :3], np.asarray(tpl["body_com"], np.float32).reshape(nb, 3)) and (body[:, 3] == 0).all()
     table = hip_backend.mass_table(tpl, device="cpu")
-    assert hip_backend._mass_dims(table) == (nb,) and np.array_equal(table.numpy(), t)
+    assert hip_backend._table_tag(table) == ("mass", (nb,)) and np.array_equal(table.numpy(), t)
 
 
 class _Env:
@@ -89,6 +89,8 @@ def test_wrapper_refusals_without_a_gpu():
     rows = torch.zeros(2 * nb, 23)
     with pytest.raises(ValueError, match="mass_table"):   # a bare tensor carries no dimensions
         hip_backend.centroidal(torch.zeros(table.numel()), nb, rows)
+    with pytest.raises(ValueError, match="mass_table"):   # nor does a table of another kind stand in: the tag names the kind
+        hip_backend.centroidal(hip_backend.joint_table(tpl, device="cpu"), nb, rows)
     with pytest.raises(ValueError, match="23"):
         hip_backend.centroidal(table, nb, torch.zeros(2 * nb, 13))
     with pytest.raises(ValueError, match="multiple"):

@@ -163,7 +163,7 @@ def test_a_table_of_another_nb_gives_zeros(dev):
     C = case("cmp31", "fk")
     rows = rows23(C["bq"], C["bqd"], C["mass"], C["inertia"], dev)
     wrong = gpu_mass_table("mixed25").clone()   # 8 + 4 * 25 floats: shorter than the table of 31 bodies
-    wrong._pd_mass_dims = (31,)                 # ... passed off as one
+    wrong._pd_table = ("mass", (31,))           # ... passed off as one
     out = hip_backend.centroidal(wrong, 31, rows)
     g = hip_backend.centroidal_vjp(wrong, 31, rows, torch.tensor(C["g_out"], device=dev))
     assert (out == 0).all() and (g == 0).all()

@@ -104,10 +104,12 @@ def test_joint_table_refusals_and_wrapper_checks_without_a_gpu():
     with pytest.raises(ValueError, match="coordinates"):
         hip_backend.joint_table_host(star)
     table = hip_backend.joint_table(tpl, device="cpu")
-    assert hip_backend._joint_dims(table) == (nb, int(tpl["nq"]), int(tpl["nqd"]))
+    assert hip_backend._table_tag(table) == ("joint", (nb, int(tpl["nq"]), int(tpl["nqd"])))
     state = torch.zeros(2 * nb, 13)
     with pytest.raises(ValueError, match="joint_table"):   # a bare tensor carries no dimensions
         hip_backend.joint_coords(torch.zeros(table.numel()), nb, state)
+    with pytest.raises(ValueError, match="joint_table"):   # nor does a table of another kind stand in: the tag names the kind
+        hip_backend.joint_coords(hip_backend.mass_table(tpl, device="cpu"), nb, state)
     with pytest.raises(ValueError, match="13"):
         hip_backend.joint_coords(table, nb, torch.zeros(2 * nb, 7))
     with pytest.raises(ValueError, match="multiple"):
