@@ -416,13 +416,36 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  *   then 4 floats per body     com.xyz, 0
  * A table whose nb is not the call's a_broadcast is not read beyond its first float: out / g_b are then written as zeros.
  *
+ * Ground-contact state of body states -- per body the height of its lowest contact candidate, where that candidate is and how fast
+ * it moves, how many candidates touch and how deep:
+ *   PD_POSE_CONTACT_STATE  b = body states [n][13] and a_broadcast = nb as for PD_POSE_GROUND_WRENCH (nb < 1 or n % nb != 0 is refused at
+ *                          every n; any nb).  a = the contact table of PD_POSE_GROUND_WRENCH, unchanged (its material rows and
+ *                          bounding spheres are not read) -> out [n][8] = (h, x, z, u.x, u.y, u.z, s, k).  Per candidate c of the
+ *                          body, P_c = (x, y, z, dist), with the quaternion AS IT IS (not normalised) and R = its linear map:
+ *                            h_c = p.y + (row 1 of R) . P_c.xyz - dist_c     the rollouts' height and touch decision !(h_c > 0),
+ *                                                                             bit for bit (csrc/pd_math.h contact_height)
+ *                            rp = R P_c.xyz      rc = R com      rr_c = (rp.x - rc.x, h_c - p.y - rc.y, rp.z - rc.z)
+ *                            u_c = v + w x rr_c                                           (cp, rr, dpdt of contact_point_fwd)
+ *                          c* = the candidate of lowest h_c, lowest table index on ties: h = h_c*, (x, z) = (p.x + rp*.x,
+ *                          p.z + rp*.z), u = u_c*;
+ *                          k = the number of touching candidates, stored as a float; s = the sum of -h_c over them.  A body
+ *                          without candidates gives (+inf, 0, 0, 0, 0, 0, 0, 0).  A row with a non-finite entry may give anything
+ *                          in its own element; it reads nothing out of range and disturbs no other element.  One wavefront per
+ *                          element sweeps ALL the body's candidates (no early-out: the height is wanted for bodies in the air),
+ *                          then a fixed-order butterfly: no atomics, the same bits on every run, at every n and place in the launch.
+ *                          VJP: g_out [n][8] (entry 7, the count's, is ignored) -> g_b [n][13], the raw partials (quaternion
+ *                          entries not projected): through c*, found again with the same bits, and through s.  Zeros for a body
+ *                          without candidates.  The table has no gradient: a non-NULL g_a is refused, at every n.
+ * A table whose nb is not the call's a_broadcast, or a candidate range that leaves the table's nc, reads no candidate: the element is
+ * then a body without candidates.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
- * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS and PD_POSE_CENTROIDAL are new op codes of the two
- * entries: no symbol or signature changed, the version stays 9.  The enum has a gap: codes 7 and 8 are NOT assigned and are refused as
- * "unknown op" -- callers and tests of version 9 rely on that refusal, so the next op took 9 and the two stay free for as long as the
- * version is 9. */
+ * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL and PD_POSE_CONTACT_STATE are new
+ * op codes of the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8 and 10 are NOT
+ * assigned and are refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal op
+ * took 9, of 10 since the contact state took 11), so the three stay free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
-       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9 };
+       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

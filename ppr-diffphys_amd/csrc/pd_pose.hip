@@ -768,6 +768,143 @@ __global__ __launch_bounds__(256) void k_centroidal_vjp(int nsets, int nb, const
   dst[20] = ai.z * wb.x; dst[21] = ai.z * wb.y; dst[22] = ai.z * wb.z;
 }
 
+// ---- PD_POSE_CONTACT_STATE: the ground-contact geometry of every body of a state set -- the height of its lowest candidate, where that
+// candidate is and how fast it moves, and how many candidates touch and how deep -- and its vector-Jacobian product with respect to the
+// state rows.  Per candidate c of the body (P_c = (x, y, z, dist) and com: the contact table; cv = the cull vector stage_record makes):
+//   h_c = contact_height(cv, P_c)      the rollouts' height, bit for bit, and with it their touch decision !(h_c > 0)
+//   rp = qrot(q, P_c.xyz), rc = rotm(q) com;  rr_c = (rp.x - rc.x, h_c - p.y - rc.y, rp.z - rc.z);  u_c = v + w x rr_c
+// (cp, rr, dpdt of contact_point_fwd).  out [8] = (h, x, z, u.xyz, s, k): c* = the candidate of lowest h_c, lowest table index on ties;
+// h = h_c*, (x, z) = (p.x + rp*.x, p.z + rp*.z), u = u_c*; k = the number of touching candidates (as a float), s = the sum of -h_c over them.  A body
+// without candidates: (+inf, 0, 0, 0, 0, 0, 0, 0).  A NaN height is never a minimum (strict <), so a non-finite row has a defined
+// winner or none -- it reads no candidate outside its body's range.
+// Mapping (the ground wrench's): one wavefront per element, four per workgroup; lanes stride over the body's candidates keeping a running
+// (h, index) and partial sums, then a six-step xor butterfly -- wave_sum for the sums, wave_argmin for the winner -- after which every
+// lane holds the same winner and forms the outputs from it.  No bounding-sphere early-out (the height is wanted for bodies in the
+// air), no LDS, no atomics, no barrier: an element's bits depend neither on the run nor on n nor on its place in the launch.
+enum { CS_OUT = 8, CS_NONE = 0x7fffffff };
+struct CsBody { BodyState s; v3 rc; float4 cv; float Rm[9]; const float4 *pts; int count; };
+// Element i's state, cull vector and candidate range.  A table of another nb, or a range that leaves the table's nc candidates, reads
+// no candidate (count 0) -- the host cannot validate a device buffer.
+__device__ __forceinline__ CsBody cs_stage(const float *tab, int nb, int body, const float *state, size_t i, v3 &com) {
+  CsBody C;
+  C.s = load_state0(state, i);
+  rotm(C.s.r, C.Rm);
+  C.cv = make_float4(C.s.p.y, C.Rm[3], C.Rm[4], C.Rm[5]);  // (stage_record)
+  com = V3(0, 0, 0); C.rc = com; C.pts = nullptr; C.count = 0;
+  if ((int)tab[0] != nb) return C;
+  const GwTable T = gw_table(tab);
+  const float *B = T.body + GW_BODY * body;
+  com = ld3(B);
+  C.rc = mat_vec(C.Rm, com);
+  const int first = (int)B[3], count = (int)B[4], nc = (int)tab[1];
+  if (first >= 0 && count > 0 && first <= nc && count <= nc - first) { C.pts = T.pts + first; C.count = count; }
+  return C;
+}
+// rr of the winner: contact_point_fwd's cp - (p + rc) with p.x and p.z taken out of both sides before the subtraction -- the same
+// function, without the cancellation of two numbers of the size of the body's distance from the origin.
+__device__ __forceinline__ v3 cs_arm(const CsBody &C, v3 rp, float h) { return V3(rp.x - C.rc.x, (h - C.s.p.y) - C.rc.y, rp.z - C.rc.z); }
+// The lower (h, k) pair of the wave in every lane: the lower height, on equal heights the lower index.  h is never NaN (see above), so
+// the pairs are totally ordered and both lanes of an exchange keep the same one.
+__device__ __forceinline__ void wave_argmin(float &h, int &k) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float oh = __shfl_xor(h, off);
+    const int ok = __shfl_xor(k, off);
+    const bool take = oh < h || (oh == h && ok < k);
+    h = take ? oh : h; k = take ? ok : k;
+  }
+}
+// The sweep both kernels run: the winner and, over the touching candidates, their number, the sum of -h and (SUMS) the sum of P.xyz.
+template <bool SUMS>
+__device__ __forceinline__ void cs_sweep(const CsBody &C, int lane, float &h, int &k, float &depth, float &touching, v3 &sumP) {
+  h = INFINITY; k = CS_NONE; depth = 0.f; touching = 0.f; sumP = V3(0, 0, 0);
+  for (int c = lane; c < C.count; c += 64) {
+    const float4 P = C.pts[c];
+    const float hc = contact_height(C.cv, P);
+    if (hc < h) { h = hc; k = c; }
+    if (!(hc > 0.0f)) {
+      depth -= hc; touching += 1.0f;
+      if (SUMS) sumP += V3(P.x, P.y, P.z);
+    }
+  }
+  wave_argmin(h, k);
+  depth = wave_sum(depth); touching = wave_sum(touching);
+  if (SUMS) { sumP.x = wave_sum(sumP.x); sumP.y = wave_sum(sumP.y); sumP.z = wave_sum(sumP.z); }
+}
+
+__global__ __launch_bounds__(256) void k_contact_state_fwd(int n, int nb, const float *__restrict__ tab, const float *__restrict__ state,
+                                                           float *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  v3 com, sumP;
+  const CsBody C = cs_stage(tab, nb, (int)(i % nb), state, (size_t)i, com);
+  float h, depth, touching;
+  int k;
+  cs_sweep<false>(C, lane, h, k, depth, touching, sumP);
+  float o[CS_OUT] = {INFINITY, 0.f, 0.f, 0.f, 0.f, 0.f, depth, touching};
+  if (k != CS_NONE) {  // (k < C.count: an index some lane swept)
+    const float4 P = C.pts[k];
+    const v3 rp = qrot(C.s.r, V3(P.x, P.y, P.z));
+    const v3 u = C.s.v + cross(C.s.w, cs_arm(C, rp, h));
+    o[0] = h; o[1] = C.s.p.x + rp.x; o[2] = C.s.p.z + rp.z; o[3] = u.x; o[4] = u.y; o[5] = u.z;
+  }
+  if (lane < CS_OUT) {
+    float v = o[0];
+#pragma unroll
+    for (int j = 1; j < CS_OUT; ++j) v = lane == j ? o[j] : v;
+    out[(size_t)i * CS_OUT + lane] = v;
+  }
+}
+
+// g_b [n][13]: the raw partials of <g_out, out> with respect to the state row (quaternion entries not projected; g_out[7], the count's,
+// is ignored).  Through c*, found again with the forward kernel's bits, and through s: d s / d p.y = -k and d s / d q = the row-1 adjoint
+// of rotm applied to -sum_touching P_c.xyz.  Every rotation by q is rotm(q) (pd_math.h), so the quaternion adjoint is ONE matrix adjoint:
+// rows 0 and 2 from rp and rc, row 1 from the heights and rc, then one rotm_adj.
+__global__ __launch_bounds__(256) void k_contact_state_vjp(int n, int nb, const float *__restrict__ tab, const float *__restrict__ state,
+                                                           const float *__restrict__ g_out, float *__restrict__ g_b) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  v3 com, sumP;
+  const CsBody C = cs_stage(tab, nb, (int)(i % nb), state, (size_t)i, com);
+  float h, depth, touching;
+  int k;
+  cs_sweep<true>(C, lane, h, k, depth, touching, sumP);
+  float acc[PD_ADJ];
+#pragma unroll
+  for (int j = 0; j < PD_ADJ; ++j) acc[j] = 0.f;
+  if (k != CS_NONE) {
+    const float *g = g_out + (size_t)i * CS_OUT;
+    const float g_h = g[0], g_x = g[1], g_z = g[2], g_s = g[6];
+    const v3 g_u = ld3(g + 3);
+    const float4 P = C.pts[k];
+    const v3 cpt = V3(P.x, P.y, P.z);
+    const v3 rp = qrot(C.s.r, cpt);
+    const v3 rr = cs_arm(C, rp, h);
+    BodyAdj o = adj_zero();
+    v3 adj_rr = V3(0, 0, 0);
+    o.v = g_u;
+    adj_cross(C.s.w, rr, o.w, adj_rr, g_u);                      // u = v + w x rr
+    // rr does not depend on p (p.y enters h and leaves rr.y again): p sees x, z, h and s = -sum_touching h_c alone
+    o.p = V3(g_x, g_h - g_s * touching, g_z);
+    float aM[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) aM[j] = 0.f;
+    add_outer(aM, V3(adj_rr.x + g_x, adj_rr.y + g_h, adj_rr.z + g_z), cpt);  // rp = rotm(q) P.xyz (rows 0, 2), h = p.y + row1 . P - dist (row 1)
+    add_outer(aM, -adj_rr, com);                                 // rc = rotm(q) com
+    add_outer(aM, V3(0.f, -g_s, 0.f), sumP);
+    rotm_adj(C.s.r, aM, o.r);
+    adj_store(acc, o);
+  }
+  if (lane < PD_ADJ) {
+    float v = acc[0];
+#pragma unroll
+    for (int j = 1; j < PD_ADJ; ++j) v = lane == j ? acc[j] : v;
+    g_b[(size_t)i * PD_ADJ + lane] = v;
+  }
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -787,12 +924,14 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 //   ground wrench      out / g_out [n][6], g_a [n][nmat][4]; any nb
 //   joint coordinates  out / g_out [n / nb][nq + nqd]; no g_a
 //   centroidal         out / g_out [n / nb][16], g_b [n][23]; no g_a
+//   contact state      out / g_out [n][8]; the ground wrench's contact table, no g_a; any nb
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
 struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
 constexpr TabledOp TABLED[] = {
     {PD_POSE_GROUND_WRENCH, "PD_POSE_GROUND_WRENCH", "contact", 0, true, GEO_WAVE, GEO_WAVE},
     {PD_POSE_JOINT_COORDS, "PD_POSE_JOINT_COORDS", "joint", JC_MAXNB, false, GEO_LANE, GEO_SETS},
     {PD_POSE_CENTROIDAL, "PD_POSE_CENTROIDAL", "mass", CT_MAXNB, false, GEO_SETS, GEO_SETS},
+    {PD_POSE_CONTACT_STATE, "PD_POSE_CONTACT_STATE", "contact", 0, false, GEO_WAVE, GEO_WAVE},
 };
 
 template <class... A>
@@ -826,9 +965,13 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
       if (out) hipLaunchKernelGGL(k_joint_coords_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_joint_coords_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
       break;
-    default:
+    case PD_POSE_CENTROIDAL:
       if (out) hipLaunchKernelGGL(k_centroidal_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_centroidal_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
+    default:
+      if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
   }
   if (hipGetLastError() == hipSuccess) return 0;
   pd_set_error("pd_pose_op: the kernel launch failed");
@@ -836,7 +979,7 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
 }
 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL))  // (codes 7 and 8 are not assigned: include/ppr_diffphys.h)
+  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE))  // (codes 7, 8 and 10 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
     if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);

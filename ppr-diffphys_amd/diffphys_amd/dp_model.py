@@ -177,6 +177,38 @@ class Centroidal(torch.autograd.Function):
                 g_r[:, 13].reshape(lead + (nb,)) if need[2] else None, g_r[:, 14:].reshape(lead + (nb, 3, 3)) if need[3] else None, None)
 
 
+class ContactState(torch.autograd.Function):
+    """body_q (..., nb, 7), body_qd (..., nb, 6) in Warp order (w, v), env -> (..., nb, 8) = (h, x, z, u.xyz, s, k) per body: height,
+    world (x, z) and velocity of its lowest contact candidate, the summed depth and the number of its touching candidates
+    (``pd_pose_op`` PD_POSE_CONTACT_STATE on the env's contact table, one launch forward and one for the vector-Jacobian product); a
+    body without candidates gives (+inf, 0, 0, 0, 0, 0, 0, 0).  float32 GPU tensors, or an error: no CPU fallback.  The gradients are
+    the raw partials (quaternion entries not projected), nothing is scrubbed; the count k has none."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_qd, env):
+        nb = int(env.nb)
+        _need_gpu("ContactState", body_q, body_qd)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_qd.shape) == lead + (nb, 6)):
+            raise ValueError("ContactState: body_q (..., %d, 7) and body_qd (..., %d, 6) with equal leading shapes; got %s and %s" % (
+                nb, nb, tuple(body_q.shape), tuple(body_qd.shape)))
+        table = hip_backend.env_contact_table(env, body_q.device)
+        state = _state_rows(body_q, body_qd)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(state)
+        return hip_backend.contact_state(table, nb, state).view(lead + (nb, 8))
+
+    @staticmethod
+    def backward(ctx, g):
+        (state,) = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        lead, nb = ctx.lead, ctx.nb
+        g_s = hip_backend.contact_state_vjp(ctx.table, nb, state, g.to(torch.float32).reshape(-1, 8).contiguous())
+        return (g_s[:, :7].reshape(lead + (nb, 7)) if ctx.needs_input_grad[0] else None,
+                g_s[:, 7:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None, None)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

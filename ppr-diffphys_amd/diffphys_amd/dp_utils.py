@@ -318,6 +318,64 @@ def centroidal(body_q, body_qd, body_mass, body_inertia, env):
     return CentroidalState(out[..., 0], out[..., 1:4], out[..., 4:7], out[..., 7:10], out[..., 10:13], out[..., 13], out[..., 14])
 
 
+class ContactState(NamedTuple):
+    """What :func:`contact_state` returns, per body: views of one (..., nb, 8) tensor."""
+    height: torch.Tensor     # (..., nb)     h of the lowest contact candidate c* (lowest index on ties); +inf for a body without candidates
+    point_xz: torch.Tensor   # (..., nb, 2)  world (x, z) of c*
+    velocity: torch.Tensor   # (..., nb, 3)  u = v + w x rr of c*, the velocity the contact model sees
+    depth: torch.Tensor      # (..., nb)     s = sum of -h_c over the touching candidates (!(h_c > 0): the rollouts' touch decision)
+    count: torch.Tensor      # (..., nb)     their number, as a float; carries no gradient
+
+
+def contact_state(body_q, body_qd, env):
+    """The ground-contact geometry of body states, per body: body_q (..., nb, 7) poses (p, q xyzw) and body_qd (..., nb, 6) twists in the
+    rollouts' order (w, v) -- wp_pos / wp_vel rows reshaped to (..., nb, .), or ``ForwardKinematics``' outputs -- ->
+    :class:`ContactState` (height, point_xz, velocity, depth, count).  Heights and the touch decision are the rollout kernels' own
+    arithmetic on the env's contact candidates; every candidate of every body is swept.  One HIP launch
+    (``dp_model.ContactState``), differentiable in body_q and body_qd (raw partials; quaternions are taken as they are): through the
+    lowest candidate, and through the depth sum.  A body without candidates has height +inf and zeros elsewhere, and a zero gradient:
+    :func:`penetration_loss` and :func:`skate_loss` mask such bodies out.  float32 GPU tensors only."""
+    from .dp_model import ContactState as _ContactState
+
+    _need_gpu("contact_state", body_q, body_qd)
+    _check_states("contact_state", body_q, body_qd, int(env.nb))
+    out = _ContactState.apply(body_q, body_qd, env)
+    return ContactState(out[..., 0], out[..., 1:3], out[..., 3:6], out[..., 6], out[..., 7].detach())
+
+
+def _contact_bodies(cs, bodies, *fields):
+    """The chosen bodies' columns of ``fields`` with the bodies WITHOUT candidates (height +inf) replaced by zeros BEFORE any arithmetic
+    (a select, not a product: inf * 0 never forms, in the value or in the gradient) -> (mask, fields..., number of bodies kept)."""
+    pick = (lambda t: t) if bodies is None else (lambda t: t.index_select(cs.height.dim() - 1, torch.as_tensor(
+        bodies, dtype=torch.long, device=cs.height.device).reshape(-1)))
+    mask = pick(cs.height) != float("inf")
+    out = []
+    for f in fields:
+        f = pick(f)
+        out.append(torch.where(mask if f.dim() == mask.dim() else mask.unsqueeze(-1), f, torch.zeros((), dtype=f.dtype, device=f.device)))
+    m = mask.to(cs.height.dtype).reshape(-1)
+    return (mask,) + tuple(out) + (torch.dot(m, m).clamp(min=1.0),)
+
+
+# (the sums below are dot products, like phys_model._mean_sq: torch's multi-block full reductions replay stale inside a captured HIP graph)
+def penetration_loss(cs, bodies=None):
+    """Ground-penetration term of a :class:`ContactState`: mean of depth^2 over the chosen bodies (``bodies``: indices along the body
+    axis; None = all) that have contact candidates, over all leading dimensions.  depth = sum of -h_c over a body's touching
+    candidates, so the term is zero -- with a zero gradient -- for states that touch nothing.  0 when no chosen body has candidates."""
+    _, depth, kept = _contact_bodies(cs, bodies, cs.depth)
+    d = depth.reshape(-1)
+    return torch.dot(d, d) / kept
+
+
+def skate_loss(cs, h0=0.02, bodies=None):
+    """Foot-skate term of a :class:`ContactState`: mean over the chosen bodies that have contact candidates (and all leading dimensions) of
+    clamp(1 - height / h0, 0, 1) * (velocity.x^2 + velocity.z^2) -- the horizontal speed of a body's lowest candidate, weighted 1 at and
+    below the ground and falling linearly to 0 at height h0 (metres) above it."""
+    _, height, vel, kept = _contact_bodies(cs, bodies, cs.height, cs.velocity)
+    near = (1.0 - height / float(h0)).clamp(0.0, 1.0)
+    return torch.dot(near.reshape(-1), (vel[..., 0] ** 2 + vel[..., 2] ** 2).reshape(-1)) / kept
+
+
 def compute_com(body_q, part_com, part_mass):
     """mass-weighted COM of one articulation (numpy)   dp_utils.py:86-90"""
     from scipy.spatial.transform import Rotation as R

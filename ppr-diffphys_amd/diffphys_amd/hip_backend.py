@@ -722,7 +722,7 @@ def pose_op_vjp(op, a, b, g_out, need_a=True, need_b=True):
     return g_a, g_b
 
 
-# ---- The tabled state ops (ground wrench, joint coordinates, centroidal): each takes a device table compiled from a template.  They share
+# ---- The tabled state ops (ground wrench, joint coordinates, centroidal, contact state): each takes a device table compiled from a template.  They share
 # one tag on the table tensor, one per-model cache, one argument check and one gradient check; what differs is passed in.
 _ROWS = {13: ("state", "(p, q xyzw, w, v)"), 23: ("rows", "(p, q xyzw, w, v, m, I row-major)")}   # operand row width -> its name, its columns
 
@@ -751,7 +751,7 @@ def _env_table(env, key, build):
 
 
 def _state_op_check(op, kind, width, table, nb, rows, bare=False):
-    """The argument check of the six state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    """The argument check of the eight state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
@@ -1047,6 +1047,32 @@ def centroidal_vjp(table, nb, rows, g_out):
     _grad_check("centroidal_vjp", "g_out", g_out, sets, _CT_OUT)
     g_b = torch.empty(n, _CT_ROW, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_CENTROIDAL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", sets * _CT_OUT),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
+POSE_CONTACT_STATE = 11   # (code 10 is not assigned either: include/ppr_diffphys.h)
+_CS_OUT = 8   # floats of an output row: (h, x, z, u.xyz, s, k)
+
+
+def contact_state(table, nb, state):
+    """``pd_pose_op`` PD_POSE_CONTACT_STATE: state [n, 13] = (p, q xyzw, w, v) rows, n a multiple of nb (row i is body i % nb), and the
+    contact table of ``ground_wrench`` -> [n, 8] = (h, x, z, u.xyz, s, k) per body: height, world (x, z) and velocity of its lowest
+    contact candidate (lowest table index on ties), the summed depth s and the number k of its touching candidates; (+inf, 0, ...) for
+    a body without candidates.  The same bits on every call."""
+    n, _ = _state_op_check("contact_state", "contact", 13, table, int(nb), state)
+    out = torch.empty(n, _CS_OUT, device=state.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_CONTACT_STATE, n, _dev(table, "table"), int(nb), _ptr(state, "state"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def contact_state_vjp(table, nb, state, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_CONTACT_STATE: g_out [n, 8] (entry 7, the count's, is ignored) -> g_state [n, 13], the raw partials
+    (quaternion entries not projected)."""
+    n, _ = _state_op_check("contact_state_vjp", "contact", 13, table, int(nb), state)
+    _grad_check("contact_state_vjp", "g_out", g_out, n, _CS_OUT)
+    g_b = torch.empty(n, 13, device=state.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_CONTACT_STATE, n, _dev(table, "table"), int(nb), _ptr(state, "state"), _ptr(g_out, "g_out", n * _CS_OUT),
                                 None, _ptr(g_b, "g_b"), _stream()))
     return g_b
 

@@ -25,8 +25,8 @@ import torch.nn as nn
 from . import robots, sim
 from .dataloader import mocap_tensors, bullet2gl, parse_amp
 from .dp_model import ForwardKinematics, ForwardWarp, ForwardWarpTrajLossFK, convert_ppr_warp
-from .dp_utils import (compose_delta, project_bodies, reduce_loss, reduce_loss_masked, reproj_loss, rotate_frame, rotate_frame_vel,
-                       se3_loss)
+from .dp_utils import (compose_delta, contact_state, penetration_loss, project_bodies, reduce_loss, reduce_loss_masked, reproj_loss,
+                       rotate_frame, rotate_frame_vel, se3_loss, skate_loss)
 from .geom_utils import fid_reindex
 from .grad_guard import GradHistory
 from .time_mlp import TimeMLPWrapper, interp_wt, match_param_name
@@ -518,6 +518,10 @@ class phys_model(nn.Module):
             sim_position, sim_velocity = ForwardWarp.apply(q_init, qd_init, torques, res_fin, ref_ja, target_ke, target_kd, body_mass,
                                                            body_inv_mass, body_inertia, body_inv_inertia, self)
             queried_position, queried_velocity, self.pid_ref = ForwardKinematics.apply(queried_q, queried_qd, self.env)
+        # reg_pen / reg_skate (opt-in, off at weight 0: nothing of them is evaluated, no key enters loss_dict): ground penetration and
+        # foot skate of the KINEMATIC states, like reg_foot -- the FK poses and twists in the rollouts' (w, v) order, as FK returns them
+        wt_pen, wt_skate = (float(self.opts.get(k, 0.0) or 0.0) for k in ("reg_pen_wt", "reg_skate_wt"))
+        contact = contact_state(queried_position, queried_velocity, self.env) if (wt_pen > 0 or wt_skate > 0) else None
         sim_velocity = convert_ppr_warp(sim_velocity)
         queried_velocity = convert_ppr_warp(queried_velocity)
         foot_height = self.get_foot_height(queried_position)
@@ -553,6 +557,10 @@ class phys_model(nn.Module):
         loss_dict["reg_torque"] = zero() if torques is None else _mean_sq(torques)
         loss_dict["reg_res_f"] = zero() if res_f is None else _mean_sq(res_f)
         loss_dict["reg_foot"] = foot_height.pow(2).mean()
+        if wt_pen > 0:
+            loss_dict["reg_pen"] = penetration_loss(contact)
+        if wt_skate > 0:
+            loss_dict["reg_skate"] = skate_loss(contact)
 
         total_loss = 0
         for k, v in loss_dict.items():
@@ -707,7 +715,8 @@ class phys_model(nn.Module):
     def _graph_usable(self):
         st = getattr(self, "_graph", None)
         return (st is not None and self.training and st["shape"] == (self.num_envs, self.frames_per_wdw) and st["env"] is self.env
-                and st["absent"] == bool(self.absent_zero_controls) and all(self.opts.get(k) == v for k, v in st["weights"].items()))
+                and st["absent"] == bool(self.absent_zero_controls)   # (every *_wt key: an opt-in weight ADDED after the capture counts too)
+                and {k: v for k, v in self.opts.items() if k.endswith("_wt")} == st["weights"])
 
     def iteration(self):
         """forward() + backward() of one optimisation iteration; returns forward()'s dict.  The replay of the captured graph when there is
@@ -739,7 +748,7 @@ class phys_model(nn.Module):
         return st["out"]
 
     @torch.no_grad()
-    def query(self, img_size=None, joint_coords=False, centroidal=False):
+    def query(self, img_size=None, joint_coords=False, centroidal=False, contacts=False):
         """Env 0 of the last forward(), frame by frame, in the reference's keys (dp_model.py:843-902): the simulated, target and
         control-reference robots POSED -- the reference hands trimesh objects to its renderer (articulate_robot_rbrt:
         collision-mesh vertices rotated and translated by each body's pose); here each is the array of those posed vertices
@@ -751,7 +760,10 @@ class phys_model(nn.Module):
         (dp_utils.joint_coords, generalised rates; one small launch on the env's device) -- comparable with ref_ja, the PD targets.
         centroidal=True adds `sim_centroidal`, a dict of arrays per frame -- mass [F], com, com_vel, momentum, angular_momentum [F, 3],
         kinetic, potential [F] -- of `sim_poses` and the frame twists with the LEARNED body_mass and norm_body_inertia x body_mass
-        (dp_utils.centroidal; `com` / `com_k` above keep the template masses, as the reference)."""
+        (dp_utils.centroidal; `com` / `com_k` above keep the template masses, as the reference).
+        contacts=True adds `sim_contacts`, a dict of arrays per frame and body -- height [F, nb] (+inf for a body without contact
+        candidates), point_xz [F, nb, 2], velocity [F, nb, 3], depth, count [F, nb] -- of `sim_poses` and the frame twists
+        (dp_utils.contact_state: the lowest candidate of every body, and how many of its candidates touch)."""
         sim = np.stack(list(self.sim_trajs), 0).astype(np.float64)
         tgt = np.stack(list(self.target_trajs), 0).astype(np.float64)
         ref = np.stack(list(self.pid_ref), 0).astype(np.float64)
@@ -805,4 +817,11 @@ class phys_model(nn.Module):
             inertia = self.norm_body_inertia.detach().to(self.device, torch.float32) * mass[:, None, None]
             cs = _centroidal(up(self.sim_trajs), up(vels), mass, inertia, self.env)
             data["sim_centroidal"] = {k: v.cpu().numpy() for k, v in cs._asdict().items()}
+        if contacts:
+            vels = getattr(self, "sim_vels", None)
+            if vels is None:
+                raise RuntimeError("query(contacts=True): the last forward() left no frame twists (sim_vels)")
+            up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
+            cs = contact_state(up(self.sim_trajs), up(vels), self.env)
+            data["sim_contacts"] = {k: v.cpu().numpy() for k, v in cs._asdict().items()}
         return data

@@ -60,6 +60,7 @@ def kernels_of(path):
         body = m.group(0).replace(n, "KERNEL")
         body = re.sub(r"\.LBB\d+_", ".LBB_", body)
         body = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", body)
+        body = re.sub(r"[ \t]*;.*$", "", body, flags=re.M)   # comments name the function index too ("in Loop: Header=BB19_38"), padded to a column
         out[n] = (hashlib.sha256(body.encode()).hexdigest(), meta[n])
     return out
 
