@@ -23,6 +23,11 @@ _ip = ctypes.POINTER(ctypes.c_int)
 # The gradients the adjoint stores PER STEP -- [T, bs*nqd], [T, bs*nb, 6], [T, bs*nqd] -- and the only ones a caller may decline
 # (``want=`` of rollout_backward / rollout_backward_traj_loss): the library takes a NULL pointer for each as "not wanted".
 GRAD_NAMES = ("torques", "res_f", "refs")
+# The tensor operands of rollout_forward / rollout_forward_traj_loss after (bs, nsteps, dt), in call order; the adjoints
+# (rollout_backward / rollout_backward_traj_loss) take the same without res_f.  tests/test_host_plumbing.py holds the signatures to them.
+ROLLOUT_INPUTS = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia",
+                  "body_inv_inertia")
+ADJOINT_INPUTS = tuple(n for n in ROLLOUT_INPUTS if n != "res_f")
 
 
 def grad_want(want):

@@ -28,7 +28,7 @@ def worker(lib_path, out_path, names):
 
     hip_backend._LIB_PATH = lib_path   # before anything loads the library
     from helpers import golden_inputs, load_golden
-    from test_gpu_parity import gpu_rollout
+    from gpu_harness import gpu_rollout
     from diffphys_amd import robots, synth
 
     dev = torch.device("cuda:0")

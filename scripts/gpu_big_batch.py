@@ -1,14 +1,10 @@
 #!/usr/bin/env python3
 """Big-batch sanity: 150 001 Laikago envs x 40 steps (6.5 GB workspace) and 60 001 human envs x 20 steps -- copies of a 257-env batch inside
 the big one must come out bit-identical to the small batch (poses and gradients), lane-per-body kernels."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "ppr-diffphys_amd"), os.path.join(ROOT, "tests")]
+from gpu_common import BWD, FWD, dev_inputs
 import numpy as np, torch
 from diffphys_amd import hip_backend, robots, synth
 dev = torch.device("cuda:0")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 for name, bs, T in (("laikago", 150001, 40), ("human", 60001, 20)):
     tpl = robots.load_template(name); nb = int(tpl["nb"])
     small = synth.make_inputs(tpl, name, bs=257, nsteps=T, seed=5, steps_per_frame=13, penetration=0.003)
@@ -22,7 +18,7 @@ for name, bs, T in (("laikago", 150001, 40), ("human", 60001, 20)):
     f2s = list(small["frame2step"])
     dm = hip_backend.DeviceModel(tpl); dm.set_kernel_family(1)
     def run(inp, n):
-        t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD + ("adj_pos", "adj_vel")}
+        t = dev_inputs(inp, dev)
         o = dm.rollout_forward(n, T, small["dt"], *[t[k] for k in FWD], frame2step=f2s)
         g = dm.rollout_backward(n, T, small["dt"], *[t[k] for k in BWD], f2s, o[4], t["adj_pos"], t["adj_vel"])
         torch.cuda.synchronize()

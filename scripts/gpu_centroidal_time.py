@@ -2,13 +2,11 @@
 """Device time of the whole-body (centroidal) op (pd_pose_op PD_POSE_CENTROIDAL): forward and vector-Jacobian product on 100 states per
 env, Laikago 4096 envs by default (arguments: robot:bs ...), and beside it the same expression composed from torch ops in fp32 on the
 GPU (forward, and forward + backward of <g_out, out> by autograd: what a user would write without the op).  The states are the FK
-kernel's of random joint coordinates; masses and inertias are the template's, per state set.  HIP events around each launch, 4 warm-up
-rounds, median of 5 (the rule of scripts/gpu_joint_coords_time.py).  Also printed: the bytes each launch moves at the least -- 92 B
-read per body (forward: + 64 B written per state set; VJP: + 64 B read per set and 92 B written per body) -- the bandwidth that
+kernel's of random joint coordinates; masses and inertias are the template's, per state set.  Timed by the rule of
+gpu_common.timed.  Also printed: the bytes each launch moves at the least -- 92 B read per body (forward: + 64 B written per state set; VJP: + 64 B read per set and 92 B written per body) -- the bandwidth that
 amounts to and its fraction of the HBM peak (8 TB/s)."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
+import sys
+from gpu_common import timed
 import numpy as np, torch
 from diffphys_amd import hip_backend, robots, sim
 
@@ -16,19 +14,6 @@ cfgs = [(a.split(":")[0], int(a.split(":")[1])) for a in sys.argv[1:] if not a.s
 dev = torch.device("cuda:0")
 T = 100
 HBM_PEAK = 8.0e12
-
-
-def timed(fn):
-    ms = []
-    for it in range(9):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        if it >= 4:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms))
 
 
 def q_rot(q, v, sign=1.0):

@@ -9,13 +9,10 @@ the first batches discarded.  Prints the chosen kernels' geometry (DeviceModel.l
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
+from gpu_common import BWD, FWD, ROOT
 import numpy as np, torch
 from diffphys_amd import hip_backend, sim, synth
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 dev = torch.device("cuda:0")
 with np.load(os.path.join(ROOT, "tests", "golden", "template_laikago_toes.npz")) as z:
     orig = {k: z[k] for k in z.files}

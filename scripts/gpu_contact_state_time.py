@@ -1,33 +1,17 @@
 #!/usr/bin/env python3
 """Device time of the contact-state op (pd_pose_op PD_POSE_CONTACT_STATE), forward and VJP, on the frame states of a rollout -- Laikago
 4096 and human 1024 by default (arguments: robot:bs ...), 100 steps, the first four frames -- beside the ground-wrench op (forward and
-state VJP) on the SAME rows.  HIP events around each measured piece, 4 warm-up rounds, median of 5 (the rule of
-scripts/gpu_fwd_only_time.py).  Also printed: the element count (frames x bs x nb), the candidates a state set sweeps, the share of
-elements with a touching candidate, and the two launches on the 10 x 24 state sets of phys_model's training window (what reg_pen /
+state VJP) on the SAME rows.  Each measured piece is timed by the rule of gpu_common.timed.  Also printed:
+the element count (frames x bs x nb), the candidates a state set sweeps, the share of elements with a touching candidate, and the two launches on the 10 x 24 state sets of phys_model's training window (what reg_pen /
 reg_skate add to an iteration)."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
-import numpy as np, torch
+import sys
+from gpu_common import FWD, timed
+import torch
 from diffphys_amd import hip_backend, robots, sim, synth
 
 cfgs = [(a.split(":")[0], int(a.split(":")[1])) for a in sys.argv[1:] if not a.startswith("--")] or [("laikago", 4096), ("human", 1024)]
 dev = torch.device("cuda:0")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 FRAMES = 4
-
-
-def timed(fn):
-    ms = []
-    for it in range(9):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        if it >= 4:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms))
 
 
 for name, bs in cfgs:

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 from helpers import first_branch_difference, grad_env_errors, oracle_bundle, GRAD_LEAD
-from test_gpu_parity import gpu_rollout
+from gpu_harness import gpu_rollout
 from test_gpu_tight import _config_inputs
 from diffphys_amd import hip_backend
 

@@ -4,9 +4,8 @@ config, T = 100, HIP events around the last launch of back-to-back batches (as s
 (default: the configs of DESIGN.md's forward-only section).  --phys: also phys_model.forward() at the reference's 10 x 760 window with
 grad enabled and under torch.no_grad() (wall time per call, synchronised).  Under rocprofv3 --kernel-trace --stats the two forward
 kernels of a config carry different names (the SAVE template argument)."""
-import os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import sys, time
+from gpu_common import FWD
 import numpy as np, torch
 from diffphys_amd import robots, synth, hip_backend
 
@@ -14,7 +13,6 @@ args = [a for a in sys.argv[1:] if not a.startswith("--")]
 cfgs = [(a.split(":")[0], int(a.split(":")[1]), int(a.split(":")[2])) for a in args] or [
     ("laikago", 4096, 16), ("laikago", 512, 16), ("human", 1024, 32), ("quad", 8192, 32)]
 dev = torch.device("cuda:0")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 for name, bs, segw in cfgs:
     tpl = robots.load_template(name)
     T = 100

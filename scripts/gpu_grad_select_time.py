@@ -9,9 +9,8 @@ adjoint and its peak memory, for every input / target_ke only / res_f + target_k
 One process, no retries: any error ends it.  Run it under a time limit of its own, e.g.
     timeout -k 10 600 python scripts/gpu_grad_select_time.py --warp
 Under rocprofv3 --kernel-trace --stats (a run of its own) the selective kernels carry their own names (the last template argument)."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
+import sys
+from gpu_common import BWD, FWD, dev_inputs
 import numpy as np, torch
 from diffphys_amd import dp_model, robots, synth, hip_backend
 
@@ -25,8 +24,6 @@ args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and s
 cfgs = [tuple([a.split(":")[0]] + [int(x) for x in a.split(":")[1:]]) for a in args] or [
     ("laikago", 4096, 16, 1), ("laikago", 512, 64, 2), ("human", 1024, 32, 0), ("quad", 8192, 32, 0)]
 dev = torch.device("cuda:0")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = tuple(k for k in FWD if k != "res_f")
 MODES = (("all three", hip_backend.GRAD_NAMES), ("none", ()), ("res_f only", ("res_f",)))
 print("library", hip_backend.build_id(), flush=True)
 for name, bs, segw, family in cfgs:
@@ -60,7 +57,7 @@ if "--warp" in sys.argv:
     tpl = robots.load_template("laikago")
     T0 = 100
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T0, seed=21, seqs=("mi-trot", "mi-spin"), penetration=0.003)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in synth.INPUT_NAMES}
+    t = dev_inputs(inp, dev, synth.INPUT_NAMES)
     for k in ("torques", "res_f", "refs"):
         t[k] = t[k].repeat((-(-T // T0),) + (1,) * (t[k].dim() - 1))[:T].contiguous()
 

@@ -1,34 +1,17 @@
 #!/usr/bin/env python3
 """Device time of the ground-wrench op (pd_pose_op PD_POSE_GROUND_WRENCH) beside the adjoint launch of the same run, Laikago 4096 x 100 by
-default (arguments: robot:bs ...).  HIP events around each measured piece, 4 warm-up rounds, median of 5 (the rule of
-scripts/gpu_fwd_only_time.py):
+default (arguments: robot:bs ...).  Each measured piece is timed by the rule of gpu_common.timed:
   material gradient   dp_model.material_gradient over the whole saved trajectory: the chunked VJP launches and their colsums
   frame wrench        the forward op on the states of the rollout's frames (the differentiable-grf recipe)
   adjoint             the rollout's adjoint launch (pd_last_kernel_ms), which produced the g_res_f the material gradient contracts
 Also printed: the element count (T x bs x nb) and the share of elements -- one wavefront each -- that found a touching candidate."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
+import sys
+from gpu_common import BWD, FWD, timed
 import numpy as np, torch
 from diffphys_amd import dp_model, hip_backend, robots, sim, synth
 
 cfgs = [(a.split(":")[0], int(a.split(":")[1])) for a in sys.argv[1:] if not a.startswith("--")] or [("laikago", 4096)]
 dev = torch.device("cuda:0")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = tuple(k for k in FWD if k != "res_f")
-
-
-def timed(fn):
-    ms = []
-    for it in range(9):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        if it >= 4:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms))
 
 
 for name, bs in cfgs:

@@ -28,8 +28,7 @@ def one_run(calls):
     bs, T = 4, 1
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T, seed=0)
     dm = hip_backend.DeviceModel(tpl)
-    names = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-    args = [torch.from_numpy(inp[k]).to(dev) for k in names]
+    args = [torch.from_numpy(inp[k]).to(dev) for k in hip_backend.ROLLOUT_INPUTS]
     f2s = list(inp["frame2step"])
     bufs = dm.alloc_rollout(bs, T, len(f2s), dev, backward=False)
     for _ in range(200):

@@ -1,31 +1,16 @@
 #!/usr/bin/env python3
 """Device time of the joint-coordinates op (pd_pose_op PD_POSE_JOINT_COORDS): forward and vector-Jacobian product on 100 states per env,
 Laikago 4096 envs and human 1024 envs by default (arguments: robot:bs ...).  The states are the FK kernel's of random joint coordinates
-(angles uniform in +-1, random unit root quaternions).  HIP events around each launch, 4 warm-up rounds, median of 5 (the rule of
-scripts/gpu_ground_wrench_time.py).  Also printed: the bytes each launch moves at the least -- 52 B read per body plus the outputs
-(forward: 4 (nq + nqd) B per state set; VJP: that read again as g_out, 52 B written per body) -- and the bandwidth that amounts to."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
-import numpy as np, torch
+(angles uniform in +-1, random unit root quaternions).  Timed by the rule of gpu_common.timed.  Also printed:
+the bytes each launch moves at the least -- 52 B read per body plus the outputs (forward: 4 (nq + nqd) B per state set; VJP: that read again as g_out, 52 B written per body) -- and the bandwidth that amounts to."""
+import sys
+from gpu_common import timed
+import torch
 from diffphys_amd import hip_backend, robots, sim
 
 cfgs = [(a.split(":")[0], int(a.split(":")[1])) for a in sys.argv[1:] if not a.startswith("--")] or [("laikago", 4096), ("human", 1024)]
 dev = torch.device("cuda:0")
 T = 100
-
-
-def timed(fn):
-    ms = []
-    for it in range(9):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        if it >= 4:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms))
 
 
 for name, bs in cfgs:

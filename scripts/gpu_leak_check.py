@@ -1,16 +1,13 @@
 #!/usr/bin/env python3
 """Device-memory leak check: 180 create / roll out (five frame tables each) / destroy cycles over the three robots; free device memory before and after."""
-import os, sys, gc
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "ppr-diffphys_amd")]
-import numpy as np, torch
+import gc
+from gpu_common import BWD, FWD, dev_inputs
+import torch
 from diffphys_amd import hip_backend, robots, synth
 dev = torch.device("cuda:0")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 tpls = {n: robots.load_template(n) for n in ("laikago", "human", "quad")}
 inps = {n: synth.make_inputs(tpls[n], n, bs=8, nsteps=10, seed=1) for n in tpls}
-ts = {n: {k: torch.from_numpy(np.ascontiguousarray(inps[n][k], dtype=np.float32)).to(dev) for k in FWD + ("adj_pos", "adj_vel")} for n in tpls}
+ts = {n: dev_inputs(inps[n], dev) for n in tpls}
 def cycle(n_frames_variants):
     for name in tpls:
         dm = hip_backend.DeviceModel(tpls[name])

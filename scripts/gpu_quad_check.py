@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ppr-diffphys_amd"), os.path.join(ROOT, "tests")]
 import numpy as np, torch
 from helpers import relmax
-from test_gpu_parity import gpu_rollout
+from gpu_harness import gpu_rollout
 from diffphys_amd import hip_backend, robots, synth
 
 dev = torch.device("cuda:0")

@@ -3,23 +3,18 @@
 the speculative sweep's redo path, drops into the ground that overflow hit lists, large joint velocities), plus run-to-run
 bitwise repeats.  Prints one line per case and a summary; exits non-zero on a violation.  Usage: gpu_stress.py [ncases] [seed]"""
 import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from gpu_common import BWD, FWD, ROOT, dev_inputs
 import numpy as np, torch
 from diffphys_amd import dp_model, hip_backend, robots, synth
 from oracle import ref_c
 from oracle.ref_c import RefC
 
-INPUT_NAMES = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_mass", "body_inv_mass", "body_inertia",
-               "body_inv_inertia")
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 dev = torch.device("cuda:0")
 
 def gpu(dm, inp):
     bs = inp["q_init"].size // dm.nq
     T, f2s = inp["nsteps"], inp["frame2step"]
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
+    t = dev_inputs(inp, dev, synth.INPUT_NAMES + ("adj_pos", "adj_vel"))
     fos = list(f2s)
     pos, vel, grf, jaf, ws = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=fos)
     g = dm.rollout_backward(bs, T, inp["dt"], *[t[k] for k in BWD], fos, ws, t["adj_pos"], t["adj_vel"])
@@ -94,7 +89,7 @@ for case in range(ncases):
         # per env (tests/helpers.py, the machinery of test_config_size_gradients_every_tensor_per_env): every env whose gradient is off
         # must be explained by its measured conditioning or by a discrete branch the kernel took differently from float64
         from helpers import first_branch_difference, grad_env_errors, oracle_bundle, GRAD_LEAD
-        from test_gpu_parity import gpu_rollout
+        from gpu_harness import gpu_rollout
         full = gpu_rollout(dm, inp, dev, keep_traj=True)
         ob = oracle_bundle(tpl, inp, bs)
         ee = grad_env_errors(full["grads"], ob["g64"], bs)

@@ -3,15 +3,12 @@
 NaN / far targets x kernel families.  Per case: the loss table = se3_loss of the gathered poses; reduce_loss + shares = the reference's
 per-env loop on that table (oracle/pose_torch.py); the self-seeded adjoint = the plain adjoint fed the same seeds; the FK chains that ride
 along = pd_fk_forward / pd_fk_backward bit for bit.  Usage: gpu_stress_f4.py [ncases] [seed]; exits non-zero on a violation."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "ppr-diffphys_amd"), os.path.join(ROOT, "tests")]
+import sys
+from gpu_common import BWD, FWD, dev_inputs
 import numpy as np, torch
 from diffphys_amd import dp_utils, hip_backend, robots, synth
 from oracle.pose_torch import reduce_loss_loop
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 dev = torch.device("cuda:0")
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -35,7 +32,7 @@ for case in range(ncases):
     dm = dms[key]
     inp = synth.make_inputs(tpl, name, bs=bs, nsteps=max(T, 1), seed=int(rng.randint(1 << 30)), steps_per_frame=max(1, T // 3), penetration=float(rng.choice([0.0, 0.003])))
     for k in ("torques", "res_f", "refs"): inp[k] = inp[k][:T]
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD}
+    t = dev_inputs(inp, dev, FWD)
     g = torch.Generator().manual_seed(case)
     pos0 = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)[0]
     tgt = (pos0.view(F, bs, nb, 7).permute(1, 0, 2, 3) + 0.02 * torch.randn(bs, F, nb, 7, generator=g).to(dev)).contiguous()

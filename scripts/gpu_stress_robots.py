@@ -5,8 +5,7 @@ collisions.  Per robot: forward against the C oracle with the fp32 oracle's own 
 float64 adjoint of the kernel's own trajectory (both kernel families when the quad-lane one is eligible), a zero-step rollout, run-to-run
 bits.  Usage: gpu_stress_robots.py [nrobots] [seed]; exits non-zero on a violation."""
 import os, sys, tempfile
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "ppr-diffphys_amd"), os.path.join(ROOT, "tests")]
+from gpu_common import BWD, FWD
 import numpy as np, torch
 from diffphys_amd import hip_backend, sim
 from diffphys_amd.import_urdf import parse_urdf
@@ -17,8 +16,6 @@ from oracle.ref_c import RefC
 dev = torch.device("cuda:0")
 nrob = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 tmp = tempfile.mkdtemp()
 
 bad = 0

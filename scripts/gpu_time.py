@@ -2,8 +2,7 @@
 """Per-kernel device timing of rollout fwd / adjoint for a list of (robot, bs, segw) configs (HIP events around the last
 launches of back-to-back batches)."""
 import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd"))
+from gpu_common import BWD, FWD
 import numpy as np, torch
 from diffphys_amd import robots, synth, hip_backend, dp_model
 
@@ -21,8 +20,8 @@ for name, bs, segw in cfgs:
         dm.set_kernel_family(int(os.environ["PD_FAMILY"]))
     t = {k: torch.from_numpy(inp[k]).to(dev) for k in synth.INPUT_NAMES}
     f2s = inp["frame2step"]; fos = list(f2s)
-    fa = [t[k] for k in ("q_init","qd_init","torques","res_f","refs","target_ke","target_kd","body_inv_mass","body_inertia","body_inv_inertia")]
-    ba = [t[k] for k in ("q_init","qd_init","torques","refs","target_ke","target_kd","body_inv_mass","body_inertia","body_inv_inertia")]
+    fa = [t[k] for k in FWD]
+    ba = [t[k] for k in BWD]
     ap = torch.from_numpy(inp["adj_pos"]).to(dev); av = torch.from_numpy(inp["adj_vel"]).to(dev)
     # batches of steps enqueued back to back (like bench.py's timed region: no idle gaps for the clocks to sag in), the durations
     # of the last forward / adjoint launch of each batch are read; the first batches warm the clocks up

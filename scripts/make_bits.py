@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ppr-diffphys_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 from helpers import golden_inputs, load_golden
-from test_gpu_parity import gpu_rollout
+from gpu_harness import gpu_rollout
 from diffphys_amd import hip_backend, robots, synth
 
 tag = sys.argv[1]

@@ -58,7 +58,8 @@ def _info(dm, kind):
 
 def record_model(key, dev, tmp_path):
     from diffphys_amd import hip_backend
-    from test_gpu_forward_only import BWD, FWD, _inputs, _run_pair, _template
+    from diffphys_amd.hip_backend import ADJOINT_INPUTS as BWD, ROLLOUT_INPUTS as FWD
+    from test_gpu_forward_only import _inputs, _run_pair, _template
 
     tpl, robot = _template(key, tmp_path)
     dm = hip_backend.DeviceModel(tpl)

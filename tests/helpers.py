@@ -10,10 +10,9 @@ for p in (ROOT, os.path.join(ROOT, "ppr-diffphys_amd")):
         sys.path.insert(0, p)
 
 from diffphys_amd import sim  # noqa: E402
+from diffphys_amd.synth import INPUT_NAMES  # noqa: E402,F401
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-INPUT_NAMES = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_mass", "body_inv_mass",
-               "body_inertia", "body_inv_inertia")
 
 
 def relmax(a, b):
@@ -213,21 +212,14 @@ def own_trajectory_check(dm, tpl, inp, dev, hitlog_check=True, abs_floor=0.0, li
     re-decided in float64 -- the Coulomb min and the +-500 N force clamp -- is probed on the kernel's states (singularity_probe).
     Returns dict(worst [bs] = per env the largest per-tensor relative error (grad_env_errors), errors per tensor, probe minima
     per env: coulomb, force_clamp, height; grads of the oracle)."""
-    import torch
-
+    from gpu_harness import gpu_rollout
     from oracle.ref_c import RefC
 
     bs = inp["q_init"].size // dm.nq
-    T, f2s = inp["nsteps"], list(inp["frame2step"])
-    FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-    BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
-    pos, vel, grf, jaf, ws = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)
-    g = dm.rollout_backward(bs, T, inp["dt"], *[t[k] for k in BWD], f2s, ws, t["adj_pos"], t["adj_vel"])
-    grads = {k: v.cpu().numpy() for k, v in g.items()}
-    bq, bqd, bf, mask = dm.saved_trajectory(ws, bs, T)
-    traj = dict(states_q=bq.cpu().numpy(), states_qd=bqd.cpu().numpy(), states_f=bf.cpu().numpy())
-    mask = mask.cpu().numpy()
+    T = inp["nsteps"]
+    run = gpu_rollout(dm, inp, dev, keep_traj=True)
+    grads, traj, ws = run["grads"], run["traj"], run["ws"]
+    mask = traj.pop("clamp")
     rc = RefC(tpl, np.float64)
     # A model with FIXED joints: their angular error is evaluated scale-invariantly by the kernels (pd_math.h fixed_ang_h); the float64
     # reference must do the same (ref_set_twist_eval(1)) -- its literal form turns the fp32 norm error of the stored quaternions into

@@ -13,22 +13,17 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import FWD, dev, dev_inputs  # noqa: F401
 from centroidal_ref import SLICES, centroidal, centroidal_of, template_constants
 from generated_robots import robot, rollout_inputs
 from helpers import INPUT_NAMES, tight_inputs
 from joint_coords_ref import load_tpl
-from test_gpu_state_ops_generated import FWD, SETS, bar, fk_case, frozen
+from test_gpu_state_ops_generated import SETS, bar, fk_case, frozen
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ["fk", "tumbled", "scaled"]
 NAMES = ("mass", "com", "com_vel", "momentum", "angular_momentum", "kinetic", "potential")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def test_the_launch_shapes_are_the_ones_meant():
@@ -189,7 +184,7 @@ def test_shipped_templates_on_rollout_frames(name, dev):
     f2s = inp["frame2step"]
     F = len(f2s)
     env = sim.Model.from_template(tpl, bs, dev)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     with torch.no_grad():
         pos, vel = dp_model.ForwardWarp.apply(*[t[k] for k in INPUT_NAMES], _Host(env, bs, T, f2s, inp["dt"]))
     bq, bqd = pos.view(F, bs, nb, 7).clone().requires_grad_(True), vel.view(F, bs, nb, 6).clone().requires_grad_(True)
@@ -224,7 +219,7 @@ def momentum_rollout(name):
     inp = rollout_inputs(tpl, bs=3, T=8)
     env = sim.Model.from_template(tpl, 3, dev)
     dm = hip_backend.device_model(env)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     pos, vel, grf, jaf, ws = dm.rollout_forward(3, 8, inp["dt"], *[t[k] for k in FWD], frame2step=[3, 4])
     return dict(tpl=tpl, inp=inp, env=env, nb=dm.nb, t=t, pos=pos, vel=vel, grf=grf)
 

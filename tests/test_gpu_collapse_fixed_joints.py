@@ -15,20 +15,14 @@ import pytest
 import torch
 
 from helpers import GOLDEN, GRAD_LEAD, relmax, tight_inputs
-from test_gpu_parity import gpu_rollout
-from test_gpu_tight import CAPS, _oracle
+from gpu_harness import c_oracles, dev, gpu_rollout  # noqa: F401
+from test_gpu_tight import CAPS
 
 pytestmark = pytest.mark.gpu
 
 SEED_SHORT = {1: 12, 3: 14}
 SEED_OWN = 6
 FAMILIES = pytest.mark.parametrize("family", [1, 2], ids=["lane-per-body", "quad-lane"])
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def toes_template():
@@ -120,8 +114,8 @@ def test_short_horizon_tight_on_the_collapsed_template(T, family, collapsed, dev
     dm.set_kernel_family(family)
     out = gpu_rollout(dm, inp, dev)
     assert dm.last_launch_info(0)["envs_per_wg"] == (1 if family == 2 else 64 // WIDTH_COLLAPSED)
-    s64, g64 = _oracle(tpl, inp, np.float64)
-    s32, g32 = _oracle(tpl, inp, np.float32)
+    s64, g64 = c_oracles(tpl, inp, np.float64)
+    s32, g32 = c_oracles(tpl, inp, np.float32)
     assert np.abs(s64["grf"]).max() > 10.0 and np.abs(s64["jaf"]).max() > 1.0, "contacts and joints must be loaded"
     toes = np.asarray(tpl["contact_body"])[-4:]
     assert np.abs(s64["grf"].reshape(2, bs, -1, 6)[0][:, toes]).max() > 10.0, "the lower legs, which now own the toe spheres, carry the load"

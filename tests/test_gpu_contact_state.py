@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import dev  # noqa: F401
 from contact_state_cases import CASES, GENERATED_CASES, STRIDE_COUNTS, TIED, case, conditions, tie_case
 from contact_state_ref import contact_state_of, field, input_conditions
 from test_gpu_state_ops_generated import GW_SETS, bar, frozen, rows13
@@ -22,12 +23,6 @@ from test_gpu_state_ops_generated import GW_SETS, bar, frozen, rows13
 pytestmark = pytest.mark.gpu
 
 TENSORS = ("height", "point_xz", "velocity", "depth")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 @functools.lru_cache(maxsize=None)

@@ -9,18 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import INPUT_NAMES
+from gpu_harness import BWD, FWD, dev, dev_inputs, warp_host  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def _template(key, tmp_path):
@@ -89,7 +81,7 @@ def _run_pair(dm, inp, dev, loss):
     """the same launch with and without a workspace -> (saving, forward-only) dicts of every output, plus the launch infos"""
     bs = inp["q_init"].size // dm.nq
     T, f2s = inp["nsteps"], list(inp["frame2step"])
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     res = []
     for save in (True, False):
         if not loss:
@@ -166,7 +158,7 @@ def test_forward_only_writes_nothing_outside_its_outputs(dev, tmp_path, key, bs,
     inp = _inputs(tpl, robot, bs, T)
     f2s = list(inp["frame2step"])
     F, nb, N = len(f2s), dm.nb, bs * dm.nb
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     ref = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)
     sizes = dict(wp_pos=F * N * 7, wp_vel=F * N * 6, grf=F * N * 6, jaf=F * N * 6)
     bufs = {k: _fenced(n, dev) for k, n in sizes.items()}
@@ -202,19 +194,6 @@ def test_forward_only_writes_nothing_outside_its_outputs(dev, tmp_path, key, bs,
     assert torch.equal(bufs["wp_pos"][1], pos_l.reshape(-1))
 
 
-class _Host:  # the attributes ForwardWarp reads from `self`
-    pass
-
-
-def _host(tpl_name, bs, T, f2s, dt, dev):
-    from diffphys_amd import robots
-
-    h = _Host()
-    h.env = robots.env_from_template(tpl_name, bs, device=dev)
-    h.num_envs, h.steps_idx, h.frame2step, h.dt = bs, range(T), f2s, dt
-    return h
-
-
 def test_no_grad_forward_warp_needs_no_workspace(dev):
     """Laikago 4096 envs x 10 000 steps, 11 frames: the saving forward needs 47.8 GB of workspace.  ForwardWarp.apply under no_grad
     raises the peak of allocated device memory by no more than its outputs + 256 MB, and its frames equal a saving launch's bit for bit."""
@@ -230,11 +209,11 @@ def test_no_grad_forward_warp_needs_no_workspace(dev):
         print("SKIP reason: %.1f GB free, the saving comparison launch needs ~70 GB" % (free / 1e9))
         pytest.skip("needs ~110 GB of free device memory")
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T0, seed=21, seqs=("mi-trot", "mi-spin"), penetration=0.003)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in synth.INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     for k in ("torques", "res_f", "refs"):   # the 100-step controls, repeated over the 10 000 steps
         t[k] = t[k].repeat((R,) + (1,) * (t[k].dim() - 1)).contiguous()
     f2s = list(range(0, T + 1, T // 10))
-    h = _host("laikago", bs, T, f2s, inp["dt"], dev)
+    h = warp_host("laikago", bs, T, f2s, inp["dt"], dev)
     args = [t[k] for k in synth.INPUT_NAMES]
     gc.collect()
     torch.cuda.synchronize()
@@ -251,7 +230,7 @@ def test_no_grad_forward_warp_needs_no_workspace(dev):
     grfs = [g.clone() for g in h.grfs]
     del h
     gc.collect()
-    dm = hip_backend.device_model(_host("laikago", bs, T, f2s, inp["dt"], dev).env)   # the model ForwardWarp launched on
+    dm = hip_backend.device_model(warp_host("laikago", bs, T, f2s, inp["dt"], dev).env)   # the model ForwardWarp launched on
     pos_s, vel_s, grf_s, jaf_s, ws = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)
     torch.cuda.synchronize()
     assert torch.equal(pos, pos_s) and torch.equal(vel, vel_s)
@@ -274,7 +253,7 @@ def test_a_rollout_the_saving_path_cannot_hold(dev):
     f2s = list(range(0, T + 1, 100))
     dm = hip_backend.DeviceModel(tpl)
     assert dm.workspace_floats(bs0 * R, T) * 4 > 300e9
-    t0 = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD}
+    t0 = dev_inputs(inp, dev, FWD)
     for k in ("torques", "res_f", "refs"):
         t0[k] = t0[k].repeat((RT,) + (1,) * (t0[k].dim() - 1)).contiguous()
     pos0, vel0, grf0, jaf0, ws0 = dm.rollout_forward(bs0, T, inp["dt"], *[t0[k] for k in FWD], frame2step=f2s)
@@ -362,7 +341,7 @@ def test_forward_only_refusals(dev):
     dm = hip_backend.DeviceModel(tpl)
     bs, T = 8, 10
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T, seed=1, steps_per_frame=5)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     f2s = list(inp["frame2step"])
     F, nb = len(f2s), dm.nb
     lib = hip_backend.lib()
@@ -383,9 +362,7 @@ def test_forward_only_refusals(dev):
     ap, av = e(F, bs * nb, 7), e(F, bs * nb, 6)
     g = dm._alloc_grads(bs, T, dev)
     rc = lib.pd_rollout_backward(dm.h, bs, T, ctypes.c_float(inp["dt"]), *[t[k].data_ptr() for k in BWD], F, f2s_c, None, ap.data_ptr(),
-                                 av.data_ptr(), *[g[k].data_ptr() for k in ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke",
-                                                                             "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")],
-                                 hip_backend._stream())
+                                 av.data_ptr(), *[g[k].data_ptr() for k in FWD], hip_backend._stream())
     assert rc != 0 and "null device pointer" in lib.pd_last_error().decode()
     with pytest.raises((TypeError, AttributeError, RuntimeError)):
         dm.rollout_backward(bs, T, inp["dt"], *[t[k] for k in BWD], f2s, ws, ap, av)

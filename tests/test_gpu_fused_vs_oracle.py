@@ -15,16 +15,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import BWD, FWD, dev, dev_inputs  # noqa: F401
 from helpers import relmax, toy_inputs, toy_template
-from test_gpu_parity import BWD, FWD, GRADS
+from test_gpu_parity import GRADS
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def _oracle_pipeline(rc, inp, tgt, outseq, wt, qq, qqd, w_q, w_qd):
@@ -114,7 +109,7 @@ def test_fused_entries_vs_float64_oracle_pipeline(case, dev, oracle_libs, tmp_pa
 
     # ---- the fused entries through the C ABI
     dm = hip_backend.DeviceModel(tpl)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in set(FWD) | set(BWD)}
+    t = dev_inputs(inp, dev, set(FWD) | set(BWD))
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
     tgt_d, outseq_d = d(tgt), torch.from_numpy(outseq).to(dev)
     qq_d, qqd_d = d(qq), d(qqd)

@@ -12,12 +12,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import BWD, FWD, SEEDED, dev, dev_inputs, device_model, warp_grads, warp_host  # noqa: F401
 from helpers import INPUT_NAMES, tight_inputs
 
 pytestmark = pytest.mark.gpu
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 PARAMS = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 STEPWISE = ("torques", "res_f", "refs")
 # the seven proper subsets of the three per-step gradients, the empty one first
@@ -26,12 +25,6 @@ T12, F2S = 12, [0, 5, 12]
 # (robot, envs, kernel family, numeric policy literal)
 CASES = [("laikago", 5, 1, False), ("laikago", 5, 2, False), ("human", 3, 0, False), ("quad", 3, 0, False)]
 LITERAL_CASES = [("laikago", 5, 1, True), ("human", 3, 0, True)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def _inputs(robot, bs, T=T12, f2s=F2S, seed=3):
@@ -57,14 +50,9 @@ def _bundle(dev, robot, bs, family, literal):
     """One saving forward and the all-three adjoint of a case, computed once and left unchanged: (dm, inp, tensors, ws, reference grads)"""
     key = (robot, bs, family, literal)
     if key not in _BUNDLES:
-        from diffphys_amd import hip_backend
-
         tpl, inp = _inputs(robot, bs)
-        dm = hip_backend.DeviceModel(tpl)
-        dm.set_kernel_family(family)
-        if literal:
-            dm.set_numeric_policy(hip_backend.NUM_LITERAL)
-        t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
+        dm = device_model(tpl, family, literal=literal)
+        t = dev_inputs(inp, dev, SEEDED)
         pos, vel, grf, jaf, ws = dm.rollout_forward(bs, T12, inp["dt"], *[t[k] for k in FWD], frame2step=F2S)
         assert float(grf.abs().max()) > 0.0, "contacts must be active"
         g = dm.rollout_backward(bs, T12, inp["dt"], *[t[k] for k in BWD], F2S, ws, t["adj_pos"], t["adj_vel"])
@@ -211,19 +199,6 @@ def test_traj_loss_fk_entry(dev, family):
         _assert_same(g, ref, ("traj_loss_fk", family, want))
 
 
-class _Host:  # the attributes ForwardWarp reads from `self`
-    pass
-
-
-def _host(robot, bs, T, f2s, dt, dev, K=None):
-    from diffphys_amd import robots
-
-    h = _Host()
-    h.env = robots.env_from_template(robot, bs, device=dev)
-    h.num_envs, h.steps_idx, h.frame2step, h.dt, h.checkpoint_steps = bs, range(T), f2s, dt, K
-    return h
-
-
 class _Spy:
     """records the ``want`` of every DeviceModel.rollout_backward call"""
 
@@ -240,27 +215,19 @@ class _Spy:
         monkeypatch.setattr(hip_backend.DeviceModel, "rollout_backward", spy)
 
 
-def _warp_grads(t_in, ap, av, h, needs, names=INPUT_NAMES, cls=None):
-    from diffphys_amd import dp_model
-
-    t = {k: t_in[k].detach().clone().requires_grad_(k in needs) for k in names}
-    pos, vel = (cls or dp_model.ForwardWarp).apply(*[t[k] for k in names], h)
-    ((pos * ap).sum() + (vel * av).sum()).backward()
-    torch.cuda.synchronize()
-    return {k: t[k].grad for k in names}
-
-
 @pytest.mark.parametrize("K", [None, 5], ids=["single-launch", "checkpoint-5"])
 def test_forward_warp_asks_only_for_what_needs_a_gradient(dev, monkeypatch, K):
     """ForwardWarp.apply with requires_grad on torques and target_ke only: the adjoint launches ask for g_torques alone, torques.grad and
     target_ke.grad are those of the run where every input requires a gradient, bit for bit, res_f.grad and refs.grad are None.  K = 5:
     the checkpointed adjoint, segments 5, 5, 2 (5 is no multiple of the 4-step cull epoch), against the unselective checkpointed run."""
+    from diffphys_amd import dp_model
+
     _, inp, t, _, _, _ = _bundle(dev, "laikago", 5, 1, False)
     bs, ap, av = 5, t["adj_pos"], t["adj_vel"]
-    h = _host("laikago", bs, T12, F2S, inp["dt"], dev, K)
-    full = _warp_grads(t, ap, av, h, INPUT_NAMES)
+    h = warp_host("laikago", bs, T12, F2S, inp["dt"], dev, K)
+    full = warp_grads(dp_model.ForwardWarp, INPUT_NAMES, t, h, ap, av)[2]
     spy = _Spy(monkeypatch)
-    sel = _warp_grads(t, ap, av, h, ("torques", "target_ke"))
+    sel = warp_grads(dp_model.ForwardWarp, INPUT_NAMES, t, h, ap, av, needs=("torques", "target_ke"))[2]
     assert spy.wants == [("torques",)] * (3 if K else 1), spy.wants
     assert torch.equal(sel["torques"], full["torques"]) and torch.equal(sel["target_ke"], full["target_ke"])
     assert float(full["torques"].abs().max()) > 0.0 and float(full["res_f"].abs().max()) > 0.0
@@ -278,11 +245,11 @@ def test_forward_warp_state_with_only_the_body_state(dev, monkeypatch):
     tin = dict(t, body_q0=pos[1], body_qd0=vel[1])
     for k in STEPWISE:
         tin[k] = t[k][s:].contiguous()
-    h = _host("laikago", bs, T12 - s, [0, T12 - s], inp["dt"], dev)
+    h = warp_host("laikago", bs, T12 - s, [0, T12 - s], inp["dt"], dev, None)
     ap, av = t["adj_pos"][1:], t["adj_vel"][1:]
-    full = _warp_grads(tin, ap, av, h, names, names, dp_model.ForwardWarpState)
+    full = warp_grads(dp_model.ForwardWarpState, names, tin, h, ap, av)[2]
     spy = _Spy(monkeypatch)
-    sel = _warp_grads(tin, ap, av, h, ("body_q0", "body_qd0"), names, dp_model.ForwardWarpState)
+    sel = warp_grads(dp_model.ForwardWarpState, names, tin, h, ap, av, needs=("body_q0", "body_qd0"))[2]
     assert spy.wants == [()], spy.wants
     assert torch.equal(sel["body_q0"], full["body_q0"]) and torch.equal(sel["body_qd0"], full["body_qd0"]) and float(full["body_q0"].abs().max()) > 0.0
     assert all(sel[k] is None for k in names[2:])
@@ -299,10 +266,9 @@ def test_backward_peak_memory_drops_by_the_per_step_gradients(dev):
     nb, nqd = int(tpl["nb"]), int(tpl["nqd"])
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T, seed=2, steps_per_frame=100, penetration=0.003)
     f2s = [int(x) for x in inp["frame2step"]]
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
-    ap = torch.from_numpy(np.ascontiguousarray(inp["adj_pos"], dtype=np.float32)).to(dev)
-    av = torch.from_numpy(np.ascontiguousarray(inp["adj_vel"], dtype=np.float32)).to(dev)
-    h = _host("laikago", bs, T, f2s, inp["dt"], dev, K)
+    t = dev_inputs(inp, dev, SEEDED)
+    ap, av = t["adj_pos"], t["adj_vel"]
+    h = warp_host("laikago", bs, T, f2s, inp["dt"], dev, K)
 
     def peak(needs):
         x = {k: t[k].detach().clone().requires_grad_(k in needs) for k in INPUT_NAMES}

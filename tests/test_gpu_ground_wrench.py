@@ -18,19 +18,13 @@ import torch
 from ground_wrench_common import (MATERIALS, MATERIALS_B, candidate_probe, model_inputs, oracle_rollout_grads, two_material_template,
                                   wrench_and_state_grads)
 from helpers import INPUT_NAMES, chain2, build_template, relmax
-from test_gpu_parity import BWD, FWD
+from gpu_harness import BWD, FWD, dev, dev_inputs  # noqa: F401
 from test_gpu_tight import CAPS
 
 pytestmark = pytest.mark.gpu
 
 BS, T = 3, 6
 FRAMES = [0, 3, 5, 6]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def check(what, a, c32, ref, cap, floor=1e-5):
@@ -58,7 +52,7 @@ def case(name):
     dm = hip_backend.device_model(env)
     nb = dm.nb
     rng = np.random.RandomState(7)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     adj_pos = torch.from_numpy(rng.randn(len(FRAMES), BS * nb, 7).astype(np.float32)).to(dev)
     adj_vel = torch.from_numpy(rng.randn(len(FRAMES), BS * nb, 6).astype(np.float32)).to(dev)
     pos, vel, grf, jaf, ws = dm.rollout_forward(BS, T, inp["dt"], *[t[k] for k in FWD], frame2step=FRAMES)
@@ -172,7 +166,7 @@ def _e2e(name, dev, frame2step):
     rng = np.random.RandomState(11)
     F, N = len(frame2step), 8 * int(tpl["nb"])
     w = dict(pos=rng.randn(F, N, 7), vel=rng.randn(F, N, 6), grf=rng.randn(sum(s < 3 for s in frame2step), N, 6))
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     return tpl, inp, env, w, t
 
 
@@ -231,7 +225,7 @@ def test_a_materials_update_rebuilds_the_device_model(dev):
     wp, wv = (torch.from_numpy(w[k].astype(np.float32)).to(dev) for k in ("pos", "vel"))
 
     def run(env, rows):
-        t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev).requires_grad_(True) for k in INPUT_NAMES}
+        t = {k: v.requires_grad_(True) for k, v in dev_inputs(inp, dev).items()}
         M = torch.from_numpy(rows).to(dev).requires_grad_(True)
         h = _Host(env, 8, 3, inp["frame2step"], inp["dt"])
         pos, vel = dp_model.ForwardWarpContact.apply(*[t[k] for k in INPUT_NAMES], M, h)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import dev, dev_inputs  # noqa: F401
 from helpers import INPUT_NAMES, relmax, tight_inputs
 from joint_coords_ref import coords_of, fk_states, joint_coords, load_tpl, oracle_template, random_coords, tangent
 
@@ -22,12 +23,6 @@ RATES = ["generalized", "measured"]
 # (template, state sets): 41 Laikago sets are 533 elements -- sets straddle the forward kernel's workgroups and fill three of the VJP's
 VALUE_CASES = [("laikago", 5), ("human", 3), ("laikago_toes", 2), ("laikago", 41), ("laikago", 1)]
 VJP_CASES = [("laikago", 5), ("laikago", 41), ("human", 3), ("laikago_toes", 2)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def bar(what, gpu, f32, ref, floor=1e-5):
@@ -107,7 +102,7 @@ def test_simulated_states(name, dev):
     nb = int(tpl["nb"])
     inp = synth.make_inputs(tpl, name, bs=bs, nsteps=T, seed=2, penetration=0.004)
     env = sim.Model.from_template(tpl, bs, dev)
-    t = [torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES]
+    t = list(dev_inputs(inp, dev).values())
     with torch.no_grad():
         pos, vel = dp_model.ForwardWarp.apply(*t, _Host(env, bs, T, f2s, inp["dt"]))
     F = len(f2s)
@@ -188,7 +183,7 @@ def test_gradients_through_the_rollout(dev):
     F = len(f2s)
     w_q = np.random.RandomState(23).randn(F, bs, nq)
     env = sim.Model.from_template(tpl, bs, dev)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     wrt = ("q_init", "qd_init", "refs")
     for k in wrt:
         t[k].requires_grad_(True)

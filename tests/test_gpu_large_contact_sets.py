@@ -12,18 +12,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, GRAD_LEAD, INPUT_NAMES, per_env, relmax
+from gpu_harness import c_oracles, dev, gpu_rollout, same_bits  # noqa: F401
+from helpers import GOLDEN, GRAD_LEAD, per_env, relmax
 
 pytestmark = pytest.mark.gpu
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def toes_template():
@@ -74,36 +67,11 @@ def inputs(tpl, robot, bs, T, seed, kicked=False):
     return inp
 
 
-def run(dm, inp, dev):
-    bs = inp["q_init"].size // dm.nq
-    T, f2s = inp["nsteps"], list(inp["frame2step"])
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
-    pos, vel, grf, jaf, ws = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)
-    g = dm.rollout_backward(bs, T, inp["dt"], *[t[k] for k in BWD], f2s, ws, t["adj_pos"], t["adj_vel"])
-    torch.cuda.synchronize()
-    out = dict(wp_pos=pos.cpu().numpy(), wp_vel=vel.cpu().numpy(), grf=grf.cpu().numpy(), jaf=jaf.cpu().numpy())
-    out["grads"] = {k: v.cpu().numpy() for k, v in g.items()}
-    return out
-
-
-def same_bits(a, b):
-    return all(np.array_equal(a[k], b[k]) for k in ("wp_pos", "wp_vel", "grf", "jaf")) and all(np.array_equal(a["grads"][k], b["grads"][k]) for k in a["grads"])
-
-
 def oracle(tpl, inp, dtype=np.float32):
     """C oracle forward + adjoint.  A model with FIXED joints (laikago_toes) is evaluated with the kernels' scale-invariant fixed-joint
     angle (set_twist_eval(True)), as test_gpu_parity.py::test_generic_joint_kernel_on_toy_robot does: the literal form turns the fp32 norm
     error of the quaternions into spurious angles for any evaluator."""
-    from oracle.ref_c import RefC
-
-    rc = RefC(tpl, dtype)
-    rc.set_twist_eval(has_fixed(tpl))
-    try:
-        st = rc.rollout_forward(inp, inp["nsteps"], inp["frame2step"], inp["dt"])
-        gr = rc.rollout_backward(st, inp["adj_pos"], inp["adj_vel"])
-    finally:
-        rc.set_twist_eval(False)
-    return st, gr
+    return c_oracles(tpl, inp, dtype, twist_eval=has_fixed(tpl))
 
 
 def has_fixed(tpl):
@@ -188,12 +156,12 @@ def test_one_workgroup_against_the_fp32_oracle(key, bs, family, dev, oracle_libs
     if family:
         dm.set_kernel_family(family)
     inp = inputs(tpl, robot, bs, 12, seed=4)
-    out = run(dm, inp, dev)
+    out = gpu_rollout(dm, inp, dev)
     assert_global_tables(dm, tpl)
     if family == 2:
         assert dm.last_launch_info(0)["envs_per_wg"] <= 4, dm.last_launch_info(0)   # the quad-lane kernels ran
     check_vs_oracle(tpl, inp, out)
-    assert same_bits(out, run(dm, inp, dev)), "two runs must give the same bits"
+    assert same_bits(out, gpu_rollout(dm, inp, dev)), "two runs must give the same bits"
 
 
 @pytest.mark.parametrize("key,family", [("laikago_toes", 0), ("laikago12k", 1), ("laikago12k", 2), ("human10k", 0)])
@@ -232,12 +200,12 @@ def test_full_chip(key, bs, dev, oracle_libs):
     dm.set_kernel_family(1)
     T = 10
     inp = inputs(tpl, robot, bs, T, seed=7)
-    out = run(dm, inp, dev)
+    out = gpu_rollout(dm, inp, dev)
     assert_global_tables(dm, tpl)
     if robot == "laikago" and key == "laikago12k":
         assert dm.last_launch_info(0)["threads_per_wg"] % 192 == 0   # body, contact and cull wave per env group
     assert all(np.isfinite(v).all() for v in (out["wp_pos"], out["wp_vel"])) and all(np.isfinite(v).all() for v in out["grads"].values())
-    assert same_bits(out, run(dm, inp, dev))
+    assert same_bits(out, gpu_rollout(dm, inp, dev))
     pick = np.linspace(0, bs - 1, 8).astype(np.int64)
     sub = sub_batch(inp, bs, pick)
     F = len(inp["frame2step"])
@@ -255,7 +223,7 @@ def test_65535_candidates_build_and_run_65536_are_refused(dev, oracle_libs):
     tpl = replicated("laikago", 65535)
     dm = hip_backend.DeviceModel(tpl)
     inp = inputs(tpl, "laikago", 9, 6, seed=2)
-    out = run(dm, inp, dev)
+    out = gpu_rollout(dm, inp, dev)
     assert_global_tables(dm, tpl)
     check_vs_oracle(tpl, inp, out)
     with pytest.raises(RuntimeError, match="more than 65535 contact candidates"):

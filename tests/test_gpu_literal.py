@@ -7,29 +7,14 @@ The yardsticks are the C oracle in ITS literal setting (ref_set_twist_eval(0), i
 as "what a plain fp32 evaluation of the reference's text gives"."""
 import numpy as np
 import pytest
-import torch
 
 from helpers import GRAD_LEAD, relmax, tight_inputs
-from test_gpu_parity import gpu_rollout
+from gpu_harness import c_oracles, dev, gpu_rollout  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
-
-
-def _oracle(tpl, inp, dtype):
-    from oracle.ref_c import RefC
-
-    rc = RefC(tpl, dtype)   # literal twist / FIXED evaluation is the oracle's default
-    st = rc.rollout_forward(inp, inp["nsteps"], inp["frame2step"], inp["dt"])
-    return st, rc.rollout_backward(st, inp["adj_pos"], inp["adj_vel"])
-
-
-def _model(tpl, family=0, literal=True):
+def _model(tpl, family=0, literal=True):   # (not gpu_harness.device_model: this one asserts the policy it finds and sets)
     from diffphys_amd import hip_backend
 
     dm = hip_backend.DeviceModel(tpl)
@@ -62,8 +47,8 @@ def test_literal_short_horizon_vs_literal_oracle(T, family, dev, oracle_libs):
     tpl = robots.load_template("laikago")
     inp = tight_inputs(tpl, "laikago", 48, T, seed=11 + T)
     out = gpu_rollout(_model(tpl, family), inp, dev)
-    s64, g64 = _oracle(tpl, inp, np.float64)
-    s32, g32 = _oracle(tpl, inp, np.float32)
+    s64, g64 = c_oracles(tpl, inp, np.float64)
+    s32, g32 = c_oracles(tpl, inp, np.float32)
 
     def check(what, a, c32, ref, cap, floor):
         e_gpu, e_c = relmax(a, ref), relmax(c32, ref)
@@ -99,8 +84,8 @@ def test_the_switch_switches_small_joint_angles(family, dev, oracle_libs):
     nb = int(tpl["nb"])
     inp["adj_pos"] = (rng.randn(2, bs * nb, 7) * 1e-3).astype(np.float32)
     inp["adj_vel"] = (rng.randn(2, bs * nb, 6) * 1e-3).astype(np.float32)
-    s64, _ = _oracle(tpl, inp, np.float64)
-    s32, _ = _oracle(tpl, inp, np.float32)
+    s64, _ = c_oracles(tpl, inp, np.float64)
+    s32, _ = c_oracles(tpl, inp, np.float32)
     lit = gpu_rollout(_model(tpl, family, literal=True), inp, dev, backward=False)
     stab = gpu_rollout(_model(tpl, family, literal=False), inp, dev, backward=False)
     ref = np.asarray(s64["jaf"], np.float64)[0]
@@ -189,8 +174,8 @@ def test_literal_generic_robot_with_a_fixed_joint(dev, oracle_libs, tmp_path):
     inp.update(frame2step=[0, 11], nsteps=T, dt=5e-4)
     dm = _model(tpl)
     out = gpu_rollout(dm, inp, dev)
-    s64, _ = _oracle(tpl, inp, np.float64)
-    s32, _ = _oracle(tpl, inp, np.float32)
+    s64, _ = c_oracles(tpl, inp, np.float64)
+    s32, _ = c_oracles(tpl, inp, np.float32)
     # per env (the acos noise of the FIXED joint is a random +-1e-3 rad per step and evaluator: a max over 64 envs compares two tails)
     F = len(inp["frame2step"])
     for k, floor in (("wp_pos", 2e-5), ("wp_vel", 2e-3), ("grf", 5e-3), ("jaf", 5e-3)):

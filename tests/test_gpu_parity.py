@@ -14,37 +14,12 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import BWD, FWD, SEEDED, dev, dev_inputs, gpu_rollout  # noqa: F401
 from helpers import GRAD_LEAD, INPUT_NAMES, golden_inputs, load_golden, relmax
 
 pytestmark = pytest.mark.gpu
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-BWD = ("q_init", "qd_init", "torques", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 GRADS = FWD
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
-
-
-def gpu_rollout(dm, inp, dev, backward=True, keep_traj=False):
-    from diffphys_amd import dp_model
-
-    bs = inp["q_init"].size // dm.nq
-    T, f2s = inp["nsteps"], inp["frame2step"]
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
-    fos = list(f2s)
-    pos, vel, grf, jaf, ws = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=fos)
-    out = dict(wp_pos=pos.cpu().numpy(), wp_vel=vel.cpu().numpy(), grf=grf.cpu().numpy(), jaf=jaf.cpu().numpy())
-    if backward:
-        g = dm.rollout_backward(bs, T, inp["dt"], *[t[k] for k in BWD], fos, ws, t["adj_pos"], t["adj_vel"])
-        out["grads"] = {k: v.cpu().numpy() for k, v in g.items()}
-    if keep_traj:  # the states, total wrenches and clamp masks the kernel saved for its adjoint
-        bq, bqd, bf, mask = dm.saved_trajectory(ws, bs, T)
-        out["traj"] = dict(states_q=bq.cpu().numpy(), states_qd=bqd.cpu().numpy(), states_f=bf.cpu().numpy(), clamp=mask.cpu().numpy())
-    return out
 
 
 @pytest.mark.parametrize("name,segw", [("laikago", 0), ("laikago", 32), ("laikago", 64), ("human", 0), ("human", 64), ("quad", 0), ("quad", 64)])
@@ -1184,7 +1159,7 @@ def test_edge_shapes_every_robot(name, family, dev, oracle_libs):
                 assert np.abs(out["grads"][k]).max() == 0, (k, bs, T)
     # no force snapshots: same poses, no grf / jaf buffers touched
     inp = synth.make_inputs(tpl, name, bs=3, nsteps=5, seed=15, penetration=0.002)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD}
+    t = dev_inputs(inp, dev, FWD)
     a = dm.rollout_forward(3, 5, inp["dt"], *[t[k] for k in FWD], frame2step=[0, 5])
     b = dm.rollout_forward(3, 5, inp["dt"], *[t[k] for k in FWD], frame2step=[0, 5], want_forces=False)
     assert b[2] is None and b[3] is None and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
@@ -1220,7 +1195,7 @@ def test_every_state_is_a_frame(name, family, dev, oracle_libs):
     # the same through the loss-evaluating entries: table = se3_loss of every state's poses, seeds at every step
     from diffphys_amd import dp_utils
 
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD}
+    t = dev_inputs(inp, dev, FWD)
     F = T + 1
     pos = torch.from_numpy(out["wp_pos"]).to(dev)
     tgt = (pos.view(F, bs, nb, 7).permute(1, 0, 2, 3) + 0.01 * torch.randn(bs, F, nb, 7, device=dev)).contiguous()
@@ -1250,7 +1225,7 @@ def test_mixed_families_between_the_two_thresholds(dev, oracle_libs):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     if not (2 * cus < bs <= 4 * cus):
         pytest.skip("batch is not between the two thresholds on this device")
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
+    t = dev_inputs(inp, dev, SEEDED)
     f2s = list(inp["frame2step"])
     fwd = lambda: dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)
     bwd = lambda ws: dm.rollout_backward(bs, T, inp["dt"], *[t[k] for k in BWD], f2s, ws, t["adj_pos"], t["adj_vel"])
@@ -1290,7 +1265,7 @@ def test_traj_loss_and_fk_ride_at_the_edges(name, family, dev):
         inp = synth.make_inputs(tpl, name, bs=bs, nsteps=max(T, 1), seed=18, penetration=0.002)
         for k in ("torques", "res_f", "refs"):
             inp[k] = inp[k][:T]
-        t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD}
+        t = dev_inputs(inp, dev, FWD)
         F = len(f2s)
         jq = (t["q_init"].view(1, bs, nq) + 0.1 * torch.randn(2, bs, nq, generator=g).to(dev)).contiguous()
         jqd = (0.3 * torch.randn(2, bs, nqd, generator=g)).to(dev).contiguous()
@@ -1521,7 +1496,7 @@ def test_reduce_loss_inside_the_launch_on_awkward_tables(dev):
     for tag, bs, F in cases:
         T = F - 1
         inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T, seed=23, steps_per_frame=1, penetration=0.002)
-        t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in FWD}
+        t = dev_inputs(inp, dev, FWD)
         f2s = list(range(F))
         pos0 = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)[0]
         tgt = (pos0.view(F, bs, nb, 7).permute(1, 0, 2, 3) + 0.01 * torch.randn(bs, F, nb, 7, generator=g).to(dev)).contiguous()
@@ -1718,7 +1693,7 @@ def test_a_million_envs_past_four_gib(R, T, f2s, need_gb, dev):
     inp["adj_pos"] = (rng.randn(F, bs0 * nb, 7) * 1e-2).astype(np.float32)
     inp["adj_vel"] = (rng.randn(F, bs0 * nb, 6) * 1e-2).astype(np.float32)
     lead = dict(GRAD_LEAD, body_mass=0, adj_pos=1, adj_vel=1)
-    t0 = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
+    t0 = dev_inputs(inp, dev, SEEDED)
 
     def tiled(k):   # the env axis (after the step / frame axis where there is one) repeated R times
         x = t0[k]
@@ -1780,7 +1755,7 @@ def test_a_million_envs_through_the_fused_loss_and_fk_entries(dev):
     inp = synth.make_inputs(tpl, "laikago", bs=bs0, nsteps=T, seed=13, seqs=("mi-trot", "mi-spin"), penetration=0.003)
     F, nb, nq, nqd = len(f2s), 13, 19, 18
     rng = np.random.RandomState(6)
-    t0 = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t0 = dev_inputs(inp, dev)
     dm = hip_backend.DeviceModel(tpl)
     pos_plain = dm.rollout_forward(bs0, T, inp["dt"], *[t0[k] for k in FWD], frame2step=f2s)[0]
     tgt0 = pos_plain.reshape(F, bs0, nb, 7).permute(1, 0, 2, 3).contiguous().clone()

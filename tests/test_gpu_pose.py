@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def dev():
+def dev():   # (not gpu_harness.dev: without a GPU this module skips)
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     return torch.device("cuda:0")

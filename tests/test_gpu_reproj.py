@@ -23,15 +23,10 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import BWD, FWD, dev  # noqa: F401
 from helpers import GOLDEN, INPUT_NAMES, relmax, tight_inputs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ the restatement (any dtype, any device)
@@ -389,7 +384,6 @@ def _run_fused(S, fk, h, terms):
 def _direct(S, fk, adj_pos, adj_vel):
     """the library call the Function's backward must be: dm.rollout_backward_traj_loss(..., adj_pos=, adj_vel=) on a forward of the same inputs"""
     from diffphys_amd import hip_backend
-    from test_gpu_parity import BWD, FWD
 
     h = S["host"]()
     dm = hip_backend.device_model(h.env)

@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import FWD, SEEDED, dev, dev_inputs, device_model, same_bits, warp_grads, warp_host  # noqa: F401
 from helpers import INPUT_NAMES
 
 pytestmark = pytest.mark.gpu
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 PARAMS = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 SUMMED = PARAMS
 STEPWISE = ("torques", "refs", "res_f")
@@ -24,29 +24,12 @@ CASES = [("laikago", 256, 1), ("laikago", 64, 2), ("human", 128, 0), ("quad", 12
 T60 = 60
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
-
-
 def _setup(robot, bs, family, dev, T=T60, seed=0, literal=False, segw=None):
-    from diffphys_amd import hip_backend, robots, synth
+    from diffphys_amd import robots, synth
 
     tpl = robots.load_template(robot)
     inp = synth.make_inputs(tpl, robot, bs=bs, nsteps=T, seed=seed, steps_per_frame=20, penetration=0.003)
-    dm = hip_backend.DeviceModel(tpl)
-    if segw is not None:
-        dm.set_segment_width(segw)
-    dm.set_kernel_family(family)
-    if literal:
-        dm.set_numeric_policy(hip_backend.NUM_LITERAL)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
-    return dm, inp, t
-
-
-def _same(a, b):
-    return torch.equal(a, b) or bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
+    return device_model(tpl, family, segw, literal), inp, dev_inputs(inp, dev)
 
 
 def _resumed_forward_case(dev, robot, bs, family, splits, **kw):
@@ -74,11 +57,11 @@ def _resumed_forward_case(dev, robot, bs, family, splits, **kw):
             assert float(g2.abs().max()) > 0.0, "contacts must be active"
             assert torch.equal(p2[0], pos[fs]) and torch.equal(v2[0], vel[fs]), "a frame at step 0 returns the state bit for bit"
             for name, a, b in (("wp_pos", p2, pos[fs:]), ("wp_vel", v2, vel[fs:]), ("grf", g2, grf[fs:]), ("jaf", j2, jaf[fs:])):
-                assert _same(a, b), (robot, family, s, name)
+                assert same_bits(a, b, nan_equal=True), (robot, family, s, name)
         for k in range(4):
-            assert _same(outs[0][k], outs[1][k]), "the resumed forward-only launch equals the resumed saving launch"
+            assert same_bits(outs[0][k], outs[1][k], nan_equal=True), "the resumed forward-only launch equals the resumed saving launch"
         for name, a, b in zip(("body_q", "body_qd", "body_f", "clamp mask"), traj, traj2):
-            assert _same(a[s:], b), (robot, family, s, "saved " + name)
+            assert same_bits(a[s:], b, nan_equal=True), (robot, family, s, "saved " + name)
         print("%s bs=%d family %d split %d: resumed forward continues bit for bit (frames, wrenches, saved trajectory)" % (robot, bs, family, s))
 
 
@@ -149,31 +132,14 @@ def test_chained_adjoint_equals_the_single_adjoint(dev, robot, bs, family):
     print("%s bs=%d family %d: chained adjoint (split 23) equals the single adjoint bit for bit" % (robot, bs, family))
 
 
-class _Host:  # the attributes ForwardWarp reads from `self`
-    pass
-
-
-def _host(robot, bs, T, f2s, dt, dev, K=None, attr=True):
-    from diffphys_amd import robots
-
-    h = _Host()
-    h.env = robots.env_from_template(robot, bs, device=dev)
-    h.num_envs, h.steps_idx, h.frame2step, h.dt = bs, range(T), f2s, dt
-    if attr:
-        h.checkpoint_steps = K
-    return h
-
-
-def _warp_grads(robot, bs, T, f2s, dt, t_in, ap, av, dev, K, cls=None, attr=True):
-    """ForwardWarp.apply + backward of sum(pos * ap) + sum(vel * av) -> (pos, vel, grfs, grads by input name)"""
+def _warp_grads(robot, bs, T, f2s, dt, t_in, ap, av, dev, K, attr=True):
+    """ForwardWarp.apply + backward of sum(pos * ap) + sum(vel * av) -> (pos, vel, grfs, grads by input name).  attr=False: the host has no
+    ``checkpoint_steps`` attribute at all"""
     from diffphys_amd import dp_model
 
-    h = _host(robot, bs, T, f2s, dt, dev, K, attr)
-    t = {k: t_in[k].detach().clone().requires_grad_(True) for k in INPUT_NAMES}
-    pos, vel = dp_model.ForwardWarp.apply(*[t[k] for k in INPUT_NAMES], h)
-    ((pos * ap).sum() + (vel * av).sum()).backward()
-    g = {k: t[k].grad for k in INPUT_NAMES}
-    return pos.detach(), vel.detach(), [x.detach() for x in h.grfs], g
+    h = warp_host(robot, bs, T, f2s, dt, dev, K) if attr else warp_host(robot, bs, T, f2s, dt, dev)
+    pos, vel, g = warp_grads(dp_model.ForwardWarp, INPUT_NAMES, t_in, h, ap, av)
+    return pos, vel, [x.detach() for x in h.grfs], g
 
 
 def _dist(w):
@@ -197,7 +163,7 @@ def test_summed_gradients_vs_float64_adjoint_of_own_trajectory(dev, oracle_libs,
     r = own_trajectory_check(dm, tpl, inp, dev, hitlog_check=False)
     bs, T = len(r["worst"]), inp["nsteps"]
     assert (r["touch_counts"] > 0).any(), "contacts must be active"
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
+    t = dev_inputs(inp, dev, SEEDED)
     worst = lambda e, keys: np.max(np.stack([e[k] for k in keys]), axis=0)
     w1, w1s = r["worst"], worst(r["errs"], SUMMED)
     print("%s %s %d envs x %d steps, single launch : all tensors %s | the five sums %s" % (cfg, name, bs, T, _dist(w1), _dist(w1s)))
@@ -247,7 +213,7 @@ def _long_inputs(bs, T0, R, dev, seed=21):
 
     tpl = robots.load_template("laikago")
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T0, seed=seed, seqs=("mi-trot", "mi-spin"), penetration=0.003)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     for k in ("torques", "res_f", "refs"):
         t[k] = t[k].repeat((R,) + (1,) * (t[k].dim() - 1)).contiguous()
     return tpl, inp, t
@@ -275,7 +241,7 @@ def test_forward_warp_checkpointed_end_to_end_and_memory(dev):
     from diffphys_amd import dp_model
 
     x = {k: t[k].requires_grad_(True) for k in INPUT_NAMES}   # the inputs themselves carry the gradients: no copies inside the measurement
-    h = _host("laikago", bs, T, f2s, inp["dt"], dev, K)
+    h = warp_host("laikago", bs, T, f2s, inp["dt"], dev, K)
     gc.collect()
     torch.cuda.synchronize()
     base = torch.cuda.memory_allocated()
@@ -333,8 +299,8 @@ def test_forward_warp_state_chains_through_autograd(dev):
     x = {k: t[k].detach().clone().requires_grad_(True) for k in ("q_init", "qd_init") + PARAMS + ("body_mass",)}
     c1 = {k: t[k][:W].detach().clone().requires_grad_(True) for k in ("torques", "res_f", "refs")}
     c2 = {k: t[k][W:].detach().clone().requires_grad_(True) for k in ("torques", "res_f", "refs")}
-    h1 = _host(robot, bs, W, [0, 20, 30], dt, dev)
-    h2 = _host(robot, bs, W, [10, 30], dt, dev)
+    h1 = warp_host(robot, bs, W, [0, 20, 30], dt, dev, None)
+    h2 = warp_host(robot, bs, W, [10, 30], dt, dev, None)
     tail = [x[k] for k in ("target_ke", "target_kd", "body_mass", "body_inv_mass", "body_inertia", "body_inv_inertia")]
     pa, va = dp_model.ForwardWarp.apply(x["q_init"], x["qd_init"], c1["torques"], c1["res_f"], c1["refs"], *tail, h1)
     pb, vb = dp_model.ForwardWarpState.apply(pa[-1], va[-1], c2["torques"], c2["res_f"], c2["refs"], *tail, h2)
@@ -414,7 +380,7 @@ def test_resumed_refusals_and_zero_steps(dev):
         sp[0, 3, 2] = float("nan")   # raw: not scrubbed
         g0 = dm.rollout_backward(bs, 0, dt, None, None, none[0], none[2], *par, [0], ws0, sp, sv, state0=state)
         want = torch.cat([sp[0], sv[0]], dim=1)
-        assert _same(g0["state0"], want) and bool(torch.isnan(g0["state0"][3, 2]))
+        assert same_bits(g0["state0"], want, nan_equal=True) and bool(torch.isnan(g0["state0"][3, 2]))
 
 
 def test_checkpointed_nan_policy_and_todays_path(dev):
@@ -475,7 +441,7 @@ def test_a_horizon_the_single_adjoint_cannot_hold(dev):
     for K in (150, 333):
         from diffphys_amd import dp_model
 
-        h = _host("laikago", bs, T, f2s, inp["dt"], dev, K)
+        h = warp_host("laikago", bs, T, f2s, inp["dt"], dev, K)
         x = {k: t[k].requires_grad_(True) for k in INPUT_NAMES}   # (no clones: the controls are 25 GB)
         for v in x.values():
             v.grad = None

@@ -20,11 +20,11 @@ import pytest
 import torch
 
 from generated_robots import ROLLOUT_ROBOTS, TENSORS, joint_class, oracle_pair, robot, rollout_case, yardstick
+from gpu_harness import FWD, dev, dev_inputs, device_model  # noqa: F401
 from helpers import INPUT_NAMES, own_trajectory_check, relmax
 
 pytestmark = pytest.mark.gpu
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 PARAMS = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 STEPWISE = ("torques", "res_f", "refs")
 BS = 3
@@ -38,19 +38,8 @@ ENTRY_CASES = [("mixed25", 0), ("cmp20", 0), ("worldmix9", 0), ("rev12", 1), ("r
 case_id = lambda c: "-".join(str(x) for x in c if x is not None)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
-
-
 def _model(name, family=0, segw=None):
-    from diffphys_amd import hip_backend
-
-    dm = hip_backend.DeviceModel(robot(name))
-    if segw is not None:
-        dm.set_segment_width(segw)
-    dm.set_kernel_family(family)
+    dm = device_model(robot(name), family, segw)
     assert dm.kernel_family()[1] == (name == "rev12"), "quad-lane eligible: the revolute-only robot of at most 16 bodies"
     return dm
 
@@ -60,10 +49,6 @@ def _forward_reference(name, T):
     """(template, inputs, fp32 oracle, float64 oracle), every state a frame: computed once per (robot, horizon), shared, never written"""
     tpl, inp = rollout_case(name, T, 0, bs=BS, every_state=True)
     return (tpl, inp) + oracle_pair(tpl, inp)
-
-
-def _dev_inputs(inp, dev, names=INPUT_NAMES):
-    return {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in names}
 
 
 def _bar_a(tag, out, st32, st64):
@@ -86,7 +71,7 @@ def test_forward_every_state_against_float64(dev, oracle_libs, case, T):
     name, family, segw = case
     tpl, inp, st32, st64 = _forward_reference(name, T)
     dm = _model(name, family, segw)
-    t = _dev_inputs(inp, dev)
+    t = dev_inputs(inp, dev)
     f2s = inp["frame2step"]
     assert f2s == list(range(T + 1))
     pos, vel, grf, jaf, _ = dm.rollout_forward(BS, T, inp["dt"], *[t[k] for k in FWD], frame2step=f2s)
@@ -144,7 +129,7 @@ def _entries(name, family):
     c.tpl, c.inp = rollout_case(name, T12, 0, bs=BS)
     c.dm = _model(name, family)
     c.dt = c.inp["dt"]
-    c.t = _dev_inputs(c.inp, dev)
+    c.t = dev_inputs(c.inp, dev)
     rng = np.random.RandomState(5)
     N = BS * c.dm.nb
     c.ap = torch.from_numpy((rng.randn(len(F2S), N, 7) * 1e-3).astype(np.float32)).to(dev)
@@ -322,7 +307,7 @@ def test_resumed_launch_of_one_body_whose_com_is_off_every_axis(dev):
     inp = dict(q_init=q.reshape(-1), qd_init=rng.randn(bs * 6), torques=np.zeros((T, bs * 6)), res_f=rng.randn(T, bs, 6) * 0.05, refs=np.zeros((T, bs * 6)),
                target_ke=np.zeros(bs * 6), target_kd=np.zeros(bs * 6), body_mass=mass, body_inv_mass=1 / mass, body_inertia=inertia,
                body_inv_inertia=np.linalg.inv(inertia))
-    t = _dev_inputs(inp, dev)
+    t = dev_inputs(inp, dev)
     dm = hip_backend.DeviceModel(tpl)
     par = [t[k] for k in PARAMS]
     full = list(range(T + 1))

@@ -16,9 +16,10 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import FWD, dev, dev_inputs  # noqa: F401
 from generated_robots import GROUND_WRENCH_ROBOTS, ROBOTS, robot, rollout_inputs
 from ground_wrench_common import candidate_probe, wrench_and_state_grads
-from helpers import INPUT_NAMES, build_template, chain2, relmax
+from helpers import build_template, chain2, relmax
 from joint_coords_ref import coords_of, fk_states, joint_coords, oracle_template, random_coords, tangent
 
 pytestmark = pytest.mark.gpu
@@ -31,12 +32,6 @@ SETS = {"mixed25": 23, "rev64": 9, "cmp31": 17, "mixed129": 3, "rev256": 2, "wor
 GW_SETS = {"mixed25": 12, "rev64": 5, "cmp31": 10, "mixed129": 3, "free1": 200}
 GW_SEED = {"mixed25": 0, "rev64": 1, "cmp31": 0, "mixed129": 0, "free1": 0}   # (rev64: 0 puts the fp32 yardstick 1.2e-4 from float64)
 STRIDE_SEED = 1000   # (900: a candidate 9e-7 m from the ground at k = 64)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def bar(what, gpu, f32, ref, floor=1e-5):
@@ -186,7 +181,6 @@ def test_joint_coords_round_trip_through_the_products_own_kernels(name, dev):
         bar(tag + " against the float64 round trip", got, trip[torch.float32][k], trip[torch.float64][k])
 
 
-FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 
 
 @functools.lru_cache(maxsize=None)
@@ -200,7 +194,7 @@ def sim_case(name):
     inp = rollout_inputs(tpl, bs=3, T=8, seed=1)
     env = sim.Model.from_template(tpl, 3, dev)
     dm = hip_backend.device_model(env)
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     pos, vel, grf, jaf, ws = dm.rollout_forward(3, 8, inp["dt"], *[t[k] for k in FWD], frame2step=inp["frame2step"])
     return dict(tpl=tpl, inp=inp, env=env, nb=dm.nb, t=t, pos=pos, vel=vel, grf=grf)
 

@@ -22,23 +22,9 @@ import pytest
 import torch
 
 from helpers import GRAD_LEAD, INPUT_NAMES, grad_env_errors, relmax, tight_inputs
-from test_gpu_parity import BWD, FWD, gpu_rollout
+from gpu_harness import BWD, FWD, SEEDED, c_oracles, dev, dev_inputs, gpu_rollout  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
-
-
-def _oracle(tpl, inp, dtype):
-    from oracle.ref_c import RefC
-
-    rc = RefC(tpl, dtype)
-    st = rc.rollout_forward(inp, inp["nsteps"], inp["frame2step"], inp["dt"])
-    return st, rc.rollout_backward(st, inp["adj_pos"], inp["adj_vel"])
 
 
 CAPS = {  # absolute caps (relmax per tensor): pose, twist, wrench, gradient
@@ -57,8 +43,8 @@ def test_short_horizon_tight(name, T, dev, oracle_libs):
     bs = 48
     inp = tight_inputs(tpl, name, bs, T, seed=11 + T)
     out = gpu_rollout(hip_backend.DeviceModel(tpl), inp, dev)
-    s64, g64 = _oracle(tpl, inp, np.float64)
-    s32, g32 = _oracle(tpl, inp, np.float32)
+    s64, g64 = c_oracles(tpl, inp, np.float64)
+    s32, g32 = c_oracles(tpl, inp, np.float32)
     assert np.abs(s64["grf"]).max() > 10.0 and np.abs(s64["jaf"]).max() > 1.0, "contacts and joints must be loaded"
     cap_p, cap_v, cap_w, cap_g = CAPS[name]
 
@@ -98,8 +84,8 @@ def test_velocity_clamps_take_the_forward_decision(name, dev, oracle_libs):
     qd[::2, 3:6] = rng.uniform(-8.0, 8.0, (bs // 2, 3))                        # ... every other env: linear part inside them
     inp["q_init"], inp["qd_init"] = np.ascontiguousarray(q.reshape(-1), np.float32), np.ascontiguousarray(qd.reshape(-1), np.float32)
     out = gpu_rollout(hip_backend.DeviceModel(tpl), inp, dev)
-    s64, g64 = _oracle(tpl, inp, np.float64)
-    s32, g32 = _oracle(tpl, inp, np.float32)
+    s64, g64 = c_oracles(tpl, inp, np.float64)
+    s32, g32 = c_oracles(tpl, inp, np.float32)
     assert np.allclose(np.asarray(s64["grf"])[0], inp["res_f"][0], atol=1e-6), "no contacts in this test: grf is the residual wrench alone"
     vel_T = np.asarray(s64["wp_vel"]).reshape(2, bs, nb, 6)[1]
     assert (np.abs(np.abs(vel_T) - 10.0) < 1e-12).mean() > 0.1, "a good share of the final twists must sit on the clamps"
@@ -286,7 +272,7 @@ def test_frames_validated_on_the_host_and_final_state_frame(dev, oracle_libs):
         inp["adj_pos"] = (rng.randn(F, bs * 13, 7) * 1e-3).astype(np.float32)
         inp["adj_vel"] = (rng.randn(F, bs * 13, 6) * 1e-3).astype(np.float32)
         out = gpu_rollout(dm, inp, dev)
-        st, gr = _oracle(tpl, inp, np.float32)
+        st, gr = c_oracles(tpl, inp, np.float32)
         assert out["wp_pos"].shape == (F, bs * 13, 7)
         if F == 0:
             assert all(np.abs(v).max() == 0 for v in out["grads"].values())
@@ -335,7 +321,7 @@ def test_per_env_joint_X_p_binding(dev, oracle_libs):
         F = len(inp["frame2step"])
         sub["adj_pos"] = np.ascontiguousarray(inp["adj_pos"].reshape(F, bs, nb, 7)[:, e])
         sub["adj_vel"] = np.ascontiguousarray(inp["adj_vel"].reshape(F, bs, nb, 6)[:, e])
-        st, gr = _oracle(te, sub, np.float32)
+        st, gr = c_oracles(te, sub, np.float32)
         assert relmax(out["wp_pos"].reshape(F, bs, nb, 7)[:, e], st["wp_pos"].reshape(F, nb, 7)) < 5e-5, e
         assert relmax(out["grads"]["q_init"].reshape(bs, -1)[e], gr["q_init"]) < 2e-2, e
     # FK uses env i % n_envs of the binding (the reference runs eval_fk frame by frame on the same n_envs model)
@@ -499,8 +485,7 @@ def test_long_horizon_hit_log_is_complete(family, dev, oracle_libs):
     inp["qd_init"] = (rng.randn(*inp["qd_init"].shape) * 0.4).astype(np.float32)      # kicked: feet leave and hit the ground
     dm = hip_backend.DeviceModel(tpl)
     dm.set_kernel_family(family)
-    FWD = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES}
+    t = dev_inputs(inp, dev)
     pos, vel, grf, jaf, ws = dm.rollout_forward(bs, T, inp["dt"], *[t[k] for k in FWD], frame2step=list(inp["frame2step"]))
     assert dm.last_launch_info(0)["threads_per_wg"] % 192 == 0   # body, contact and cull wave per env group
     bq, bqd, bf, mask = dm.saved_trajectory(ws, bs, T)
@@ -567,7 +552,7 @@ def test_one_model_on_two_streams_at_once(dev):
     dm = hip_backend.DeviceModel(tpl)
     T = 60
     inps = [synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T, seed=30 + i, steps_per_frame=19, penetration=0.003) for i, bs in enumerate((300, 77))]
-    ts = [{k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")} for inp in inps]
+    ts = [dev_inputs(inp, dev, SEEDED) for inp in inps]
     def fwd(i):
         return dm.rollout_forward(inps[i]["q_init"].size // 19, T, inps[i]["dt"], *[ts[i][k] for k in FWD], frame2step=list(inps[i]["frame2step"]))
     def bwd(i, ws):

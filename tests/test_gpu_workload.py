@@ -9,13 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import FWD as FWD_NAMES
 from helpers import relmax
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def dev():
+def dev():   # (not gpu_harness.dev: without a GPU this module skips)
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     return torch.device("cuda:0")
@@ -70,9 +71,6 @@ class _Capture:
     def __exit__(self, *exc):
         for n, f in self.orig.items():
             setattr(self.cls, n, f)
-
-
-FWD_NAMES = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_inertia")
 
 
 def _physical(pos, vel):

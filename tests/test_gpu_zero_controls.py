@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import FWD, SEEDED, dev, dev_inputs, device_model, warp_grads, warp_host  # noqa: F401
 from helpers import GOLDEN, GRAD_LEAD, INPUT_NAMES, relmax, tight_inputs
 
 pytestmark = pytest.mark.gpu
@@ -21,12 +22,6 @@ REST = ("target_ke", "target_kd", "body_inv_mass", "body_inertia", "body_inv_ine
 STEPWISE = ("torques", "res_f", "refs")
 # which of the two controls a launch is GIVEN: (torques, res_f)
 MODES = {"res_f-null": (True, False), "torques-null": (False, True), "both-null": (False, False)}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "run with -m gpu on a GPU box"
-    return torch.device("cuda:0")
 
 
 def _template(key):
@@ -49,7 +44,7 @@ def _inputs(key, bs, T, f2s, dev, seed=5):
     inp["adj_vel"] = rng.randn(len(f2s), bs * nb, 6).astype(np.float32)
     inp["torques"] = np.zeros_like(inp["torques"])
     inp["res_f"] = np.zeros_like(inp["res_f"])
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES + ("adj_pos", "adj_vel")}
+    t = dev_inputs(inp, dev, SEEDED)
     return tpl, float(inp["dt"]), t, inp
 
 
@@ -92,27 +87,15 @@ def _contacts_active(dm, ws_i32, bs, T):
     assert (log[..., 0] != 0).any(), "no contact in any env-step: the case would pass vacuously"
 
 
-def _same(a, b, what):
+def _same(a, b, what):   # (not gpu_harness.same_bits: two dicts of tensors with the same keys, and it asserts)
     assert set(a) == set(b), (what, sorted(a), sorted(b))
     for k in a:
         assert torch.equal(a[k], b[k]), (what, k)
 
 
-def _model(tpl, family, literal, segw=None):
-    from diffphys_amd import hip_backend
-
-    dm = hip_backend.DeviceModel(tpl)
-    if segw:
-        dm.set_segment_width(segw)
-    dm.set_kernel_family(family)
-    if literal:
-        dm.set_numeric_policy(hip_backend.NUM_LITERAL)
-    return dm
-
-
 def _variant_case(dev, key, bs, T, f2s, fam_fwd, fam_bwd, literal, segw=None, check=None):
     tpl, dt, t, _ = _inputs(key, bs, T, f2s, dev)
-    dm = _model(tpl, fam_fwd, literal, segw)
+    dm = device_model(tpl, fam_fwd, segw, literal)
     o_ref, g_ref = _rollout(dm, bs, T, dt, f2s, t, None, fam_bwd=fam_bwd)
     _contacts_active(dm, o_ref["ws"], bs, T)
     if check:
@@ -185,7 +168,7 @@ def test_forward_only_composes(dev, key, bs, T, f2s, family):
     """2: the same robots with a NULL workspace and NULL controls: frame outputs equal the forward-only launch with zero tensors and the
     saving launch with zero tensors."""
     tpl, dt, t, _ = _inputs(key, bs, T, f2s, dev)
-    dm = _model(tpl, family, False)
+    dm = device_model(tpl, family)
     o_save, _ = _rollout(dm, bs, T, dt, f2s, t, None)
     _contacts_active(dm, o_save.pop("ws"), bs, T)
     o_ref, _ = _rollout(dm, bs, T, dt, f2s, t, None, save=False)
@@ -202,10 +185,10 @@ def test_fused_entries(dev, key, bs, T, f2s, family, ride):
     """3: rollout_forward_traj_loss / rollout_backward_traj_loss, with and without the FK ride: loss table, reduced, scale, seeds, FK rows,
     frame outputs, workspace and all gradients (the LOSS instantiations of both Laikago families and of the split compound forward)."""
     tpl, dt, t, _ = _inputs(key, bs, T, f2s, dev)
-    dm = _model(tpl, family, False)
+    dm = device_model(tpl, family)
     nb, nq, nqd, F = dm.nb, dm.nq, dm.nqd, len(f2s)
     gen = torch.Generator().manual_seed(11)
-    pos0 = dm.rollout_forward(bs, T, dt, *[t[k] for k in ("q_init", "qd_init", "torques", "res_f", "refs") + REST], frame2step=f2s,
+    pos0 = dm.rollout_forward(bs, T, dt, *[t[k] for k in FWD], frame2step=f2s,
                               save_trajectory=False, want_forces=False)[0]
     tgt = (pos0.view(F, bs, nb, 7).permute(1, 0, 2, 3) + 0.05 * torch.randn(bs, F, nb, 7, generator=gen).to(dev)).contiguous()
     jq = (t["q_init"].view(1, bs, nq) + 0.1 * torch.randn(F, bs, nq, generator=gen).to(dev)).contiguous()
@@ -243,7 +226,7 @@ def test_resumed_windows_chain(dev):
     key, bs, T, s = "laikago", 6, 24, 9
     f2s = [0, 9, 24]
     tpl, dt, t, _ = _inputs(key, bs, T, f2s, dev)
-    dm = _model(tpl, 1, False)
+    dm = device_model(tpl, 1)
     o_one, g_one = _rollout(dm, bs, T, dt, f2s, t, "both-null")
     _contacts_active(dm, o_one["ws"], bs, T)
 
@@ -277,7 +260,7 @@ def test_selective_adjoint_composes(dev, key, bs, family):
     """4: res_f NULL with g_res_f wanted / declined, torques NULL with only g_refs wanted, both NULL with all three declined."""
     T, f2s = 12, [0, 5, 12]
     tpl, dt, t, _ = _inputs(key, bs, T, f2s, dev)
-    dm = _model(tpl, family, False)
+    dm = device_model(tpl, family)
     o_ref, g_ref = _rollout(dm, bs, T, dt, f2s, t, None)
     _contacts_active(dm, o_ref["ws"], bs, T)
     for mode, want in (("res_f-null", ("torques", "res_f", "refs")), ("res_f-null", ("torques", "refs")), ("torques-null", ("refs",)),
@@ -289,28 +272,6 @@ def test_selective_adjoint_composes(dev, key, bs, family):
             assert torch.equal(g[k], g_ref[k]), (key, mode, want, k)
 
 
-class _Host:  # the attributes ForwardWarp reads from `self`
-    pass
-
-
-def _host(robot, bs, T, f2s, dt, dev, K=None):
-    from diffphys_amd import robots
-
-    h = _Host()
-    h.env = robots.env_from_template(robot, bs, device=dev)
-    h.num_envs, h.steps_idx, h.frame2step, h.dt, h.checkpoint_steps = bs, range(T), f2s, dt, K
-    return h
-
-
-def _apply(cls, names, tin, absent, ap, av, h):
-    """cls.apply with every tensor input requiring a gradient and None in the `absent` positions -> (pos, vel, grads by name)"""
-    x = {k: (None if k in absent else tin[k].detach().clone().requires_grad_(True)) for k in names}
-    pos, vel = cls.apply(*[x[k] for k in names], h)
-    ((pos * ap).sum() + (vel * av).sum()).backward()
-    torch.cuda.synchronize()
-    return pos.detach(), vel.detach(), {k: (None if v is None else v.grad) for k, v in x.items()}
-
-
 @pytest.mark.parametrize("K", [None, 5], ids=["single-launch", "checkpoint-5"])
 def test_forward_warp_with_none_controls(dev, monkeypatch, K):
     """5: ForwardWarp.apply(q, qd, None, None, refs, ...) against the same call with zero tensors: outputs and the .grad of every tensor
@@ -320,10 +281,10 @@ def test_forward_warp_with_none_controls(dev, monkeypatch, K):
     bs, T = 6, 17
     f2s = [0, 8, 17]
     tpl, dt, t, _ = _inputs("laikago", bs, T, f2s, dev)
-    h = _host("laikago", bs, T, f2s, dt, dev, K)
-    pz, vz, gz = _apply(dp_model.ForwardWarp, INPUT_NAMES, t, (), t["adj_pos"], t["adj_vel"], h)
+    h = warp_host("laikago", bs, T, f2s, dt, dev, K)
+    pz, vz, gz = warp_grads(dp_model.ForwardWarp, INPUT_NAMES, t, h, t["adj_pos"], t["adj_vel"])
     assert float(torch.stack([x.abs().max() for x in h.grfs]).max()) > 0.0, "contacts must be active"
-    pn, vn, gn = _apply(dp_model.ForwardWarp, INPUT_NAMES, t, ("torques", "res_f"), t["adj_pos"], t["adj_vel"], h)
+    pn, vn, gn = warp_grads(dp_model.ForwardWarp, INPUT_NAMES, t, h, t["adj_pos"], t["adj_vel"], absent=("torques", "res_f"))
     assert torch.equal(pn, pz) and torch.equal(vn, vz)
     assert gn["torques"] is None and gn["res_f"] is None
     for k in INPUT_NAMES:
@@ -338,7 +299,7 @@ def test_forward_warp_with_none_controls(dev, monkeypatch, K):
         return returned[-1]
 
     monkeypatch.setattr(dp_model.ForwardWarp, "backward", staticmethod(spy))
-    _apply(dp_model.ForwardWarp, INPUT_NAMES, t, ("torques", "res_f"), t["adj_pos"], t["adj_vel"], h)
+    warp_grads(dp_model.ForwardWarp, INPUT_NAMES, t, h, t["adj_pos"], t["adj_vel"], absent=("torques", "res_f"))
     assert len(returned) == 1 and returned[0][2] is None and returned[0][3] is None and returned[0][4] is not None
 
 
@@ -349,18 +310,18 @@ def test_forward_warp_state_with_none_controls(dev):
     bs, T, s = 6, 17, 8
     f2s = [0, 8, 17]
     tpl, dt, t, _ = _inputs("laikago", bs, T, f2s, dev)
-    dm = _model(tpl, 0, False)
-    pos, vel = dm.rollout_forward(bs, T, dt, *[t[k] for k in ("q_init", "qd_init", "torques", "res_f", "refs") + REST], frame2step=f2s,
+    dm = device_model(tpl, 0)
+    pos, vel = dm.rollout_forward(bs, T, dt, *[t[k] for k in FWD], frame2step=f2s,
                                   save_trajectory=False)[:2]
     names = ("body_q0", "body_qd0") + INPUT_NAMES[2:]
     tin = dict(t, body_q0=pos[1].clone(), body_qd0=vel[1].clone())
     for k in STEPWISE:
         tin[k] = t[k][s:].contiguous()
-    h = _host("laikago", bs, T - s, [0, T - s], dt, dev)
+    h = warp_host("laikago", bs, T - s, [0, T - s], dt, dev, None)
     ap, av = t["adj_pos"][1:], t["adj_vel"][1:]
-    pz, vz, gz = _apply(dp_model.ForwardWarpState, names, tin, (), ap, av, h)
+    pz, vz, gz = warp_grads(dp_model.ForwardWarpState, names, tin, h, ap, av)
     assert float(torch.stack([x.abs().max() for x in h.grfs]).max()) > 0.0, "contacts must be active"
-    pn, vn, gn = _apply(dp_model.ForwardWarpState, names, tin, ("torques", "res_f"), ap, av, h)
+    pn, vn, gn = warp_grads(dp_model.ForwardWarpState, names, tin, h, ap, av, absent=("torques", "res_f"))
     assert torch.equal(pn, pz) and torch.equal(vn, vz) and torch.equal(pn[1], pos[2])
     assert gn["torques"] is None and gn["res_f"] is None
     for k in names:
@@ -381,10 +342,9 @@ def test_peak_memory_drops_by_exactly_the_two_tensors(dev):
     assert (nb, nqd) == (13, 18)
     inp = synth.make_inputs(tpl, "laikago", bs=bs, nsteps=T, seed=2, steps_per_frame=100, penetration=0.003)
     f2s = [int(x) for x in inp["frame2step"]]
-    t = {k: torch.from_numpy(np.ascontiguousarray(inp[k], dtype=np.float32)).to(dev) for k in INPUT_NAMES if k not in ("torques", "res_f")}
-    ap = torch.from_numpy(np.ascontiguousarray(inp["adj_pos"], dtype=np.float32)).to(dev)
-    av = torch.from_numpy(np.ascontiguousarray(inp["adj_vel"], dtype=np.float32)).to(dev)
-    h = _host("laikago", bs, T, f2s, float(inp["dt"]), dev, K)
+    t = dev_inputs(inp, dev, [k for k in INPUT_NAMES if k not in ("torques", "res_f")])
+    ap, av = dev_inputs(inp, dev, ("adj_pos", "adj_vel")).values()
+    h = warp_host("laikago", bs, T, f2s, float(inp["dt"]), dev, K)
     expect = T * bs * (nb * 6 + nqd) * 4
 
     def peak(with_tensors):
@@ -477,7 +437,7 @@ def test_refusals(dev):
 
     bs, T, f2s = 6, 12, [0, 5, 12]
     tpl, dt, t, _ = _inputs("laikago", bs, T, f2s, dev)
-    dm = _model(tpl, 0, False)
+    dm = device_model(tpl, 0)
     lib = hip_backend.lib()
     nb, F = dm.nb, len(f2s)
     full = lambda *s: torch.full(s, SENTINEL, dtype=torch.float32, device=dev)
@@ -495,9 +455,8 @@ def test_refusals(dev):
     # the adjoint: a real workspace, sentinel-filled gradients
     _, _, _, _, ws_ok = dm.rollout_forward(bs, T, dt, t["q_init"], t["qd_init"], None, None, t["refs"], *[t[k] for k in REST], frame2step=f2s)
     g = {k: v.fill_(SENTINEL) for k, v in dm._alloc_grads(bs, T, dev).items()}
-    order = ("q_init", "qd_init", "torques", "res_f", "refs") + REST
     rc = lib.pd_rollout_backward(dm.h, bs, T, ctypes.c_float(dt), ptr(t["q_init"]), ptr(t["qd_init"]), None, None, *[ptr(t[k]) for k in REST],
-                                 F, f2s_c, ptr(ws_ok), ptr(t["adj_pos"]), ptr(t["adj_vel"]), *[ptr(g[k]) for k in order], hip_backend._stream())
+                                 F, f2s_c, ptr(ws_ok), ptr(t["adj_pos"]), ptr(t["adj_vel"]), *[ptr(g[k]) for k in FWD], hip_backend._stream())
     torch.cuda.synchronize()
     msg = lib.pd_last_error().decode()
     assert rc != 0 and "null device pointer" in msg and "refs" in msg, (rc, msg)
@@ -531,7 +490,7 @@ def test_null_launch_against_the_float64_oracle(dev, oracle_libs, key, bs, famil
     tpl, dt, t, inp = _inputs(key, bs, T, f2s, dev)
     inp = dict(inp, frame2step=f2s, nsteps=T)
     assert not inp["torques"].any() and not inp["res_f"].any()
-    dm = _model(tpl, family, False)
+    dm = device_model(tpl, family)
     o, g = _rollout(dm, bs, T, dt, f2s, t, "both-null")
     _contacts_active(dm, o["ws"], bs, T)
     res = {}

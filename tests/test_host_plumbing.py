@@ -205,3 +205,26 @@ def test_time_mlp_linear_functions_match_torch_autograd():
     shared = {}
     b1, b2 = mlp(t, shared), mlp(t, shared)   # the second call reads the cached mapping and Fourier features
     assert torch.equal(a, b1) and torch.equal(a, b2) and len(shared) == 2
+
+
+def test_rollout_operand_order_is_the_signatures():
+    """hip_backend.ROLLOUT_INPUTS / ADJOINT_INPUTS are the tensor operands of DeviceModel's four rollout entries after
+    (self, bs, nsteps, dt), in call order: every caller that spreads a dict over them (tests/gpu_harness.py, scripts/gpu_common.py)
+    is held to the positional signatures here."""
+    import inspect
+
+    from diffphys_amd import hip_backend
+
+    def operands(fn):
+        names = list(inspect.signature(fn).parameters)
+        assert names[:4] == ["self", "bs", "nsteps", "dt"]
+        return tuple(names[4:])
+
+    dm = hip_backend.DeviceModel
+    n = len(hip_backend.ROLLOUT_INPUTS)
+    assert n == 10
+    for fn in (dm.rollout_forward, dm.rollout_forward_traj_loss):
+        assert operands(fn)[:n] == hip_backend.ROLLOUT_INPUTS, fn.__name__
+    for fn in (dm.rollout_backward, dm.rollout_backward_traj_loss):
+        assert operands(fn)[:n - 1] == hip_backend.ADJOINT_INPUTS, fn.__name__
+    assert hip_backend.ADJOINT_INPUTS == tuple(k for k in hip_backend.ROLLOUT_INPUTS if k != "res_f")

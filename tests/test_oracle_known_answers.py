@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import build_template, chain2, default_inputs, free_body
+from helpers import INPUT_NAMES, build_template, chain2, default_inputs, free_body
 from diffphys_amd import sim
 from oracle import ref_torch as rt
 from oracle.ref_c import RefC
@@ -18,8 +18,7 @@ G = 9.80665
 def torch_states(tpl, inp, nsteps):
     T = rt.Template(tpl, torch.float64)
     t = {k: torch.tensor(v, dtype=torch.float64) for k, v in inp.items()}
-    q, qd = rt.rollout(T, *[t[k] for k in ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_mass",
-                                             "body_inv_mass", "body_inertia", "body_inv_inertia")],
+    q, qd = rt.rollout(T, *[t[k] for k in INPUT_NAMES],
                        nsteps=nsteps, frame2step=[0], dt=DT, return_all=True)
     return q.numpy(), qd.numpy()
 
@@ -181,8 +180,7 @@ def test_autograd_vs_finite_differences():
     inp["qd_init"] = rng.randn(*inp["qd_init"].shape) * 0.1
     inp["q_init"][1] -= 0.01  # push the feet into the ground so contacts are active
     T = rt.Template(tpl, torch.float64)
-    names = ("q_init", "qd_init", "torques", "res_f", "refs", "target_ke", "target_kd", "body_mass", "body_inv_mass",
-             "body_inertia", "body_inv_inertia")
+    names = INPUT_NAMES
     wpos = torch.tensor(rng.randn(2, bs * T.nb, 7))
     wvel = torch.tensor(rng.randn(2, bs * T.nb, 6))
 

@@ -143,7 +143,7 @@ def test_mocap_pipeline_against_the_reference(mocap):
 
 
 @pytest.fixture(scope="module")
-def dev():
+def dev():   # (not gpu_harness.dev: this one loads the library first)
     from diffphys_amd import hip_backend
 
     hip_backend.lib()
