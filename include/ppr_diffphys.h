@@ -439,13 +439,52 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * A table whose nb is not the call's a_broadcast, or a candidate range that leaves the table's nc, reads no candidate: the element is
  * then a body without candidates.
  *
+ * Joint wrench of body states -- per body what the joint pass of a step adds to body_f: the PD force, the limit force and the attachment
+ * springs of its own joint and of its children's (eval_body_joints, diffphys/integrator_euler.py:289-451, as a function of ONE state and
+ * the joints' controls; a differentiable jaf is built on it -- DESIGN.md section 8):
+ *   PD_POSE_JOINT_WRENCH   b = rows [n][25]: a state row as for PD_POSE_GROUND_WRENCH, then the controls of this body's joint in dof
+ *                          slots k = 0..2: act[k] at 13 + k, target[k] at 16 + k, ke[k] at 19 + k, kd[k] at 22 + k.  A REVOLUTE joint
+ *                          uses slot 0, a COMPOUND joint slots 0..2, FREE and FIXED joints none; an unused slot never enters
+ *                          arithmetic (it may hold anything) and its gradient is written as 0.  a_broadcast = nb as above (nb < 1 or
+ *                          n % nb != 0 is refused at every n; nb <= 256).  a = ONE joint-force table for all elements -> out [n][6] =
+ *                          (torque, force) per body.  Joint i (= child body i, frames and errors as for PD_POSE_JOINT_COORDS) makes
+ *                          the pair (t_i, f_i), with ake / akd the attachment gains, ads = 0.01, x_err = (p_c - p_p) - R(q_p) p_pj
+ *                          (p_c - p_pj without parent), v_err = v_c - v_p, r_c = -R(q_c) com_c, r_p = R(q_p) (p_pj - com_p):
+ *                            FIXED     t = R(q_wj) ang_err ake + w_err akd ads, ang_err = normalize(r_err.xyz) 2 acos(r_err.w) in its
+ *                                      scale-invariant form (2 atan2(|v|, w) / |v|, series near 0: finite at the identity)
+ *                            REVOLUTE  t = axis_p jf + (axis_p x axis_c) ake + (w_err - axis_p qd) akd ads, with axis_p = R(q_wj) axis,
+ *                                      axis_c = R(q_c) axis, q the twist angle (through atan2), qd = w_err . axis_p and
+ *                                      jf = ke (q - target) + kd qd + act - limit force(q, qd) (integrator_euler.py:261-286)
+ *                            COMPOUND  t = clamp(sum_k axw_k jf_k, +-1e4) per component on the angles, world axes axw_k = R_wj R_off a_k
+ *                                      and measured rates of PD_POSE_JOINT_COORDS (rate mode 0), jf_k as above for slot k
+ *                            f = x_err ake + v_err akd   (COMPOUND: clamped to +-1e4 per component);   FREE: no pair
+ *                          out_i = -(t_i + r_c,i x f_i, f_i) + sum over the children c of i, in the table's child order, of
+ *                          (t_c + r_p,c x f_c, f_c): what a rollout step adds to body_f for that state and those controls (its jaf;
+ *                          the same function in fp32, not the same bits -- the lever arms and x_err are formed here without the
+ *                          cancellation of two numbers of the size of the body's distance from the origin).  The default numeric
+ *                          policy only.  Whole state sets share a workgroup, a lane per body; a lane leaves the parent-side wrench of
+ *                          its joint in LDS and, after one barrier, adds its children's to its own side: no atomics, a set's bits
+ *                          depend neither on the run nor on n nor on the set's place in the launch.
+ *                          VJP: g_out [n][6] -> g_b [n][25], the raw partials with respect to the state (quaternion entries not
+ *                          projected) and the twelve control slots; a clamped component passes no gradient.  Limits, attachment
+ *                          gains and the table have no gradient: a non-NULL g_a is refused, at every n.
+ * The joint-force table: a 16-byte-aligned float buffer built on the host (hip_backend.joint_force_table is the one builder): the joint
+ * table above with rate mode 0, float for float (4 + 32 nb floats), followed by
+ *   4 floats                   attach_ke, attach_kd, 0, 0
+ *   then 12 floats per body    (lower, upper, limit_ke, limit_kd) of dof slots 0..2 = the template's joint_limit_*[qd_start + k];
+ *                              (-FLT_MAX, FLT_MAX, 0, 0) in a slot no dof uses
+ * A table whose nb is not the call's a_broadcast is not read beyond its first float: out / g_b are then written as zeros.  A parent
+ * index or a coordinate range outside the set is handled as for PD_POSE_JOINT_COORDS.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
- * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL and PD_POSE_CONTACT_STATE are new
- * op codes of the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8 and 10 are NOT
- * assigned and are refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal op
- * took 9, of 10 since the contact state took 11), so the three stay free for as long as the version is 9. */
+ * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE and
+ * PD_POSE_JOINT_WRENCH are new op codes of the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps:
+ * codes 7, 8, 10 and 12 are not assigned and are refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7
+ * and 8 since the centroidal op took 9, of 10 since the contact state took 11, of 12 since the joint wrench took 13), so the four stay
+ * free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
-       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11 };
+       PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11,
+       PD_POSE_JOINT_WRENCH = 13 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

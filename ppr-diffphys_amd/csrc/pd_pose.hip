@@ -17,7 +17,8 @@
 #include <hip/hip_runtime.h>
 #include "../../include/ppr_diffphys.h"
 #include "pd_device.h"  // PD_POSE_GROUND_WRENCH: the rollout kernels' own per-candidate contact code (contact_point_fwd / _adj / _adj_materials);
-                        // PD_POSE_JOINT_COORDS: twist_angle, quat_decompose_cols / _adj and the quaternion adjoints
+                        // PD_POSE_JOINT_COORDS: twist_angle, quat_decompose_cols / _adj and the quaternion adjoints;
+                        // PD_POSE_JOINT_WRENCH: those, and joint_force / _adj, fixed_ang_h, clamp3_pass
 
 // pd_host.hip: sets the text pd_last_error() returns, returns 1 (library-internal: hidden, no part of the C ABI)
 __attribute__((visibility("hidden"))) int pd_set_error(const char *msg);
@@ -454,6 +455,16 @@ struct JcJoint {  // what the forward pass and the adjoint share
 // A table the call was not sized for must not send a lane out of bounds (the host cannot validate a device buffer): a parent index
 // outside the set reads no row, and a joint whose coordinates do not lie inside [0, nq) x [0, nqd) -- or any joint of a table built for
 // another nb -- is taken as FIXED: nothing of it is read or written.
+// STRIDE: floats per row of set_rows (PD_ADJ: bare state rows; the joint wrench's rows carry the joint's controls behind the state).
+template <int STRIDE>
+__device__ __forceinline__ BodyState load_row(const float *rows, size_t i) {
+  if constexpr (STRIDE == PD_ADJ) return load_state0(rows, i);
+  const float *r = rows + i * STRIDE;
+  BodyState s;
+  s.p = ld3(r); s.r = ld4(r + 3); s.w = ld3(r + 7); s.v = ld3(r + 10);
+  return s;
+}
+template <int STRIDE = PD_ADJ>
 __device__ __forceinline__ JcJoint jc_joint(const float *tab, int nb, int nq, int nqd, int body, const BodyState &s, const float *set_rows) {
   JcJoint J;
   J.pp = V3(0, 0, 0); J.w_p = J.pp; J.v_p = J.pp; J.qp = Q4(0, 0, 0, 1);
@@ -471,7 +482,7 @@ __device__ __forceinline__ JcJoint jc_joint(const float *tab, int nb, int nq, in
   if (J.qs < 0 || J.qs + wq > nq || J.qds < 0 || J.qds + wqd > nqd) J.type = PD_JOINT_FIXED;
   if (J.parent >= nb) J.parent = -1;
   if (J.parent >= 0) {
-    const BodyState P = load_state0(set_rows, (size_t)J.parent);
+    const BodyState P = load_row<STRIDE>(set_rows, (size_t)J.parent);
     J.pp = P.p; J.qp = P.r; J.w_p = P.w; J.v_p = P.v;
     J.p_wj = P.p + qrot(P.r, J.p_pj);
     J.q_wj = qmul(P.r, J.q_pj);
@@ -905,6 +916,253 @@ __global__ __launch_bounds__(256) void k_contact_state_vjp(int n, int nb, const 
   }
 }
 
+// ---- PD_POSE_JOINT_WRENCH: the joint pass's contribution to body_f (eval_body_joints, integrator_euler.py:289-451; joint_fwd,
+// pd_device.h) as a function of ONE state set and the joints' controls, and its vector-Jacobian product with respect to the state rows
+// and the controls.  Joint i = child body i pulls its two bodies with the pair (t_i, f_i):
+//   out_i = -(t_i + r_c,i x f_i, f_i) + sum over the children c of i (t_c + r_p,c x f_c, f_c)     own joint first, then the table's child order
+//   FIXED     t = R(q_wj) (v h) ake + w_err akd ads,  v h = fixed_ang_h: the scale-invariant 2 acos(w) normalize(v) of r_err = (v, w)
+//   REVOLUTE  t = axis_p jf + (axis_p x axis_c) ake + (w_err - axis_p qd) akd ads,  jf = joint_force(twist_angle, qd = w_err . axis_p, slot 0)
+//   COMPOUND  t = clamp3(sum_k axw_k joint_force(ang_k, axw_k . w_err, slot k), 1e4) on jc_compound's angles, axes and measured rates
+//   f = x_err ake + v_err akd (COMPOUND: clamp3(., 1e4));  ads = 0.01;  FREE: no pair
+// The lever arms and the position error are formed without the rollout's cancellation of two numbers of the size of the body's distance
+// from the origin -- r_c = -R(q_c) com_c, r_p = R(q_p) (p_pj - com_p), x_err = (p_c - p_p) - R(q_p) p_pj: the same functions (the contact
+// state's cs_arm takes the same liberty).  Default numeric policy only, like the joint coordinates.
+// Rows [n][25]: the state (13), then the joint's controls in dof slots k = 0..2: act 13 + k, target 16 + k, ke 19 + k, kd 22 + k; a
+// REVOLUTE joint uses slot 0, a COMPOUND joint all three, FIXED / FREE none; an unused slot never enters arithmetic (a select keeps it
+// out) and its gradient is written as 0.  Table: the joint table (rate mode measured) followed by (attach_ke, attach_kd, 0, 0) and 12
+// floats per body, (lo, up, limit_ke, limit_kd) per slot.
+// Mapping: a lane per body, whole state sets per workgroup (set_lane).  Forward: a lane leaves the parent-side wrench of its joint in an
+// LDS slot of 6 floats (stride 7) and, after ONE barrier, adds its children's slots in the table's child order to its own side.  VJP: a
+// lane reads g_out of its own row and of its parent's, runs its joint's adjoint and hands the parent-side state adjoint over as
+// k_joint_coords_vjp does.  No atomics: a set's bits depend neither on the run nor on n nor on its place in the launch.
+enum { JW_ROW = 25, JW_HEAD = 4, JW_BODY = 12, JW_S = 7 };
+struct JwJoint {  // a joint's pair and what its adjoint needs of the forward pass
+  JcJoint J;
+  JcCompound C;
+  bool pulls;                                   // FIXED, REVOLUTE or COMPOUND: the joint has a pair
+  float act[3], tgt[3], ke[3], kd[3], jf[3];    // the used slots' controls (0 in an unused slot) and joint forces
+  const float *lim;                             // the body's 3 x (lo, up, limit_ke, limit_kd)
+  float ake, akd;
+  v3 r_c, r_p, x_err, v_err, f_raw, t_raw, t, f;
+  v3 axis_p, axis_c, axw[3];
+  float q, qd, dq_dda, dq_dw;                   // REVOLUTE
+};
+// tab[0] == nb is the caller's to check: a table of another nb has no row for this body.
+__device__ __forceinline__ void jw_eval(const float *tab, int nb, int body, const BodyState &s, const float *set_rows, JwJoint &W) {
+  W.J = jc_joint<JW_ROW>(tab, nb, (int)tab[1], (int)tab[2], body, s, set_rows);
+  const JcJoint &J = W.J;
+  const float *ext = tab + JC_HEAD + (JC_BODY + JC_MAXCH) * nb;
+  W.ake = ext[0]; W.akd = ext[1];
+  W.lim = ext + JW_HEAD + JW_BODY * body;
+  const float ake = W.ake, akd = W.akd, ads = 0.01f;
+  const int nd = J.type == PD_JOINT_REVOLUTE ? 1 : J.type == PD_JOINT_COMPOUND ? 3 : 0;
+  const float *c = set_rows + (size_t)body * JW_ROW + PD_ADJ;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const bool used = k < nd;
+    W.act[k] = used ? c[k] : 0.0f; W.tgt[k] = used ? c[3 + k] : 0.0f; W.ke[k] = used ? c[6 + k] : 0.0f; W.kd[k] = used ? c[9 + k] : 0.0f;
+    W.jf[k] = 0.0f;
+  }
+  const v3 zero = V3(0, 0, 0);
+  W.r_c = zero; W.r_p = zero; W.x_err = zero; W.v_err = zero; W.f_raw = zero; W.t_raw = zero; W.t = zero; W.f = zero;
+  W.pulls = J.type == PD_JOINT_FIXED || J.type == PD_JOINT_REVOLUTE || J.type == PD_JOINT_COMPOUND;
+  if (!W.pulls) return;  // FREE (:382)
+  W.r_c = -qrot(s.r, J.com);
+  W.x_err = s.p - J.p_pj;
+  if (J.parent >= 0) {
+    const v3 com_p = ld3(tab + JC_HEAD + JC_BODY * J.parent + 18);
+    W.r_p = qrot(J.qp, J.p_pj - com_p);
+    W.x_err = (s.p - J.pp) - qrot(J.qp, J.p_pj);
+  }
+  W.v_err = s.v - J.v_p;
+  W.f_raw = W.x_err * ake + W.v_err * akd;
+  W.f = W.f_raw;
+  if (J.type == PD_JOINT_FIXED) {  // :385-390
+    float hss_, hw_;
+    const v3 rv = qvec(J.r_err);
+    const v3 ang_err = rv * fixed_ang_h(dot(rv, rv), J.r_err.w, hss_, hw_);
+    W.t_raw = qrot(J.q_wj, ang_err) * ake + J.w_err * (akd * ads);
+    W.t = W.t_raw;
+  } else if (J.type == PD_JOINT_REVOLUTE) {  // :392-409
+    W.axis_p = qrot(J.q_wj, J.axis); W.axis_c = qrot(s.r, J.axis);
+    W.q = twist_angle(dot(qvec(J.r_err), J.axis), J.r_err.w, length(J.axis), W.dq_dda, W.dq_dw);
+    W.qd = dot(J.w_err, W.axis_p);
+    W.jf[0] = joint_force(W.q, W.qd, W.tgt[0], W.ke[0], W.kd[0], W.act[0], W.lim[0], W.lim[1], W.lim[2], W.lim[3]);
+    W.t_raw = W.axis_p * W.jf[0];
+    W.t_raw += cross(W.axis_p, W.axis_c) * ake + (J.w_err - W.axis_p * W.qd) * (akd * ads);
+    W.t = W.t_raw;
+  } else {  // COMPOUND :411-445
+    jc_compound(J, false, W.C);
+    const v3 ax[3] = {V3(1, 0, 0), W.C.a1, W.C.a2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float *L = W.lim + 4 * k;
+      W.axw[k] = qrot(W.C.q_w, ax[k]);
+      W.jf[k] = joint_force(W.C.ang[k], W.C.m[k], W.tgt[k], W.ke[k], W.kd[k], W.act[k], L[0], L[1], L[2], L[3]);
+      W.t_raw += W.axw[k] * W.jf[k];
+    }
+    W.t = clamp3(W.t_raw, 1.0e4f);
+    W.f = clamp3(W.f_raw, 1.0e4f);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_joint_wrench_fwd(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                          float *__restrict__ out) {
+  __shared__ float slot[256 * JW_S];  // lane -> the parent-side wrench of its joint (odd stride: distinct banks)
+  const SetLane L = set_lane(nsets, nb);
+  const bool mine = (int)tab[0] == nb;  // not this call's table: no row of it is read, zeros
+  v3 own_t = V3(0, 0, 0), own_f = own_t, par_t = own_t, par_f = own_t;
+  if (L.active && mine) {
+    const float *set_rows = rows + (size_t)L.set * nb * JW_ROW;
+    const BodyState s = load_row<JW_ROW>(set_rows, (size_t)L.body);
+    JwJoint W;
+    jw_eval(tab, nb, L.body, s, set_rows, W);
+    own_t = -(W.t + cross(W.r_c, W.f)); own_f = -W.f;  // :451
+    if (W.J.parent >= 0) { par_t = W.t + cross(W.r_p, W.f); par_f = W.f; }  // :448-449
+  }
+  float *mine_s = slot + threadIdx.x * JW_S;
+  mine_s[0] = par_t.x; mine_s[1] = par_t.y; mine_s[2] = par_t.z; mine_s[3] = par_f.x; mine_s[4] = par_f.y; mine_s[5] = par_f.z;
+  __syncthreads();
+  if (!L.active) return;
+  if (mine) {
+    const float *B = tab + JC_HEAD + JC_BODY * L.body, *ch = tab + JC_HEAD + JC_BODY * nb + JC_MAXCH * L.body;
+    const int nch = min((int)B[21], (int)JC_MAXCH);
+    for (int k = 0; k < nch; ++k) {
+      const int c = (int)ch[k];
+      if (c >= 0 && c < nb) {
+        const float *cs = slot + (L.set_l * nb + c) * JW_S;
+        own_t += ld3(cs); own_f += ld3(cs + 3);
+      }
+    }
+  }
+  float *dst = out + ((size_t)L.set * nb + L.body) * 6;
+  dst[0] = own_t.x; dst[1] = own_t.y; dst[2] = own_t.z; dst[3] = own_f.x; dst[4] = own_f.y; dst[5] = own_f.z;
+}
+
+// g_b [n][25]: the raw partials of <g_out, out> with respect to the state row (quaternion entries not projected) and the twelve control
+// slots.  Joint i sees -g_out[i] on its child side and +g_out[parent] on its parent side (the adjoint of joint_adj_apply, pd_device.h,
+// on the lever arms and the position error as jw_eval forms them); limits, attachment gains and the table have no gradient.
+__global__ __launch_bounds__(256) void k_joint_wrench_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                          const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float slot[256 * PD_ADJ];  // lane -> the parent-side state adjoint of its joint (odd stride: distinct banks)
+  const SetLane L = set_lane(nsets, nb);
+  const bool mine = (int)tab[0] == nb;
+  BodyAdj own = adj_zero(), par = adj_zero();
+  float a_act[3] = {0.f, 0.f, 0.f}, a_tgt[3] = {0.f, 0.f, 0.f}, a_ke[3] = {0.f, 0.f, 0.f}, a_kd[3] = {0.f, 0.f, 0.f};
+  if (L.active && mine) {
+    const float *set_rows = rows + (size_t)L.set * nb * JW_ROW;
+    const BodyState s = load_row<JW_ROW>(set_rows, (size_t)L.body);
+    JwJoint W;
+    jw_eval(tab, nb, L.body, s, set_rows, W);
+    const JcJoint &J = W.J;
+    if (W.pulls) {
+      const float ake = W.ake, akd = W.akd, ads = 0.01f;
+      const float *g = g_out + ((size_t)L.set * nb + L.body) * 6;
+      const v3 gc_t = ld3(g), gc_f = ld3(g + 3);
+      v3 adj_t = -gc_t, adj_f = -gc_f, adj_r_c = V3(0, 0, 0), adj_r_p = adj_r_c;
+      adj_cross(W.r_c, W.f, adj_r_c, adj_f, -gc_t);
+      if (J.parent >= 0) {
+        const float *gp = g_out + ((size_t)L.set * nb + J.parent) * 6;
+        const v3 gp_t = ld3(gp), gp_f = ld3(gp + 3);
+        adj_t += gp_t; adj_f += gp_f;
+        adj_cross(W.r_p, W.f, adj_r_p, adj_f, gp_t);
+      }
+      v3 adj_x_err = V3(0, 0, 0), adj_v_err = adj_x_err, adj_w_err = adj_x_err;
+      qt adj_r_err = Q4(0, 0, 0, 0), adj_q_wj = adj_r_err;
+      if (J.type == PD_JOINT_FIXED) {
+        const v3 rv = qvec(J.r_err);
+        float hss, h_w;
+        const float h = fixed_ang_h(dot(rv, rv), J.r_err.w, hss, h_w);
+        adj_x_err += adj_f * ake; adj_v_err += adj_f * akd; adj_w_err += adj_t * (akd * ads);
+        v3 adj_ang_err = V3(0, 0, 0);
+        adj_qrot(J.q_wj, rv * h, adj_q_wj, adj_ang_err, adj_t * ake);
+        const float va = dot(rv, adj_ang_err);
+        const v3 adj_rv = adj_ang_err * h + rv * (va * hss);
+        adj_r_err.x += adj_rv.x; adj_r_err.y += adj_rv.y; adj_r_err.z += adj_rv.z;
+        adj_r_err.w += va * h_w;
+      } else if (J.type == PD_JOINT_REVOLUTE) {
+        adj_x_err += adj_f * ake; adj_v_err += adj_f * akd;
+        const float adj_jf = dot(adj_t, W.axis_p);
+        v3 adj_axis_p = adj_t * W.jf[0], adj_axis_c = V3(0, 0, 0);
+        adj_w_err += adj_t * (akd * ads);
+        float adj_qd = -dot(adj_t, W.axis_p) * (akd * ads), adj_q = 0.f;
+        adj_axis_p += adj_t * (-W.qd * (akd * ads));
+        adj_cross(W.axis_p, W.axis_c, adj_axis_p, adj_axis_c, adj_t * ake);
+        joint_force_adj(W.q, W.qd, W.tgt[0], W.ke[0], W.kd[0], W.lim[0], W.lim[1], W.lim[2], W.lim[3], adj_jf, adj_q, adj_qd, a_tgt[0],
+                        a_ke[0], a_kd[0], a_act[0]);
+        adj_w_err += W.axis_p * adj_qd; adj_axis_p += J.w_err * adj_qd;
+        const float adj_da = adj_q * W.dq_dda;
+        adj_r_err.x += J.axis.x * adj_da; adj_r_err.y += J.axis.y * adj_da; adj_r_err.z += J.axis.z * adj_da;
+        adj_r_err.w += adj_q * W.dq_dw;
+        adj_qrot_q(J.q_wj, J.axis, adj_q_wj, adj_axis_p);
+        adj_qrot_q(s.r, J.axis, own.r, adj_axis_c);
+      } else {  // COMPOUND
+        const JcCompound &C = W.C;
+        const v3 adj_f_raw = clamp3_pass(W.f_raw, adj_f, 1.0e4f);
+        adj_x_err += adj_f_raw * ake; adj_v_err += adj_f_raw * akd;
+        const v3 adj_t_raw = clamp3_pass(W.t_raw, adj_t, 1.0e4f);
+        const v3 ax[3] = {V3(1, 0, 0), C.a1, C.a2};
+        float adj_ang[3] = {0.f, 0.f, 0.f}, adj_m[3] = {0.f, 0.f, 0.f};
+        v3 adj_ax[3] = {V3(0, 0, 0), V3(0, 0, 0), V3(0, 0, 0)};
+        qt adj_q_w = Q4(0, 0, 0, 0);
+#pragma unroll
+        for (int k = 2; k >= 0; --k) {
+          const float *Lm = W.lim + 4 * k;
+          joint_force_adj(C.ang[k], C.m[k], W.tgt[k], W.ke[k], W.kd[k], Lm[0], Lm[1], Lm[2], Lm[3], dot(adj_t_raw, W.axw[k]), adj_ang[k],
+                          adj_m[k], a_tgt[k], a_ke[k], a_kd[k], a_act[k]);
+          adj_qrot(C.q_w, ax[k], adj_q_w, adj_ax[k], adj_t_raw * W.jf[k]);
+        }
+        // m_k = a_k . u, u = R(q_w)^T w_err; then the axis chain and the decomposition, as k_joint_coords_vjp in rate mode measured
+        const v3 adj_u = V3(adj_m[0], 0, 0) + C.a1 * adj_m[1] + C.a2 * adj_m[2];
+        v3 adj_a1 = adj_ax[1] + C.u * adj_m[1];
+        const v3 adj_a2 = adj_ax[2] + C.u * adj_m[2];
+        adj_qrot_inv(C.q_w, J.w_err, adj_q_w, adj_w_err, adj_u);
+        adj_qmul_a(J.q_off, adj_q_wj, adj_q_w);
+        qt adj_q10 = Q4(0, 0, 0, 0), adj_q_1 = adj_q10, adj_q_0 = adj_q10;
+        adj_qrot_q(C.q10, V3(0, 0, 1), adj_q10, adj_a2);
+        adj_qmul(C.q_1, C.q_0, adj_q_1, adj_q_0, adj_q10);
+        adj_q_axis_angle(C.a1, C.ang[1], adj_a1, adj_ang[1], adj_q_1);
+        adj_qrot_q(C.q_0, V3(0, 1, 0), adj_q_0, adj_a1);
+        adj_q_axis_angle_ang(V3(1, 0, 0), C.ang[0], adj_ang[0], adj_q_0);
+        qt adj_q_pc = Q4(0, 0, 0, 0), adj_qa = adj_q_pc;
+        quat_decompose_adj(C.q_pc, C.c0, C.c1, C.c2, adj_ang, adj_q_pc);
+        adj_qmul_a(J.q_off, adj_qa, adj_q_pc);
+        adj_qmul_b(qconj(J.q_off), adj_r_err, adj_qa);
+      }
+      qt adj_cq = Q4(0, 0, 0, 0);
+      adj_qmul(qconj(J.q_wj), s.r, adj_cq, own.r, adj_r_err);  // r_err = conj(q_wj) q_c
+      adj_q_wj += qconj(adj_cq);
+      adj_qrot_q(s.r, J.com, own.r, -adj_r_c);                 // r_c = -R(q_c) com
+      own.p += adj_x_err; own.w += adj_w_err; own.v += adj_v_err;
+      if (J.parent >= 0) {
+        const v3 com_p = ld3(tab + JC_HEAD + JC_BODY * J.parent + 18);
+        par.p = -adj_x_err; par.w = -adj_w_err; par.v = -adj_v_err;
+        adj_qrot_q(J.qp, J.p_pj, par.r, -adj_x_err);           // x_err = (p_c - p_p) - R(q_p) p_pj
+        adj_qrot_q(J.qp, J.p_pj - com_p, par.r, adj_r_p);      // r_p = R(q_p) (p_pj - com_p)
+        adj_qmul_a(J.q_pj, par.r, adj_q_wj);                   // q_wj = q_p q_pj
+      }
+    }
+  }
+  adj_store(slot + threadIdx.x * PD_ADJ, par);
+  __syncthreads();
+  if (!L.active) return;
+  if (mine) {
+    const float *B = tab + JC_HEAD + JC_BODY * L.body, *ch = tab + JC_HEAD + JC_BODY * nb + JC_MAXCH * L.body;
+    const int nch = min((int)B[21], (int)JC_MAXCH);
+    for (int k = 0; k < nch; ++k) {
+      const int c = (int)ch[k];
+      if (c >= 0 && c < nb) adj_add_from(own, slot + (L.set_l * nb + c) * PD_ADJ);
+    }
+  }
+  float o[JW_ROW];
+  adj_store(o, own);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { o[13 + k] = a_act[k]; o[16 + k] = a_tgt[k]; o[19 + k] = a_ke[k]; o[22 + k] = a_kd[k]; }
+  float *dst = g_b + ((size_t)L.set * nb + L.body) * JW_ROW;
+#pragma unroll
+  for (int k = 0; k < JW_ROW; ++k) dst[k] = o[k];
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -920,11 +1178,12 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 }
 
 // The tabled ops: a = the op's table, a_bcast = nb (the group size g: element i is body i % g of state set i / g), b = rows [n][13]
-// ([n][23] = (state, mass, inertia) for the centroidal op).  One launcher serves them; what differs per op is a row of TABLED:
+// ([n][23] = (state, mass, inertia) for the centroidal op, [n][25] = (state, controls) for the joint wrench).  One launcher serves them; what differs per op is a row of TABLED:
 //   ground wrench      out / g_out [n][6], g_a [n][nmat][4]; any nb
 //   joint coordinates  out / g_out [n / nb][nq + nqd]; no g_a
 //   centroidal         out / g_out [n / nb][16], g_b [n][23]; no g_a
 //   contact state      out / g_out [n][8]; the ground wrench's contact table, no g_a; any nb
+//   joint wrench       b / g_b [n][25] = (state, the joint's controls), out / g_out [n][6]; the joint-force table, no g_a
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
 struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
 constexpr TabledOp TABLED[] = {
@@ -932,6 +1191,7 @@ constexpr TabledOp TABLED[] = {
     {PD_POSE_JOINT_COORDS, "PD_POSE_JOINT_COORDS", "joint", JC_MAXNB, false, GEO_LANE, GEO_SETS},
     {PD_POSE_CENTROIDAL, "PD_POSE_CENTROIDAL", "mass", CT_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_CONTACT_STATE, "PD_POSE_CONTACT_STATE", "contact", 0, false, GEO_WAVE, GEO_WAVE},
+    {PD_POSE_JOINT_WRENCH, "PD_POSE_JOINT_WRENCH", "jointforce", JC_MAXNB, false, GEO_SETS, GEO_SETS},
 };
 
 template <class... A>
@@ -969,6 +1229,10 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
       if (out) hipLaunchKernelGGL(k_centroidal_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_centroidal_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
       break;
+    case PD_POSE_JOINT_WRENCH:
+      if (out) hipLaunchKernelGGL(k_joint_wrench_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_joint_wrench_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
     default:
       if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
@@ -979,7 +1243,7 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
 }
 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE))  // (codes 7, 8 and 10 are not assigned: include/ppr_diffphys.h)
+  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH))  // (codes 7, 8, 10 and 12 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
     if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);

@@ -209,6 +209,45 @@ class ContactState(torch.autograd.Function):
                 g_s[:, 7:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None, None)
 
 
+class JointWrench(torch.autograd.Function):
+    """body_q (..., nb, 7), body_qd (..., nb, 6) in Warp order (w, v), act3, target3, ke3, kd3 (..., nb, 3), env -> (..., nb, 6) =
+    (torque, force) per body: what the joint pass of a step adds to body_f for that state and those controls -- the PD force, the
+    limit force and the attachment springs of the body's own joint and of its children's (``pd_pose_op`` PD_POSE_JOINT_WRENCH on the
+    env's joint-force table, one launch forward and one for the vector-Jacobian product).  The four control tensors hold each body's
+    joint controls in dof slots 0..2 (a REVOLUTE joint reads slot 0, a COMPOUND joint all three, FIXED and FREE joints none: an unused
+    slot may hold anything and gets a zero gradient) and carry the SAME leading shape as the states: gathering them from the
+    rollout's dof layout and broadcasting shared gains is the caller's (``dp_utils.joint_wrench`` does both, so that autograd sums the
+    gradient of a shared gain).  float32 GPU tensors, or an error: no CPU fallback.  The gradients are the raw partials (quaternion
+    entries not projected), nothing is scrubbed; limits and attachment gains have none."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_qd, act3, target3, ke3, kd3, env):
+        nb = int(env.nb)
+        _need_gpu("JointWrench", body_q, body_qd, act3, target3, ke3, kd3)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_qd.shape) == lead + (nb, 6)
+                and all(tuple(c.shape) == lead + (nb, 3) for c in (act3, target3, ke3, kd3))):
+            raise ValueError("JointWrench: body_q (..., %d, 7), body_qd (..., %d, 6) and act3, target3, ke3, kd3 (..., %d, 3) with equal "
+                             "leading shapes; got %s, %s and %s" % (nb, nb, nb, tuple(body_q.shape), tuple(body_qd.shape),
+                                                                    [tuple(c.shape) for c in (act3, target3, ke3, kd3)]))
+        table = hip_backend.env_joint_force_table(env, body_q.device)
+        rows = torch.cat([t.detach().reshape(-1, w) for t, w in zip((body_q, body_qd, act3, target3, ke3, kd3), (7, 6, 3, 3, 3, 3))], dim=1)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows)
+        return hip_backend.joint_wrench(table, nb, rows).view(lead + (nb, 6))
+
+    @staticmethod
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:6]):
+            return (None,) * 7
+        lead, nb = ctx.lead, ctx.nb
+        g_r = hip_backend.joint_wrench_vjp(ctx.table, nb, rows, g.to(torch.float32).reshape(-1, 6).contiguous())
+        cols = ((0, 7), (7, 13), (13, 16), (16, 19), (19, 22), (22, 25))
+        return tuple(g_r[:, a:b].reshape(lead + (nb, b - a)) if need[k] else None for k, (a, b) in enumerate(cols)) + (None,)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

@@ -376,6 +376,44 @@ def skate_loss(cs, h0=0.02, bodies=None):
     return torch.dot(near.reshape(-1), (vel[..., 0] ** 2 + vel[..., 2] ** 2).reshape(-1)) / kept
 
 
+def joint_wrench(body_q, body_qd, env, refs, target_ke, target_kd, torques=None):
+    """What the joint pass of a step adds to each body's body_f (eval_body_joints, integrator_euler.py:289-451 of the reference, as a
+    function of the state and the controls): the PD force, the limit force and the attachment springs of the body's own joint and of
+    its children's.  body_q (..., nb, 7) poses (p, q xyzw) and body_qd (..., nb, 6) twists in Warp order (w, v) -- wp_pos / wp_vel rows
+    reshaped to (..., nb, .) --; refs (the PD targets), target_ke, target_kd and torques broadcastable to (..., nqd) in the rollouts'
+    dof layout (torques=None: zeros, no gradient) -> (..., nb, 6) wrenches (torque, force).  One HIP launch
+    (``dp_model.JointWrench``), differentiable in every tensor argument (raw partials; quaternions are taken as they are); joint
+    limits and attachment gains are the env's and carry no gradient.  The controls are gathered into the op's per-body dof slots and
+    broadcast HERE, outside the Function, so autograd sums the gradient of a shared gain over the state sets.  The differentiable
+    jaf of a rollout frame is ``joint_wrench(wp_pos[f], wp_vel[f], env, refs[s], target_ke, target_kd, torques[s])`` with
+    ``s = frame2step[f]``.  float32 GPU tensors only."""
+    from . import hip_backend
+    from .dp_model import JointWrench
+
+    controls = (refs, target_ke, target_kd) + (() if torques is None else (torques,))
+    _need_gpu("joint_wrench", body_q, body_qd, *controls)
+    nb = int(env.nb)
+    lead = _check_states("joint_wrench", body_q, body_qd, nb)
+    idx = hip_backend.env_joint_slot_index(env, body_q.device)
+    nqd = int(env.template()["nqd"])
+
+    def slots(t, name):
+        try:
+            ok = t.dim() >= 1 and tuple(torch.broadcast_shapes(tuple(t.shape), lead + (nqd,))) == lead + (nqd,)
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError("joint_wrench: %s must broadcast to %s; got %s" % (name, lead + (nqd,), tuple(t.shape)))
+        # slot k of body b <- dof qd_start[b] + k, or the appended zero column
+        t = t.expand(t.shape[:-1] + (nqd,))
+        t = torch.cat([t, t.new_zeros(t.shape[:-1] + (1,))], dim=-1)
+        return t.index_select(-1, idx).reshape(t.shape[:-1] + (nb, 3)).expand(lead + (nb, 3))
+
+    tgt3, ke3, kd3 = slots(refs, "refs"), slots(target_ke, "target_ke"), slots(target_kd, "target_kd")
+    act3 = body_q.new_zeros(lead + (nb, 3)) if torques is None else slots(torques, "torques")
+    return JointWrench.apply(body_q, body_qd, act3, tgt3, ke3, kd3, env)
+
+
 def compute_com(body_q, part_com, part_mass):
     """mass-weighted COM of one articulation (numpy)   dp_utils.py:86-90"""
     from scipy.spatial.transform import Rotation as R

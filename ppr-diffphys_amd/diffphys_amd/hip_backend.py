@@ -727,20 +727,24 @@ def pose_op_vjp(op, a, b, g_out, need_a=True, need_b=True):
     return g_a, g_b
 
 
-# ---- The tabled state ops (ground wrench, joint coordinates, centroidal, contact state): each takes a device table compiled from a template.  They share
+# ---- The tabled state ops (ground wrench, joint coordinates, centroidal, contact state, joint wrench): each takes a device table compiled from a template.  They share
 # one tag on the table tensor, one per-model cache, one argument check and one gradient check; what differs is passed in.
-_ROWS = {13: ("state", "(p, q xyzw, w, v)"), 23: ("rows", "(p, q xyzw, w, v, m, I row-major)")}   # operand row width -> its name, its columns
+_ROWS = {13: ("state", "(p, q xyzw, w, v)"), 23: ("rows", "(p, q xyzw, w, v, m, I row-major)"),
+         25: ("rows", "(p, q xyzw, w, v, act[3], target[3], ke[3], kd[3])")}   # operand row width -> its name, its columns
+
+
+_BUILDER = {"jointforce": "joint_force"}   # table kind -> the stem of its builder's name, where the two differ
 
 
 def _tagged(table, kind, dims):
-    """Marks a table tensor with what it is: its kind ("contact", "joint" or "mass") and its dimensions, which the library cannot read
+    """Marks a table tensor with what it is: its kind ("contact", "joint", "mass" or "jointforce") and its dimensions, which the library cannot read
     back from a device buffer."""
     table._pd_table = (kind, dims)
     return table
 
 
 def _table_tag(table):
-    """-> (kind, dims) of a tensor contact_table / joint_table / mass_table made, or None."""
+    """-> (kind, dims) of a tensor contact_table / joint_table / mass_table / joint_force_table made, or None."""
     return getattr(table, "_pd_table", None)
 
 
@@ -756,14 +760,14 @@ def _env_table(env, key, build):
 
 
 def _state_op_check(op, kind, width, table, nb, rows, bare=False):
-    """The argument check of the eight state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    """The argument check of the ten state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
     if tag is None and not bare:
-        raise ValueError("%s: the table must come from hip_backend.%s_table (it carries its dimensions)" % (op, kind))
+        raise ValueError("%s: the table must come from hip_backend.%s_table (it carries its dimensions)" % (op, _BUILDER.get(kind, kind)))
     if tag is not None and tag[0] != kind:
-        raise ValueError("%s: a %s table; the op takes one from hip_backend.%s_table" % (op, tag[0], kind))
+        raise ValueError("%s: a %s table; the op takes one from hip_backend.%s_table" % (op, tag[0], _BUILDER.get(kind, kind)))
     name, columns = _ROWS[width]
     if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != width:
         raise ValueError("%s: %s must be [n, %d] = %s rows; got %s" % (op, name, width, columns, tuple(getattr(rows, "shape", ()))))
@@ -1078,6 +1082,92 @@ def contact_state_vjp(table, nb, state, g_out):
     _grad_check("contact_state_vjp", "g_out", g_out, n, _CS_OUT)
     g_b = torch.empty(n, 13, device=state.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_CONTACT_STATE, n, _dev(table, "table"), int(nb), _ptr(state, "state"), _ptr(g_out, "g_out", n * _CS_OUT),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
+POSE_JOINT_WRENCH = 13   # (code 12 is not assigned either: include/ppr_diffphys.h)
+_JW_ROW, _JW_OUT, _JW_HEAD, _JW_BODY = 25, 6, 4, 12   # floats of an operand row, of an output row, of the table's gains block / limits per body
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def joint_force_table_layout(nb):
+    """Float offsets of the joint-force table's blocks -> dict(bodies, children, gains, limits, floats): the joint table's, then the
+    attachment gains and the limits."""
+    L = joint_table_layout(nb)
+    return dict(bodies=L["bodies"], children=L["children"], gains=L["floats"], limits=L["floats"] + _JW_HEAD,
+                floats=L["floats"] + _JW_HEAD + _JW_BODY * nb)
+
+
+def joint_force_table_host(tpl):
+    """The joint-force table of PD_POSE_JOINT_WRENCH as a float32 numpy array (layout: include/ppr_diffphys.h): the floats of
+    ``joint_table_host(tpl, "measured")``, then (attach_ke, attach_kd, 0, 0), then per body (lower, upper, limit_ke, limit_kd) for dof
+    slots 0..2 = the template's joint_limit_*[qd_start + k]; a slot no dof uses holds (-FLT_MAX, FLT_MAX, 0, 0)."""
+    base = joint_table_host(tpl, "measured")
+    nb = int(tpl["nb"])
+    L = joint_force_table_layout(nb)
+    t = np.zeros(L["floats"], np.float32)
+    t[:L["gains"]] = base
+    t[L["gains"]: L["gains"] + 2] = (float(tpl["joint_attach_ke"]), float(tpl["joint_attach_kd"]))
+    ty = np.asarray(tpl["joint_type"], dtype=np.int64).reshape(nb)
+    qds = np.asarray(tpl["joint_qd_start"], dtype=np.int64).reshape(-1)[:nb]
+    lim = np.stack([np.asarray(tpl[k], dtype=np.float32).reshape(-1) for k in
+                    ("joint_limit_lower", "joint_limit_upper", "joint_limit_ke", "joint_limit_kd")], axis=1)   # [nqd, 4]
+    slots = t[L["limits"]:].reshape(nb, 3, 4)
+    slots[:] = (-_FLT_MAX, _FLT_MAX, 0.0, 0.0)
+    for b in range(nb):
+        n_dof = {1: 1, 5: 3}.get(int(ty[b]), 0)   # REVOLUTE, COMPOUND; FIXED and FREE joints have no PD dof
+        slots[b, :n_dof] = lim[qds[b]: qds[b] + n_dof]
+    return t
+
+
+def joint_force_table(tpl, device="cuda"):
+    """The joint-force table operand of ``joint_wrench`` for a template dict, as a float32 tensor on ``device``; its dimensions
+    (nb, nq, nqd) travel with the tensor."""
+    return _tagged(torch.from_numpy(joint_force_table_host(tpl)).to(device), "jointforce", (int(tpl["nb"]), int(tpl["nq"]), int(tpl["nqd"])))
+
+
+def env_joint_force_table(env, device):
+    """The joint-force table of a :class:`diffphys_amd.sim.Model`, cached on the model per device."""
+    return _env_table(env, ("jointforce", str(torch.device(device))), lambda tpl: joint_force_table(tpl, device))
+
+
+def joint_slot_index(tpl):
+    """[nb, 3] int64 numpy: the dof behind slot k of each body's joint, qd_start + k, or nqd -- a column of zeros the caller appends --
+    for a slot no dof uses.  A FREE joint's six dofs carry no PD controller: its slots are unused."""
+    nb, nqd = int(tpl["nb"]), int(tpl["nqd"])
+    ty = np.asarray(tpl["joint_type"], dtype=np.int64).reshape(nb)
+    qds = np.asarray(tpl["joint_qd_start"], dtype=np.int64).reshape(-1)[:nb]
+    idx = np.full((nb, 3), nqd, np.int64)
+    for b in range(nb):
+        n_dof = {1: 1, 5: 3}.get(int(ty[b]), 0)
+        idx[b, :n_dof] = qds[b] + np.arange(n_dof)
+    return idx
+
+
+def env_joint_slot_index(env, device):
+    """``joint_slot_index`` of a :class:`diffphys_amd.sim.Model` as a flat [3 nb] int64 tensor on ``device``, cached on the model."""
+    return _env_table(env, ("jointslots", str(torch.device(device))),
+                      lambda tpl: torch.from_numpy(joint_slot_index(tpl).reshape(-1)).to(device))
+
+
+def joint_wrench(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_JOINT_WRENCH: rows [n, 25] = (p, q xyzw, w, v, act[3], target[3], ke[3], kd[3]) per body, n a multiple of nb
+    (row i is body i % nb of set i // nb) -> [n, 6] = (torque, force), what the joint pass of a step adds to each body's body_f.  Fixed
+    summation order: a set's bits depend neither on the call nor on the other sets."""
+    n, _ = _state_op_check("joint_wrench", "jointforce", _JW_ROW, table, int(nb), rows)
+    out = torch.empty(n, _JW_OUT, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_JOINT_WRENCH, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def joint_wrench_vjp(table, nb, rows, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_JOINT_WRENCH: g_out [n, 6] -> g_rows [n, 25], the raw partials with respect to the state (quaternion
+    entries not projected) and the twelve control slots (0 in a slot the joint does not use)."""
+    n, _ = _state_op_check("joint_wrench_vjp", "jointforce", _JW_ROW, table, int(nb), rows)
+    _grad_check("joint_wrench_vjp", "g_out", g_out, n, _JW_OUT)
+    g_b = torch.empty(n, _JW_ROW, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_JOINT_WRENCH, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", n * _JW_OUT),
                                 None, _ptr(g_b, "g_b"), _stream()))
     return g_b
 
