@@ -476,15 +476,49 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * A table whose nb is not the call's a_broadcast is not read beyond its first float: out / g_b are then written as zeros.  A parent
  * index or a coordinate range outside the set is handled as for PD_POSE_JOINT_COORDS.
  *
+ * Generalised joint forces of body wrenches -- the transpose of the articulation's Jacobian: the torque about every hinge axis and the
+ * net wrench on a floating root that a set of per-body wrenches (a grf, jaf or body_f row per body) amounts to:
+ *   PD_POSE_GENERALIZED_FORCE  b = rows [n][13] = (p, q xyzw, t, f): the pose of a state row followed by the body's wrench, torque
+ *                          first, world axes, the force acting at the body's centre of mass.  Velocities are not an input.
+ *                          a_broadcast = nb as above (nb < 1 or n % nb != 0 is refused at every n; nb <= 256).  a = ONE joint table of
+ *                          PD_POSE_JOINT_COORDS, unchanged, for all elements; its mode float [3] selects the effort convention of
+ *                          COMPOUND joints -> out [n / nb][nqd], set-major, in the joint_qd layout.  With x_b = p_b + R(q_b) com_b
+ *                          (R(q) the map of the quaternion AS IT IS), the subtree sums F_i = sum f_b and N_i(o) = sum (t_b +
+ *                          (x_b - o) x f_b) over the bodies b of the subtree of body i, and the joint frame (p_wj, q_wj) and world
+ *                          axes axw_k = R_wj R_off a_k (angles from the poses) of PD_POSE_JOINT_COORDS:
+ *                            REVOLUTE  tau = (R_wj axis) . N_i(p_wj)
+ *                            COMPOUND  g_k = axw_k . N_i(p_wj); mode 1 ("generalized"): tau_k = g_k, conjugate to the generalised
+ *                                      rates (sum tau_k qd_k = N . w_err); mode 0 ("actuator"): tau = G^-1 g, G_kj = a_k . a_j -- the
+ *                                      Gram solve of the rates, singular at |q_1| = pi / 2 --, conjugate to the measured rates: the
+ *                                      efforts jf_k for which sum axw_k jf_k has these projections, the units of torques and of
+ *                                      the PD force
+ *                            FREE      (R_wj^-1 N_i(x_i), R_wj^-1 F_i): the net wrench on the subtree, the moment about the child
+ *                                      body's centre of mass -- conjugate to that body's twist (w, v) under rigid motion of the
+ *                                      subtree.  It is NOT conjugate to PD_POSE_JOINT_COORDS' FREE linear rate, which carries Warp's
+ *                                      unrotated-com lever (v_c - v_p - w_err x com).
+ *                            FIXED     no output
+ *                          Every float of out is written by exactly one lane.  Whole state sets share a workgroup, a lane per body.
+ *                          The bodies' depths come from the table's parent indices (pointer jumping in LDS); the subtree sums go
+ *                          through LDS level by level, deepest first, every body adding its children in the table's child order; the
+ *                          moments are accumulated about the origin of the set's body 0 and moved to each anchor afterwards, so the
+ *                          set's distance from the world origin does not enter.  No atomics: a set's bits depend neither on the run
+ *                          nor on n nor on the set's place in the launch.
+ *                          VJP: g_out [n / nb][nqd] -> g_b [n][13], the raw partials with respect to pose and wrench (quaternion
+ *                          entries not projected): the mirror image, an ancestor sum from the roots down, then the parent-side pose
+ *                          adjoints gathered as for PD_POSE_JOINT_COORDS.  The table has no gradient: a non-NULL g_a is refused, at
+ *                          every n.
+ * A table whose nb is not the call's a_broadcast is not read beyond its header: out [n / nb][nqd of THAT header] / g_b are then
+ * written as zeros.  A parent index or a coordinate range outside the set is handled as for PD_POSE_JOINT_COORDS.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
- * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE and
- * PD_POSE_JOINT_WRENCH are new op codes of the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps:
- * codes 7, 8, 10 and 12 are not assigned and are refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7
- * and 8 since the centroidal op took 9, of 10 since the contact state took 11, of 12 since the joint wrench took 13), so the four stay
- * free for as long as the version is 9. */
+ * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE,
+ * PD_POSE_JOINT_WRENCH and PD_POSE_GENERALIZED_FORCE are new op codes of the two entries: no symbol or signature changed, the version
+ * stays 9.  The enum has gaps: codes 7, 8, 10, 12 and 14 are not assigned and are refused as "unknown op" -- callers and tests of
+ * version 9 rely on that refusal (of 7 and 8 since the centroidal op took 9, of 10 since the contact state took 11, of 12 since the
+ * joint wrench took 13, of 14 since the generalised force took 15), so the five stay free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
        PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11,
-       PD_POSE_JOINT_WRENCH = 13 };
+       PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

@@ -1163,6 +1163,245 @@ __global__ __launch_bounds__(256) void k_joint_wrench_vjp(int nsets, int nb, con
   for (int k = 0; k < JW_ROW; ++k) dst[k] = o[k];
 }
 
+// ---- PD_POSE_GENERALIZED_FORCE: the generalised joint forces of per-body wrenches -- J^T of the articulation applied to rows
+// (p, q xyzw, t, f): per REVOLUTE / COMPOUND dof the projection on its world axis of the subtree's moment about the joint anchor, per
+// FREE joint the subtree's net wrench about the child's centre of mass in the joint frame -- and its vector-Jacobian product with
+// respect to poses and wrenches.  With x_b = p_b + R(q_b) com_b, F_i = sum_{b in subtree(i)} f_b, N_i(o) = sum (t_b + (x_b - o) x f_b):
+//   REVOLUTE  tau = (R_wj axis) . N_i(p_wj)
+//   COMPOUND  g_k = (R_wj R_off a_k) . N_i(p_wj) on jc_compound's angles and axes; mode 1 (generalized): tau = g; mode 0 (actuator):
+//             tau = G^-1 g, the Gram solve of the rates (tau_1 = g_1, (tau_0, tau_2) = ((g_0 - s g_2), (g_2 - s g_0)) / (1 - s^2))
+//   FREE      (R_wj^-1 N_i(x_i), R_wj^-1 F_i);   FIXED: nothing
+// Frames, axes, the range checks and the mode float are PD_POSE_JOINT_COORDS' (jc_joint on the joint table, unchanged; the rows' last six
+// floats are a wrench, so jc_joint's rates are not looked at).
+// Mapping: a lane per body, whole state sets per workgroup (set_lane).  The table holds parents and children, not depths: every lane
+// finds its depth by pointer jumping over the parent indices in LDS (log2 nb rounds), the workgroup's largest depth is the trip count of
+// the level sweeps -- table data alone, so every barrier sits in workgroup-uniform control flow.  Forward: (F, M) per body in an LDS
+// slot, M about o0 = the origin of the set's body 0 (the set's distance from the world origin never enters a product); levels deepest
+// first, a body adds its children's slots in the table's child order; then N_i(o) = M_i - (o - o0) x F_i with o - o0 formed from
+// differences.  VJP: the sweep again (the axes' adjoints need N_i), the joint's adjoint, an ancestor sum of (adj F, adj M) from the roots
+// down, the body's own adjoint, and the parent-side pose adjoint handed over as k_joint_coords_vjp does.  o0 is a constant of the
+// adjoint: the function does not depend on it.  No atomics: a set's bits depend neither on the run nor on n nor on its place in the
+// launch.  A table of another nb: zeros (out by that table's own nqd), no row of it is read.
+enum { GF_S = 7 };  // floats of an LDS slot (6 or 7 used; odd stride: distinct banks)
+struct GfTree { int dep, maxd, nch, parent; const float *ch; };
+// The lane's parent (inside the set, or -1), children and depth, and the workgroup's largest depth.  Every lane of the workgroup calls
+// it: the barriers' count depends on nb alone.  A malformed table (a parent cycle) gives depths that mean nothing but stay below nb.
+__device__ __forceinline__ GfTree gf_tree(const float *tab, int nb, const SetLane &L, int (*s_anc)[256], int (*s_dep)[256], int *s_max) {
+  GfTree T;
+  T.nch = 0; T.ch = tab; T.parent = -1;
+  if (L.in_set) {
+    const float *B = tab + JC_HEAD + JC_BODY * L.body;
+    const int par = (int)B[0];
+    T.parent = par >= 0 && par < nb ? par : -1;
+    T.nch = min((int)B[21], (int)JC_MAXCH);
+    T.ch = tab + JC_HEAD + JC_BODY * nb + JC_MAXCH * L.body;
+  }
+  int anc = T.parent, dep = anc >= 0 ? 1 : 0, cur = 0;
+  for (int span = 1; span < nb; span <<= 1) {  // dep = the distance to anc; anc jumps 2^round bodies up
+    s_anc[cur][threadIdx.x] = anc; s_dep[cur][threadIdx.x] = dep;
+    __syncthreads();
+    if (anc >= 0) {
+      const int a = L.set_l * nb + anc;
+      dep += s_dep[cur][a]; anc = s_anc[cur][a];
+    }
+    cur ^= 1;  // the other pair next round: nobody reads it any more
+  }
+  T.dep = min(dep, nb - 1);
+  int m = T.dep;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
+  __syncthreads();
+  T.maxd = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+  return T;
+}
+__device__ __forceinline__ void gf_put(float *s, v3 a, v3 b) { s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = b.x; s[4] = b.y; s[5] = b.z; }
+// Subtree sums of (F, M): levels deepest first, a body adds its children's slots in the table's child order and publishes its own.
+__device__ __forceinline__ void gf_up(float *slot, const GfTree &T, const SetLane &L, int nb, v3 &F, v3 &M) {
+  float *mine = slot + threadIdx.x * GF_S;
+  gf_put(mine, F, M);
+  for (int lev = T.maxd - 1; lev >= 0; --lev) {
+    __syncthreads();
+    if (L.in_set && T.dep == lev && T.nch > 0) {
+      for (int k = 0; k < T.nch; ++k) {
+        const int c = (int)T.ch[k];
+        if (c >= 0 && c < nb) {
+          const float *cs = slot + (L.set_l * nb + c) * GF_S;
+          F += ld3(cs); M += ld3(cs + 3);
+        }
+      }
+      gf_put(mine, F, M);
+    }
+  }
+}
+struct GfBody { BodyState s; JcJoint J; v3 d, r; };  // d = x_b - o0; r = the joint's anchor - o0 (p_wj, or x_b for a FREE joint)
+__device__ __forceinline__ void gf_load(const float *tab, int nb, int body, const float *set_rows, GfBody &B) {
+  const v3 o0 = ld3(set_rows);
+  B.s = load_state0(set_rows, (size_t)body);  // (s.w, s.v) = (t, f)
+  B.J = jc_joint(tab, nb, (int)tab[1], (int)tab[2], body, B.s, set_rows);
+  B.J.w_err = V3(0, 0, 0);
+  B.d = (B.s.p - o0) + qrot(B.s.r, B.J.com);
+  B.r = B.J.type == PD_JOINT_FREE ? B.d : B.J.parent >= 0 ? (B.J.pp - o0) + qrot(B.J.qp, B.J.p_pj) : B.J.p_pj - o0;
+}
+
+__global__ __launch_bounds__(256) void k_generalized_force_fwd(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                               float *__restrict__ out) {
+  __shared__ float slot[256 * GF_S];
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  const int nqd = (int)tab[2];
+  if ((int)tab[0] != nb) {  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
+    if (L.active)
+      for (int k = L.body; k < nqd; k += nb) out[(size_t)L.set * nqd + k] = 0.0f;
+    return;
+  }
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  GfBody B;
+  v3 F = V3(0, 0, 0), M = F;
+  if (L.active) {
+    gf_load(tab, nb, L.body, rows + (size_t)L.set * nb * PD_ADJ, B);
+    F = B.s.v; M = B.s.w + cross(B.d, F);
+  }
+  gf_up(slot, T, L, nb, F, M);
+  if (!L.active) return;
+  const JcJoint &J = B.J;
+  const v3 N = M - cross(B.r, F);
+  float *o = out + (size_t)L.set * nqd + J.qds;
+  if (J.type == PD_JOINT_FREE) {
+    const v3 a = qrot_inv(J.q_wj, N), l = qrot_inv(J.q_wj, F);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = l.x; o[4] = l.y; o[5] = l.z;
+  } else if (J.type == PD_JOINT_REVOLUTE) {
+    o[0] = dot(qrot(J.q_wj, J.axis), N);
+  } else if (J.type == PD_JOINT_COMPOUND) {
+    JcCompound C;
+    jc_compound(J, false, C);
+    const v3 u = qrot_inv(C.q_w, N);  // (R a) . N = a . (R^T N)
+    const float g0 = u.x, g1 = dot(C.a1, u), g2 = dot(C.a2, u);
+    if (generalized) { o[0] = g0; o[1] = g1; o[2] = g2; }
+    else {
+      const float id = 1.0f / (1.0f - C.s * C.s);
+      o[0] = (g0 - C.s * g2) * id; o[1] = g1; o[2] = (g2 - C.s * g0) * id;
+    }
+  }
+}
+
+// g_b [n][13]: the raw partials of <g_out, out> with respect to (p, q, t, f) of every body.
+__global__ __launch_bounds__(256) void k_generalized_force_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                               const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float slot[256 * GF_S], down[256 * GF_S], pslot[256 * GF_S];  // subtree sums / ancestor sums / the parent-side pose adjoint
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *dst = g_b + ((size_t)L.set * nb + L.body) * PD_ADJ;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {
+    if (L.active)
+      for (int k = 0; k < PD_ADJ; ++k) dst[k] = 0.0f;
+    return;
+  }
+  const int nqd = (int)tab[2];
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  GfBody B;
+  v3 F = V3(0, 0, 0), M = F;
+  if (L.active) {
+    gf_load(tab, nb, L.body, rows + (size_t)L.set * nb * PD_ADJ, B);
+    F = B.s.v; M = B.s.w + cross(B.d, F);
+  }
+  gf_up(slot, T, L, nb, F, M);
+  // the joint's adjoint: (adj F_i, adj M_i) of its subtree sums, the pose adjoints of its own body and of its parent
+  v3 aF = V3(0, 0, 0), aM = aF, own_p = aF, par_p = aF, adj_r = aF;
+  qt own_q = Q4(0, 0, 0, 0), par_q = own_q;
+  if (L.active) {
+    const JcJoint &J = B.J;
+    const v3 N = M - cross(B.r, F);
+    const float *g = g_out + (size_t)L.set * nqd + J.qds;
+    qt adj_q_wj = Q4(0, 0, 0, 0);
+    v3 adj_N = V3(0, 0, 0);
+    if (J.type == PD_JOINT_FREE) {
+      adj_qrot_inv(J.q_wj, N, adj_q_wj, adj_N, ld3(g));
+      adj_qrot_inv(J.q_wj, F, adj_q_wj, aF, ld3(g + 3));
+    } else if (J.type == PD_JOINT_REVOLUTE) {
+      adj_N = qrot(J.q_wj, J.axis) * g[0];
+      adj_qrot_q(J.q_wj, J.axis, adj_q_wj, N * g[0]);
+    } else if (J.type == PD_JOINT_COMPOUND) {
+      JcCompound C;
+      jc_compound(J, false, C);
+      const v3 u = qrot_inv(C.q_w, N);
+      const float g0 = u.x, g2 = dot(C.a2, u);
+      float gm[3] = {g[0], g[1], g[2]}, g_s = 0.0f;
+      if (!generalized) {  // tau_0 = (g_0 - s g_2) id, tau_2 = (g_2 - s g_0) id, id = 1 / (1 - s^2)
+        const float id = 1.0f / (1.0f - C.s * C.s);
+        const float t0 = (g0 - C.s * g2) * id, t2 = (g2 - C.s * g0) * id;
+        g_s = (g[0] * (2.0f * C.s * t0 - g2) + g[2] * (2.0f * C.s * t2 - g0)) * id;
+        gm[0] = (g[0] - C.s * g[2]) * id;
+        gm[2] = (g[2] - C.s * g[0]) * id;
+      }
+      const v3 adj_u = V3(gm[0], 0, 0) + C.a1 * gm[1] + C.a2 * gm[2];
+      v3 adj_a1 = u * gm[1], adj_a2 = u * gm[2];
+      adj_a2.x += g_s;
+      qt adj_q_w = Q4(0, 0, 0, 0), adj_r_err = adj_q_w;
+      adj_qrot_inv(C.q_w, N, adj_q_w, adj_N, adj_u);
+      adj_qmul_a(J.q_off, adj_q_wj, adj_q_w);
+      // the axis chain and the decomposition, as k_joint_coords_vjp
+      float adj_ang[3] = {0.f, 0.f, 0.f};
+      qt adj_q10 = Q4(0, 0, 0, 0), adj_q_1 = adj_q10, adj_q_0 = adj_q10;
+      adj_qrot_q(C.q10, V3(0, 0, 1), adj_q10, adj_a2);
+      adj_qmul(C.q_1, C.q_0, adj_q_1, adj_q_0, adj_q10);
+      adj_q_axis_angle(C.a1, C.ang[1], adj_a1, adj_ang[1], adj_q_1);
+      adj_qrot_q(C.q_0, V3(0, 1, 0), adj_q_0, adj_a1);
+      adj_q_axis_angle_ang(V3(1, 0, 0), C.ang[0], adj_ang[0], adj_q_0);
+      qt adj_q_pc = Q4(0, 0, 0, 0), adj_qa = adj_q_pc;
+      quat_decompose_adj(C.q_pc, C.c0, C.c1, C.c2, adj_ang, adj_q_pc);
+      adj_qmul_a(J.q_off, adj_qa, adj_q_pc);
+      adj_qmul_b(qconj(J.q_off), adj_r_err, adj_qa);
+      qt adj_cq = Q4(0, 0, 0, 0);
+      adj_qmul(qconj(J.q_wj), B.s.r, adj_cq, own_q, adj_r_err);  // r_err = conj(q_wj) q_c
+      adj_q_wj += qconj(adj_cq);
+    }
+    aM = adj_N;
+    adj_cross(B.r, F, adj_r, aF, -adj_N);  // N = M - r x F
+    if (J.type != PD_JOINT_FREE) {          // (a FREE joint's r is d: it joins the body's own adjoint below)
+      if (J.parent >= 0) {                  // r = (p_p - o0) + R(q_p) p_pj
+        par_p += adj_r;
+        adj_qrot_q(J.qp, J.p_pj, par_q, adj_r);
+      }
+      adj_r = V3(0, 0, 0);
+    }
+    if (J.parent >= 0) adj_qmul_a(J.q_pj, par_q, adj_q_wj);  // q_wj = q_p q_pj
+  }
+  float *ps = pslot + threadIdx.x * GF_S;
+  ps[0] = par_p.x; ps[1] = par_p.y; ps[2] = par_p.z; ps[3] = par_q.x; ps[4] = par_q.y; ps[5] = par_q.z; ps[6] = par_q.w;
+  // the ancestor sums: levels from the roots down, a body adds its parent's slot to its own and publishes it
+  float *dn = down + threadIdx.x * GF_S;
+  gf_put(dn, aF, aM);
+  for (int lev = 1; lev <= T.maxd; ++lev) {
+    __syncthreads();
+    if (L.in_set && T.dep == lev && T.parent >= 0) {
+      const float *pp = down + (L.set_l * nb + T.parent) * GF_S;
+      aF += ld3(pp); aM += ld3(pp + 3);
+      gf_put(dn, aF, aM);
+    }
+  }
+  __syncthreads();  // (pslot; with maxd = 0 the one barrier)
+  if (!L.active) return;
+  // the body's own share: m_b = t_b + d x f_b, d = (p_b - o0) + R(q_b) com_b
+  v3 adj_d = adj_r, adj_f = aF;
+  adj_cross(B.d, B.s.v, adj_d, adj_f, aM);
+  own_p += adj_d;
+  adj_qrot_q(B.s.r, B.J.com, own_q, adj_d);
+  for (int k = 0; k < T.nch; ++k) {
+    const int c = (int)T.ch[k];
+    if (c >= 0 && c < nb) {
+      const float *cs = pslot + (L.set_l * nb + c) * GF_S;
+      own_p += ld3(cs); own_q += ld4(cs + 3);
+    }
+  }
+  dst[0] = own_p.x; dst[1] = own_p.y; dst[2] = own_p.z;
+  dst[3] = own_q.x; dst[4] = own_q.y; dst[5] = own_q.z; dst[6] = own_q.w;
+  dst[7] = aM.x; dst[8] = aM.y; dst[9] = aM.z;
+  dst[10] = adj_f.x; dst[11] = adj_f.y; dst[12] = adj_f.z;
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -1184,6 +1423,7 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 //   centroidal         out / g_out [n / nb][16], g_b [n][23]; no g_a
 //   contact state      out / g_out [n][8]; the ground wrench's contact table, no g_a; any nb
 //   joint wrench       b / g_b [n][25] = (state, the joint's controls), out / g_out [n][6]; the joint-force table, no g_a
+//   generalized force  b / g_b [n][13] = (pose, wrench), out / g_out [n / nb][nqd]; the joint table, no g_a
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
 struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
 constexpr TabledOp TABLED[] = {
@@ -1192,6 +1432,7 @@ constexpr TabledOp TABLED[] = {
     {PD_POSE_CENTROIDAL, "PD_POSE_CENTROIDAL", "mass", CT_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_CONTACT_STATE, "PD_POSE_CONTACT_STATE", "contact", 0, false, GEO_WAVE, GEO_WAVE},
     {PD_POSE_JOINT_WRENCH, "PD_POSE_JOINT_WRENCH", "jointforce", JC_MAXNB, false, GEO_SETS, GEO_SETS},
+    {PD_POSE_GENERALIZED_FORCE, "PD_POSE_GENERALIZED_FORCE", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
 };
 
 template <class... A>
@@ -1233,6 +1474,10 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
       if (out) hipLaunchKernelGGL(k_joint_wrench_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_joint_wrench_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
       break;
+    case PD_POSE_GENERALIZED_FORCE:
+      if (out) hipLaunchKernelGGL(k_generalized_force_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_generalized_force_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
     default:
       if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
@@ -1243,7 +1488,8 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
 }
 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
-  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH))  // (codes 7, 8, 10 and 12 are not assigned: include/ppr_diffphys.h)
+  if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH &&
+                         op != PD_POSE_GENERALIZED_FORCE))  // (codes 7, 8, 10, 12 and 14 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
     if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);

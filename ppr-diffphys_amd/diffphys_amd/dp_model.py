@@ -248,6 +248,41 @@ class JointWrench(torch.autograd.Function):
         return tuple(g_r[:, a:b].reshape(lead + (nb, b - a)) if need[k] else None for k, (a, b) in enumerate(cols)) + (None,)
 
 
+class GeneralizedForce(torch.autograd.Function):
+    """body_q (..., nb, 7), body_f (..., nb, 6) = (torque, force) per body in world axes, the force at the body's centre of mass -- a
+    grf, jaf or body_f row --, env, efforts -> (..., nqd): the generalised joint forces those wrenches amount to, the transpose of the
+    articulation's Jacobian (``pd_pose_op`` PD_POSE_GENERALIZED_FORCE on the env's joint table, one launch forward and one for the
+    vector-Jacobian product): the torque about every REVOLUTE / COMPOUND axis, the net wrench on the subtree of a FREE joint, in the
+    joint_qd layout.  efforts="actuator": COMPOUND entries in the units of ``torques`` and the PD force; "generalized": conjugate to the
+    generalised rates.  float32 GPU tensors, or an error: no CPU fallback.  The gradients are the raw partials (quaternion entries
+    not projected), nothing is scrubbed."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_f, env, efforts="actuator"):
+        nb = int(env.nb)
+        _need_gpu("GeneralizedForce", body_q, body_f)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_f.shape) == lead + (nb, 6)):
+            raise ValueError("GeneralizedForce: body_q (..., %d, 7) and body_f (..., %d, 6) with equal leading shapes; got %s and %s" % (
+                nb, nb, tuple(body_q.shape), tuple(body_f.shape)))
+        table = hip_backend.env_joint_table(env, body_q.device, hip_backend.efforts_mode(efforts))
+        rows = _state_rows(body_q, body_f)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows)
+        out = hip_backend.generalized_force(table, nb, rows)
+        return out.view(lead + (out.shape[-1],))
+
+    @staticmethod
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        lead, nb = ctx.lead, ctx.nb
+        g_r = hip_backend.generalized_force_vjp(ctx.table, nb, rows, g.to(torch.float32).reshape(-1, g.shape[-1]).contiguous())
+        return (g_r[:, :7].reshape(lead + (nb, 7)) if ctx.needs_input_grad[0] else None,
+                g_r[:, 7:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None, None, None)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

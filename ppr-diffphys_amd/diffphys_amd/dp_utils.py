@@ -414,6 +414,74 @@ def joint_wrench(body_q, body_qd, env, refs, target_ke, target_kd, torques=None)
     return JointWrench.apply(body_q, body_qd, act3, tgt3, ke3, kd3, env)
 
 
+def generalized_force(body_q, body_f, env, efforts="actuator"):
+    """The generalised joint forces of per-body wrenches -- the transpose of the articulation's Jacobian: body_q (..., nb, 7) poses
+    (p, q xyzw; wp_pos rows reshaped to (..., nb, 7)) and body_f (..., nb, 6) wrenches (torque, force) in world axes, the force acting
+    at the body's centre of mass -- a ``grf``, ``jaf`` or body_f row -- -> (..., nqd) in the joint_qd layout: for every REVOLUTE and
+    COMPOUND dof the torque the wrenches on the joint's subtree exert about its axis, for a FREE joint (R_wj^-1 moment about the child
+    body's centre of mass, R_wj^-1 force) of the net wrench on its subtree; FIXED joints have no entry.
+    efforts="actuator": a COMPOUND joint's entries are the efforts jf_k with sum_k axis_k jf_k of the same projections -- the units of
+    ``torques`` and of the PD force, conjugate to the measured rates of ``joint_coords``; singular at |second angle| = pi / 2.
+    efforts="generalized": the bare projections, conjugate to the generalised rates.  The two differ for COMPOUND joints only.  The
+    FREE entries are conjugate to the child body's twist (w, v), NOT to ``joint_coords``' FREE linear rate (which carries Warp's
+    unrotated-com lever).  One HIP launch (``dp_model.GeneralizedForce``), differentiable in both tensors (raw partials; quaternions
+    are taken as they are).  float32 GPU tensors only."""
+    from .dp_model import GeneralizedForce
+
+    _need_gpu("generalized_force", body_q, body_f)
+    _check_states("generalized_force", body_q, body_f, int(env.nb))
+    return GeneralizedForce.apply(body_q, body_f, env, efforts)
+
+
+def _q_rot(q, v, inverse=False):
+    """R(q) v, or R(q)^T v: the rollouts' form, x (2 w^2 - 1) +- 2 w (u x x) + 2 u (u . x) with q = (u, w)"""
+    u, w = q[..., :3], q[..., 3:]
+    c = 2.0 * w * torch.cross(u, v, dim=-1)
+    return v * (2.0 * w * w - 1.0) + (-c if inverse else c) + 2.0 * u * (u * v).sum(-1, keepdim=True)
+
+
+def inertial_wrench(body_q, body_qd, body_qd_next, dt, body_mass, body_inertia, env):
+    """The total body_f (..., nb, 6) = (torque, force) for which one step of the rollouts' integrator (integrate_bodies,
+    integrator_euler.py:21-91 of the reference) takes the twists body_qd (..., nb, 6) of the poses body_q (..., nb, 7) to body_qd_next,
+    both in Warp order (w, v): the integrator solved for its force input --
+        f = m ((v' - v) / dt - gravity [m != 0])
+        t = R (I (R^T w' / (1 - 0.1 dt) - R^T w) / dt + R^T w x I R^T w),   R = R(q)
+    with gravity on the bodies with mass, the gyroscopic term and the (1 - 0.1 dt) angular damping undone.  body_mass broadcastable to
+    (..., nb), body_inertia (body frame, about the centre of mass: the rollouts' ``body_inertia``) to (..., nb, 3, 3); gravity is the
+    env's.  EXACT (to rounding) where the step clamped neither w' nor v' at +-10, for unit quaternions and a body_inv_inertia that is
+    the inverse of body_inertia; a clamped component has lost its force and comes back too small.  A body without mass gets force 0.
+    Plain torch on the tensors' device and dtype, differentiable by autograd in every tensor argument."""
+    nb = int(env.nb)
+    _check_states("inertial_wrench", body_q, body_qd, nb)
+    _check_states("inertial_wrench", body_q, body_qd_next, nb)
+    gravity = torch.as_tensor([float(g) for g in env.template()["gravity"]], dtype=body_q.dtype, device=body_q.device)
+    r0 = body_q[..., 3:]
+    w0, v0, w1, v1 = body_qd[..., :3], body_qd[..., 3:], body_qd_next[..., :3], body_qd_next[..., 3:]
+    mass = torch.as_tensor(body_mass, dtype=body_q.dtype, device=body_q.device)[..., None]
+    inertia = torch.as_tensor(body_inertia, dtype=body_q.dtype, device=body_q.device)
+    f = mass * ((v1 - v0) / dt - gravity * (mass != 0).to(body_q.dtype))
+    wb = _q_rot(r0, w0, inverse=True)
+    Iwb = (inertia @ wb[..., None])[..., 0]
+    dwb = (_q_rot(r0, w1 / (1.0 - 0.1 * dt), inverse=True) - wb) / dt
+    tb = (inertia @ dwb[..., None])[..., 0]
+    t = _q_rot(r0, tb + torch.cross(wb, Iwb, dim=-1))
+    return torch.cat([t, f.expand(t.shape)], -1)
+
+
+def inverse_dynamics(body_q, body_qd, body_qd_next, dt, body_mass, body_inertia, env, external=None, efforts="actuator"):
+    """The joint-space forces a motion needs: ``generalized_force(body_q, inertial_wrench(...) - external, env, efforts)`` -> (..., nqd).
+    ``external`` (..., nb, 6): the wrenches something other than the joints supplies (a rollout's grf = res_f + ground_wrench(state));
+    None: nothing, every body's whole inertial wrench is asked of the joints.
+    SIGN: the entries are what the bodies RECEIVE, read in joint space.  A rollout's joint pass puts -axis * jf on the child body, so on
+    a rollout's own states the REVOLUTE / COMPOUND entries are -jf (jf = PD force + ``torques`` - limit force: with zero gains, minus the
+    applied torques), and the FREE entries are the residual wrench on the root that no joint and no ``external`` explains -- zero for
+    a physical motion.  HIP (``generalized_force``): float32 GPU tensors only; differentiable in every tensor argument."""
+    need = inertial_wrench(body_q, body_qd, body_qd_next, dt, body_mass, body_inertia, env)
+    if external is not None:
+        need = need - external
+    return generalized_force(body_q, need.contiguous(), env, efforts)
+
+
 def compute_com(body_q, part_com, part_mass):
     """mass-weighted COM of one articulation (numpy)   dp_utils.py:86-90"""
     from scipy.spatial.transform import Rotation as R

@@ -759,8 +759,8 @@ def _env_table(env, key, build):
     return env._contact_table[key]
 
 
-def _state_op_check(op, kind, width, table, nb, rows, bare=False):
-    """The argument check of the ten state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+def _state_op_check(op, kind, width, table, nb, rows, bare=False, name=None, columns=None):
+    """The argument check of the twelve state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
@@ -768,7 +768,7 @@ def _state_op_check(op, kind, width, table, nb, rows, bare=False):
         raise ValueError("%s: the table must come from hip_backend.%s_table (it carries its dimensions)" % (op, _BUILDER.get(kind, kind)))
     if tag is not None and tag[0] != kind:
         raise ValueError("%s: a %s table; the op takes one from hip_backend.%s_table" % (op, tag[0], _BUILDER.get(kind, kind)))
-    name, columns = _ROWS[width]
+    name, columns = (name, columns) if name else _ROWS[width]   # (the generalised force's 13 floats are not a state row)
     if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != width:
         raise ValueError("%s: %s must be [n, %d] = %s rows; got %s" % (op, name, width, columns, tuple(getattr(rows, "shape", ()))))
     n = int(rows.shape[0])
@@ -1168,6 +1168,42 @@ def joint_wrench_vjp(table, nb, rows, g_out):
     _grad_check("joint_wrench_vjp", "g_out", g_out, n, _JW_OUT)
     g_b = torch.empty(n, _JW_ROW, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_JOINT_WRENCH, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", n * _JW_OUT),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
+POSE_GENERALIZED_FORCE = 15   # (code 14 is not assigned either: include/ppr_diffphys.h)
+_GF_EFFORTS = {"actuator": "measured", "generalized": "generalized"}   # effort convention -> the joint table's mode it rides on
+
+
+def efforts_mode(efforts):
+    """The ``rates`` of the joint table that carries an effort convention of ``generalized_force``: "actuator" efforts are conjugate to
+    the measured rates (mode 0), "generalized" efforts to the generalised rates (mode 1)."""
+    if efforts not in _GF_EFFORTS:
+        raise ValueError("generalized_force: efforts must be 'actuator' or 'generalized'; got %r" % (efforts,))
+    return _GF_EFFORTS[efforts]
+
+
+def generalized_force(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_GENERALIZED_FORCE: rows [n, 13] = (p, q xyzw, t, f) per body -- a pose and a wrench (torque, force; world
+    axes, the force at the body's centre of mass) --, n a multiple of nb (row i is body i % nb of set i // nb), and the joint table of
+    ``joint_coords`` -> [n / nb, nqd]: per REVOLUTE / COMPOUND dof the torque about its axis, per FREE joint the net wrench on its
+    subtree, in the joint_qd layout.  The table's mode selects the COMPOUND convention: "measured" = actuator efforts, "generalized" =
+    generalised forces (``efforts_mode``).  Fixed summation order: a set's bits depend neither on the call nor on the other sets."""
+    n, (_, _, nqd) = _state_op_check("generalized_force", "joint", 13, table, int(nb), rows, name="rows", columns="(p, q xyzw, t, f)")
+    out = torch.empty(n // int(nb), nqd, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_GENERALIZED_FORCE, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def generalized_force_vjp(table, nb, rows, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_GENERALIZED_FORCE: g_out [n / nb, nqd] -> g_rows [n, 13], the raw partials with respect to pose and
+    wrench (quaternion entries not projected)."""
+    n, (_, _, nqd) = _state_op_check("generalized_force_vjp", "joint", 13, table, int(nb), rows, name="rows", columns="(p, q xyzw, t, f)")
+    sets = n // int(nb)
+    _grad_check("generalized_force_vjp", "g_out", g_out, sets, nqd)
+    g_b = torch.empty(n, 13, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_GENERALIZED_FORCE, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", sets * nqd),
                                 None, _ptr(g_b, "g_b"), _stream()))
     return g_b
 

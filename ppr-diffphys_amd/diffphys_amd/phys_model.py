@@ -748,7 +748,7 @@ class phys_model(nn.Module):
         return st["out"]
 
     @torch.no_grad()
-    def query(self, img_size=None, joint_coords=False, centroidal=False, contacts=False):
+    def query(self, img_size=None, joint_coords=False, centroidal=False, contacts=False, efforts=False):
         """Env 0 of the last forward(), frame by frame, in the reference's keys (dp_model.py:843-902): the simulated, target and
         control-reference robots POSED -- the reference hands trimesh objects to its renderer (articulate_robot_rbrt:
         collision-mesh vertices rotated and translated by each body's pose); here each is the array of those posed vertices
@@ -763,7 +763,10 @@ class phys_model(nn.Module):
         (dp_utils.centroidal; `com` / `com_k` above keep the template masses, as the reference).
         contacts=True adds `sim_contacts`, a dict of arrays per frame and body -- height [F, nb] (+inf for a body without contact
         candidates), point_xz [F, nb, 2], velocity [F, nb, 3], depth, count [F, nb] -- of `sim_poses` and the frame twists
-        (dp_utils.contact_state: the lowest candidate of every body, and how many of its candidates touch)."""
+        (dp_utils.contact_state: the lowest candidate of every body, and how many of its candidates touch).
+        efforts=True adds `sim_joint_efforts` [F, nqd]: `jaf` of each frame read in joint space (dp_utils.generalized_force of
+        `sim_poses` and env 0's jaf, actuator efforts, the joint_qd layout) -- how hard every actuator pulled, and the net joint
+        wrench on the floating root."""
         sim = np.stack(list(self.sim_trajs), 0).astype(np.float64)
         tgt = np.stack(list(self.target_trajs), 0).astype(np.float64)
         ref = np.stack(list(self.pid_ref), 0).astype(np.float64)
@@ -824,4 +827,11 @@ class phys_model(nn.Module):
             up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
             cs = contact_state(up(self.sim_trajs), up(vels), self.env)
             data["sim_contacts"] = {k: v.cpu().numpy() for k, v in cs._asdict().items()}
+        if efforts:
+            from .dp_utils import generalized_force as _generalized_force
+
+            up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
+            nb = int(self.env.nb)
+            jaf0 = torch.stack(self.jafs, 0)[:, :nb].to(self.device, torch.float32).contiguous()   # env 0
+            data["sim_joint_efforts"] = _generalized_force(up(self.sim_trajs), jaf0, self.env, efforts="actuator").cpu().numpy()
         return data
