@@ -510,15 +510,44 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * A table whose nb is not the call's a_broadcast is not read beyond its header: out [n / nb][nqd of THAT header] / g_b are then
  * written as zeros.  A parent index or a coordinate range outside the set is handled as for PD_POSE_JOINT_COORDS.
  *
+ * Rigid-body twists of joint rates -- the articulation's Jacobian applied to joint rates, the conjugate of PD_POSE_GENERALIZED_FORCE:
+ * the twist (w, v) every body has when the joints move at those rates and the links are rigid:
+ *   PD_POSE_BODY_TWIST     b = rows [n][13] = (p, q xyzw, r_0..r_5): the pose of a state row followed by the rates of THIS body's joint
+ *                          in six slots, slot k = joint_qd[qd_start + k] for k below the joint's dof count (6 FREE, 3 COMPOUND,
+ *                          1 REVOLUTE, 0 FIXED); a further slot never enters arithmetic and its gradient is written as 0.
+ *                          a_broadcast = nb as above (nb < 1 or n % nb != 0 is refused at every n; nb <= 256).  a = ONE joint table of
+ *                          PD_POSE_JOINT_COORDS, unchanged, for all elements; its mode float [3] selects the rate convention of
+ *                          COMPOUND joints (0 measured, 1 generalized) -> out [n][6] = (w, v) per body, world axes, v the velocity of
+ *                          the body's centre of mass x_b = p_b + R(q_b) com_b.  On the frames, axes and anchors of
+ *                          PD_POSE_GENERALIZED_FORCE, per joint i:
+ *                            REVOLUTE  w_i = (R_wj axis) r_0                 u_i = 0              o_i = p_wj
+ *                            COMPOUND  w_i = sum_k axw_k rho_k               u_i = 0              o_i = p_wj;  mode 1: rho = r; mode 0:
+ *                                      rho = G^-1 r, the Gram solve of the rates (singular at |q_1| = pi / 2)
+ *                            FREE      w_i = R_wj r_0..2                     u_i = R_wj r_3..5    o_i = x_i, the child's centre of mass
+ *                            FIXED     nothing
+ *                          w_b = sum w_i and v_b = sum (u_i + w_i x (x_b - o_i)) over the joints of b and of its ancestors: the exact
+ *                          transpose of PD_POSE_GENERALIZED_FORCE in each mode (sum tau . r = sum wrench . twist).  The FREE linear
+ *                          slots are R_wj^-1 of the centre-of-mass velocity the joint contributes, NOT PD_POSE_JOINT_COORDS' FREE
+ *                          linear rate.  A lane per body, whole state sets per workgroup; the ancestor sums go through LDS level by
+ *                          level from the roots down, every lever formed from differences about the origin of the set's body 0.  No
+ *                          atomics: a set's bits depend neither on the run nor on n nor on the set's place in the launch.
+ *                          VJP: g_out [n][6] -> g_b [n][13], the raw partials with respect to pose and rate slots (quaternion entries
+ *                          not projected): the ancestor sum of w again, subtree sums of the twists' adjoints, the joint's adjoint and
+ *                          the parent-side pose adjoints gathered as for PD_POSE_JOINT_COORDS.  The table has no gradient: a
+ *                          non-NULL g_a is refused, at every n.
+ * A table whose nb is not the call's a_broadcast is not read beyond its first float: out / g_b are then written as zeros.  A parent
+ * index or a coordinate range outside the set is handled as for PD_POSE_JOINT_COORDS.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
  * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE,
- * PD_POSE_JOINT_WRENCH and PD_POSE_GENERALIZED_FORCE are new op codes of the two entries: no symbol or signature changed, the version
- * stays 9.  The enum has gaps: codes 7, 8, 10, 12 and 14 are not assigned and are refused as "unknown op" -- callers and tests of
- * version 9 rely on that refusal (of 7 and 8 since the centroidal op took 9, of 10 since the contact state took 11, of 12 since the
- * joint wrench took 13, of 14 since the generalised force took 15), so the five stay free for as long as the version is 9. */
+ * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE and PD_POSE_BODY_TWIST are new op codes of the two entries: no symbol or signature
+ * changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14 and 16 are not assigned and are refused as "unknown op" --
+ * callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal op took 9, of 10 since the contact state took
+ * 11, of 12 since the joint wrench took 13, of 14 since the generalised force took 15, of 16 since the body twist took 17), so the six
+ * stay free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
        PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11,
-       PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15 };
+       PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15, PD_POSE_BODY_TWIST = 17 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

@@ -1402,6 +1402,184 @@ __global__ __launch_bounds__(256) void k_generalized_force_vjp(int nsets, int nb
   dst[10] = adj_f.x; dst[11] = adj_f.y; dst[12] = adj_f.z;
 }
 
+// ---- PD_POSE_BODY_TWIST: the rigid twists of joint rates -- J of the articulation applied to rows (p, q xyzw, r_0..r_5), the exact
+// transpose of PD_POSE_GENERALIZED_FORCE in each mode -- and its vector-Jacobian product with respect to poses and rates.  Per joint i,
+// on jc_joint's frames and jc_compound's angles and axes, r_i = the joint's anchor - o0 as gf_load forms it:
+//   REVOLUTE  w_i = (R_wj axis) r_0                   u_i = 0             anchor p_wj
+//   COMPOUND  w_i = R_wj R_off sum_k a_k rho_k        u_i = 0             anchor p_wj;  mode 1 (generalized): rho = r; mode 0 (measured):
+//             rho = G^-1 r, the Gram solve (rho_1 = r_1, (rho_0, rho_2) = ((r_0 - s r_2), (r_2 - s r_0)) / (1 - s^2))
+//   FREE      w_i = R_wj r_0..2                       u_i = R_wj r_3..5   anchor x_i;   FIXED: nothing
+//   w_b = W_b = sum w_i,  v_b = C_b + W_b x d_b,  C_b = sum (u_i - w_i x r_i), the sums over b and its ancestors, d_b = x_b - o0
+// Mapping and sweeps are the generalised force's, mirrored: forward the ancestor sum (gf_down), VJP the ancestor sum of w (adj d needs
+// W_b), then subtree sums of (adj C, adj W) = (g_v, g_w + d x g_v) through gf_up, the joint's adjoint -- the rate adjoints are the
+// generalised force's projections --, and the parent-side pose adjoint handed over.  No atomics; every float has one writing lane.
+// Ancestor sums of (a, b): levels from the roots down, a body adds its parent's slot to its own and publishes it -- the loop of
+// k_generalized_force_vjp, which keeps its own copy (calling this from there changes that kernel's instruction stream).
+__device__ __forceinline__ void gf_down(float *down, const GfTree &T, const SetLane &L, int nb, v3 &a, v3 &b) {
+  float *dn = down + threadIdx.x * GF_S;
+  gf_put(dn, a, b);
+  for (int lev = 1; lev <= T.maxd; ++lev) {
+    __syncthreads();
+    if (L.in_set && T.dep == lev && T.parent >= 0) {
+      const float *pp = down + (L.set_l * nb + T.parent) * GF_S;
+      a += ld3(pp); b += ld3(pp + 3);
+      gf_put(dn, a, b);
+    }
+  }
+}
+struct BtJoint { v3 w, u, e; JcCompound C; float rho[3]; };  // e: the COMPOUND rate in the offset frame, w = R(q_w) e
+__device__ __forceinline__ void bt_joint(const GfBody &B, bool generalized, BtJoint &Q) {
+  const JcJoint &J = B.J;
+  Q.w = V3(0, 0, 0); Q.u = Q.w; Q.e = Q.w;
+  if (J.type == PD_JOINT_FREE) {
+    Q.w = qrot(J.q_wj, B.s.w); Q.u = qrot(J.q_wj, B.s.v);
+  } else if (J.type == PD_JOINT_REVOLUTE) {
+    Q.w = qrot(J.q_wj, J.axis) * B.s.w.x;
+  } else if (J.type == PD_JOINT_COMPOUND) {
+    jc_compound(J, false, Q.C);
+    const float s = Q.C.s;
+    Q.rho[0] = B.s.w.x; Q.rho[1] = B.s.w.y; Q.rho[2] = B.s.w.z;
+    if (!generalized) {
+      const float id = 1.0f / (1.0f - s * s);
+      Q.rho[0] = (B.s.w.x - s * B.s.w.z) * id; Q.rho[2] = (B.s.w.z - s * B.s.w.x) * id;
+    }
+    Q.e = V3(Q.rho[0], 0, 0) + Q.C.a1 * Q.rho[1] + Q.C.a2 * Q.rho[2];
+    Q.w = qrot(Q.C.q_w, Q.e);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_body_twist_fwd(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                        float *__restrict__ out) {
+  __shared__ float down[256 * GF_S];
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *o = out + ((size_t)L.set * nb + L.body) * 6;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
+    if (L.active)
+      for (int k = 0; k < 6; ++k) o[k] = 0.0f;
+    return;
+  }
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  GfBody B;
+  v3 W = V3(0, 0, 0), C = W;
+  if (L.active) {
+    gf_load(tab, nb, L.body, rows + (size_t)L.set * nb * PD_ADJ, B);
+    BtJoint Q;
+    bt_joint(B, generalized, Q);
+    W = Q.w; C = Q.u - cross(Q.w, B.r);
+  }
+  gf_down(down, T, L, nb, W, C);
+  if (!L.active) return;
+  const v3 v = C + cross(W, B.d);
+  o[0] = W.x; o[1] = W.y; o[2] = W.z; o[3] = v.x; o[4] = v.y; o[5] = v.z;
+}
+
+// g_b [n][13]: the raw partials of <g_out, out> with respect to (p, q, r_0..r_5) of every body; a slot past the joint's dofs gets zero.
+__global__ __launch_bounds__(256) void k_body_twist_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                        const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float slot[256 * GF_S], down[256 * GF_S], pslot[256 * GF_S];  // subtree sums / ancestor sums / the parent-side pose adjoint
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *dst = g_b + ((size_t)L.set * nb + L.body) * PD_ADJ;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {
+    if (L.active)
+      for (int k = 0; k < PD_ADJ; ++k) dst[k] = 0.0f;
+    return;
+  }
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  GfBody B;
+  BtJoint Q;
+  v3 W = V3(0, 0, 0), C = W;
+  if (L.active) {
+    gf_load(tab, nb, L.body, rows + (size_t)L.set * nb * PD_ADJ, B);
+    bt_joint(B, generalized, Q);
+    W = Q.w; C = Q.u - cross(Q.w, B.r);
+  }
+  gf_down(down, T, L, nb, W, C);
+  // the body's own share: w_b = W, v_b = C + W x d
+  v3 F = V3(0, 0, 0), M = F, adj_d = F;
+  if (L.active) {
+    const float *g = g_out + ((size_t)L.set * nb + L.body) * 6;
+    F = ld3(g + 3); M = ld3(g);
+    adj_cross(W, B.d, M, adj_d, F);
+  }
+  gf_up(slot, T, L, nb, F, M);  // (adj C, adj W) of the joint's subtree
+  v3 own_p = V3(0, 0, 0), par_p = own_p;
+  qt own_q = Q4(0, 0, 0, 0), par_q = own_q;
+  float gr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (L.active) {
+    const JcJoint &J = B.J;
+    const v3 N = M - cross(B.r, F);  // adj w_i: c_i = u_i - w_i x r_i
+    v3 adj_r = cross(Q.w, F);
+    qt adj_q_wj = Q4(0, 0, 0, 0);
+    if (J.type == PD_JOINT_FREE) {
+      const v3 a = qrot_inv(J.q_wj, N), l = qrot_inv(J.q_wj, F);
+      gr[0] = a.x; gr[1] = a.y; gr[2] = a.z; gr[3] = l.x; gr[4] = l.y; gr[5] = l.z;
+      adj_qrot_q(J.q_wj, B.s.w, adj_q_wj, N);
+      adj_qrot_q(J.q_wj, B.s.v, adj_q_wj, F);
+    } else if (J.type == PD_JOINT_REVOLUTE) {
+      gr[0] = dot(qrot(J.q_wj, J.axis), N);
+      adj_qrot_q(J.q_wj, J.axis, adj_q_wj, N * B.s.w.x);
+    } else if (J.type == PD_JOINT_COMPOUND) {
+      const JcCompound &K = Q.C;
+      const v3 u = qrot_inv(K.q_w, N);  // adj e
+      float gm[3] = {u.x, dot(K.a1, u), dot(K.a2, u)}, g_s = 0.0f;  // adj rho
+      gr[0] = gm[0]; gr[1] = gm[1]; gr[2] = gm[2];
+      if (!generalized) {  // rho_0 = (r_0 - s r_2) id, rho_2 = (r_2 - s r_0) id, id = 1 / (1 - s^2)
+        const float id = 1.0f / (1.0f - K.s * K.s);
+        g_s = (gm[0] * (2.0f * K.s * Q.rho[0] - B.s.w.z) + gm[2] * (2.0f * K.s * Q.rho[2] - B.s.w.x)) * id;
+        gr[0] = (gm[0] - K.s * gm[2]) * id;
+        gr[2] = (gm[2] - K.s * gm[0]) * id;
+      }
+      v3 adj_a1 = u * Q.rho[1], adj_a2 = u * Q.rho[2];
+      adj_a2.x += g_s;
+      qt adj_q_w = Q4(0, 0, 0, 0), adj_r_err = adj_q_w;
+      adj_qrot_q(K.q_w, Q.e, adj_q_w, N);
+      adj_qmul_a(J.q_off, adj_q_wj, adj_q_w);
+      // the axis chain and the decomposition, as k_generalized_force_vjp
+      float adj_ang[3] = {0.f, 0.f, 0.f};
+      qt adj_q10 = Q4(0, 0, 0, 0), adj_q_1 = adj_q10, adj_q_0 = adj_q10;
+      adj_qrot_q(K.q10, V3(0, 0, 1), adj_q10, adj_a2);
+      adj_qmul(K.q_1, K.q_0, adj_q_1, adj_q_0, adj_q10);
+      adj_q_axis_angle(K.a1, K.ang[1], adj_a1, adj_ang[1], adj_q_1);
+      adj_qrot_q(K.q_0, V3(0, 1, 0), adj_q_0, adj_a1);
+      adj_q_axis_angle_ang(V3(1, 0, 0), K.ang[0], adj_ang[0], adj_q_0);
+      qt adj_q_pc = Q4(0, 0, 0, 0), adj_qa = adj_q_pc;
+      quat_decompose_adj(K.q_pc, K.c0, K.c1, K.c2, adj_ang, adj_q_pc);
+      adj_qmul_a(J.q_off, adj_qa, adj_q_pc);
+      adj_qmul_b(qconj(J.q_off), adj_r_err, adj_qa);
+      qt adj_cq = Q4(0, 0, 0, 0);
+      adj_qmul(qconj(J.q_wj), B.s.r, adj_cq, own_q, adj_r_err);  // r_err = conj(q_wj) q_c
+      adj_q_wj += qconj(adj_cq);
+    }
+    if (J.type == PD_JOINT_FREE) adj_d += adj_r;  // (a FREE joint's r is d)
+    else if (J.parent >= 0) {                     // r = (p_p - o0) + R(q_p) p_pj
+      par_p += adj_r;
+      adj_qrot_q(J.qp, J.p_pj, par_q, adj_r);
+    }
+    if (J.parent >= 0) adj_qmul_a(J.q_pj, par_q, adj_q_wj);  // q_wj = q_p q_pj
+    own_p += adj_d;  // d = (p_b - o0) + R(q_b) com_b
+    adj_qrot_q(B.s.r, J.com, own_q, adj_d);
+  }
+  float *ps = pslot + threadIdx.x * GF_S;
+  ps[0] = par_p.x; ps[1] = par_p.y; ps[2] = par_p.z; ps[3] = par_q.x; ps[4] = par_q.y; ps[5] = par_q.z; ps[6] = par_q.w;
+  __syncthreads();
+  if (!L.active) return;
+  for (int k = 0; k < T.nch; ++k) {
+    const int c = (int)T.ch[k];
+    if (c >= 0 && c < nb) {
+      const float *cs = pslot + (L.set_l * nb + c) * GF_S;
+      own_p += ld3(cs); own_q += ld4(cs + 3);
+    }
+  }
+  dst[0] = own_p.x; dst[1] = own_p.y; dst[2] = own_p.z;
+  dst[3] = own_q.x; dst[4] = own_q.y; dst[5] = own_q.z; dst[6] = own_q.w;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) dst[7 + k] = gr[k];
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -1424,6 +1602,7 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 //   contact state      out / g_out [n][8]; the ground wrench's contact table, no g_a; any nb
 //   joint wrench       b / g_b [n][25] = (state, the joint's controls), out / g_out [n][6]; the joint-force table, no g_a
 //   generalized force  b / g_b [n][13] = (pose, wrench), out / g_out [n / nb][nqd]; the joint table, no g_a
+//   body twist         b / g_b [n][13] = (pose, the joint's rates in six slots), out / g_out [n][6]; the joint table, no g_a
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
 struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
 constexpr TabledOp TABLED[] = {
@@ -1433,6 +1612,7 @@ constexpr TabledOp TABLED[] = {
     {PD_POSE_CONTACT_STATE, "PD_POSE_CONTACT_STATE", "contact", 0, false, GEO_WAVE, GEO_WAVE},
     {PD_POSE_JOINT_WRENCH, "PD_POSE_JOINT_WRENCH", "jointforce", JC_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_GENERALIZED_FORCE, "PD_POSE_GENERALIZED_FORCE", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
+    {PD_POSE_BODY_TWIST, "PD_POSE_BODY_TWIST", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
 };
 
 template <class... A>
@@ -1478,6 +1658,10 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
       if (out) hipLaunchKernelGGL(k_generalized_force_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_generalized_force_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
       break;
+    case PD_POSE_BODY_TWIST:
+      if (out) hipLaunchKernelGGL(k_body_twist_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_body_twist_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
     default:
       if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
@@ -1489,7 +1673,7 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
   if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH &&
-                         op != PD_POSE_GENERALIZED_FORCE))  // (codes 7, 8, 10, 12 and 14 are not assigned: include/ppr_diffphys.h)
+                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST))  // (codes 7, 8, 10, 12, 14 and 16 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
     if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);

@@ -283,6 +283,40 @@ class GeneralizedForce(torch.autograd.Function):
                 g_r[:, 7:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None, None, None)
 
 
+class BodyTwists(torch.autograd.Function):
+    """body_q (..., nb, 7), rates6 (..., nb, 6) = the rates of each body's joint in six slots (``hip_backend.joint_rate_slot_index``;
+    a slot no dof uses may hold anything and gets a zero gradient), env, rates -> (..., nb, 6) = (w, v) per body in world axes, v of
+    the body's centre of mass: the rigid twists those joint rates give, the articulation's Jacobian applied to them (``pd_pose_op``
+    PD_POSE_BODY_TWIST on the env's joint table, one launch forward and one for the vector-Jacobian product).  rates="generalized" or
+    "measured": the COMPOUND convention, that of ``joint_coords``.  Gathering the slots from the joint_qd layout is the caller's
+    (``dp_utils.body_twists`` does it, so that autograd sums a shared rate's gradient).  float32 GPU tensors, or an error: no CPU
+    fallback.  The gradients are the raw partials (quaternion entries not projected), nothing is scrubbed."""
+
+    @staticmethod
+    def forward(ctx, body_q, rates6, env, rates="generalized"):
+        nb = int(env.nb)
+        _need_gpu("BodyTwists", body_q, rates6)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(rates6.shape) == lead + (nb, 6)):
+            raise ValueError("BodyTwists: body_q (..., %d, 7) and rates6 (..., %d, 6) with equal leading shapes; got %s and %s" % (
+                nb, nb, tuple(body_q.shape), tuple(rates6.shape)))
+        table = hip_backend.env_joint_table(env, body_q.device, rates)
+        rows = _state_rows(body_q, rates6)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows)
+        return hip_backend.body_twists(table, nb, rows).view(lead + (nb, 6))
+
+    @staticmethod
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        lead, nb = ctx.lead, ctx.nb
+        g_r = hip_backend.body_twists_vjp(ctx.table, nb, rows, g.to(torch.float32).reshape(-1, 6).contiguous())
+        return (g_r[:, :7].reshape(lead + (nb, 7)) if ctx.needs_input_grad[0] else None,
+                g_r[:, 7:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None, None, None)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

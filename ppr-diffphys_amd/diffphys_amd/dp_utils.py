@@ -482,6 +482,114 @@ def inverse_dynamics(body_q, body_qd, body_qd_next, dt, body_mass, body_inertia,
     return generalized_force(body_q, need.contiguous(), env, efforts)
 
 
+def body_twists(body_q, joint_qd, env, rates="generalized"):
+    """The rigid-body twists of joint rates -- the articulation's Jacobian applied to them, the conjugate of ``generalized_force``:
+    body_q (..., nb, 7) poses (p, q xyzw) and joint_qd broadcastable to (..., nqd) in the joint_qd layout -> (..., nb, 6) twists in the
+    rollouts' order (w, v), world axes, v the velocity of the body's centre of mass: what every body does when the joints move at
+    those rates and the links are rigid.  ``ForwardKinematics``' velocities are NOT that (Warp's eval_fk leaves out the levers of the
+    ancestors' angular velocities); these are what ``contact_state``, ``centroidal``, ``inertial_wrench`` and ``inverse_dynamics`` assume.
+    rates="generalized" pairs with ``joint_coords(rates="generalized")`` and ``generalized_force(efforts="generalized")``,
+    rates="measured" with ``joint_coords(rates="measured")`` and ``efforts="actuator"``; they differ for COMPOUND joints only.  In each
+    pairing sum(generalized_force * joint_qd) = sum(body_f * body_twists).  A FREE joint's six entries are conjugate to
+    ``generalized_force``'s FREE entries: (R_wj^-1 w, R_wj^-1 v) of what the joint adds to the child body's twist, v of its centre of
+    mass -- NOT ``joint_coords``' FREE linear rate, which carries Warp's unrotated-com lever (``rigid_twists`` converts).  One HIP
+    launch (``dp_model.BodyTwists``), differentiable in both tensors (raw partials; quaternions are taken as they are).  The rates are
+    gathered into the op's per-body slots HERE, outside the Function, so autograd sums the gradient of a shared rate over the state
+    sets.  float32 GPU tensors only."""
+    from . import hip_backend
+    from .dp_model import BodyTwists
+
+    _need_gpu("body_twists", body_q, joint_qd)
+    nb, nqd = int(env.nb), int(env.template()["nqd"])
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7)):
+        raise ValueError("body_twists: body_q must be (..., %d, 7); got %s" % (nb, tuple(body_q.shape)))
+    lead = tuple(body_q.shape[:-2])
+    try:
+        ok = joint_qd.dim() >= 1 and tuple(torch.broadcast_shapes(tuple(joint_qd.shape), lead + (nqd,))) == lead + (nqd,)
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise ValueError("body_twists: joint_qd must broadcast to %s; got %s" % (lead + (nqd,), tuple(joint_qd.shape)))
+    hip_backend._jc_rate_mode(rates)
+    # slot k of body b <- dof qd_start[b] + k, or the appended zero column
+    t = joint_qd.expand(joint_qd.shape[:-1] + (nqd,))
+    t = torch.cat([t, t.new_zeros(t.shape[:-1] + (1,))], dim=-1)
+    idx = hip_backend.env_joint_rate_slot_index(env, body_q.device)
+    rates6 = t.index_select(-1, idx).reshape(t.shape[:-1] + (nb, 6)).expand(lead + (nb, 6))
+    return BodyTwists.apply(body_q, rates6, env, rates)
+
+
+def jacobian(body_q, env, rates="generalized"):
+    """The articulation's Jacobian: body_q (..., nb, 7) -> (..., nb, 6, nqd), column j the twists (w, v of the centre of mass, world
+    axes) of unit rate on dof j -- ``body_twists`` on the poses repeated nqd times against the identity, ONE launch of
+    S * nqd * nb rows for S state sets (Laikago: 18 * 13 rows per set), so it is meant for a few sets, not for a batch of thousands.
+    ``jacobian @ joint_qd`` is ``body_twists``; its transpose applied to wrenches is ``generalized_force`` of the paired convention.
+    Differentiable in body_q.  float32 GPU tensors only."""
+    _need_gpu("jacobian", body_q)
+    nb, nqd = int(env.nb), int(env.template()["nqd"])
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7)):
+        raise ValueError("jacobian: body_q must be (..., %d, 7); got %s" % (nb, tuple(body_q.shape)))
+    lead = tuple(body_q.shape[:-2])
+    eye = torch.eye(nqd, dtype=body_q.dtype, device=body_q.device)
+    tw = body_twists(body_q.unsqueeze(-3).expand(lead + (nqd, nb, 7)), eye.expand(lead + (nqd, nqd)), env, rates)   # (..., nqd, nb, 6)
+    return tw.permute(tuple(range(len(lead))) + (len(lead) + 1, len(lead) + 2, len(lead)))
+
+
+def mass_matrix(body_q, body_mass, body_inertia, env):
+    """The joint-space mass matrix H = sum_b J_b^T diag(R_b I_b R_b^T, m_b 1) J_b of the generalised rates: body_q (..., nb, 7),
+    body_mass broadcastable to (..., nb), body_inertia (body frame, about the centre of mass) to (..., nb, 3, 3) -> (..., nqd, nqd),
+    with qd^T H qd / 2 the kinetic energy of ``body_twists(body_q, qd, env)``.  Plain torch on ``jacobian(body_q, env, "generalized")``
+    -- its S * nqd * nb rows --, not a composite-rigid-body kernel; differentiable in every tensor argument."""
+    J = jacobian(body_q, env, "generalized")
+    mass = torch.as_tensor(body_mass, dtype=J.dtype, device=J.device)
+    inertia = torch.as_tensor(body_inertia, dtype=J.dtype, device=J.device)
+    Jw, Jv = J[..., :3, :], J[..., 3:, :]
+    cols = Jw.transpose(-1, -2)
+    A = _q_rot(body_q[..., None, 3:].expand(cols.shape[:-1] + (4,)), cols, inverse=True)   # (..., nb, nqd, 3): the angular columns in the body frame
+    IA = A @ inertia.transpose(-1, -2)                                        # rows (I a)^T
+    return (A @ IA.transpose(-1, -2)).sum(-3) + (mass[..., None, None] * (Jv.transpose(-1, -2) @ Jv)).sum(-3)
+
+
+def _free_roots(tpl):
+    """-> [(body, qd_start, the quaternion of joint_X_p)] of the template's FREE joints; ValueError if one of them has a parent."""
+    import numpy as np
+
+    nb = int(tpl["nb"])
+    ty = np.asarray(tpl["joint_type"]).reshape(nb)
+    par = np.asarray(tpl["joint_parent"]).reshape(nb)
+    qds = np.asarray(tpl["joint_qd_start"]).reshape(-1)
+    X_p = np.asarray(tpl["joint_X_p"], dtype=np.float32).reshape(nb, 7)
+    free = [b for b in range(nb) if int(ty[b]) == 4]   # JOINT_FREE
+    bad = [b for b in free if par[b] >= 0]
+    if bad:
+        raise ValueError("rigid_twists: the FREE joint of body %d has a parent (body %d); only FREE joints of the world are served" % (
+            bad[0], par[bad[0]]))
+    return [(b, int(qds[b]), X_p[b, 3:]) for b in free]
+
+
+def rigid_twists(body_q, body_qd, env):
+    """Body states whose twists may not be rigid -- ``ForwardKinematics``' outputs -- -> (..., nb, 6) rigid twists of the same joint
+    rates: the hinge rates and the FREE angular rates of ``joint_coords(body_q, body_qd, env, "generalized")``, the FREE linear
+    entries R_wj^-1 v of the FREE body's own twist, then ``body_twists``.  A rigid state (a rollout's) comes back unchanged to
+    rounding; on FK states every angular part and the rows of the FREE roots are kept and the other linear parts are replaced by the
+    rigid ones.  Robots whose FREE joints have no parent; ValueError otherwise.  Two HIP launches, differentiable in both tensors.
+    float32 GPU tensors only."""
+    from . import hip_backend
+
+    free = _free_roots(env.template())
+    _need_gpu("rigid_twists", body_q, body_qd)
+    _check_states("rigid_twists", body_q, body_qd, int(env.nb))
+    _, jqd = joint_coords(body_q, body_qd, env, "generalized")
+    if free:
+        # (the index and the joint frames live on the model: nothing is uploaded per call, so a captured iteration can hold the call)
+        idx, quats = hip_backend._env_table(env, ("freeroots", str(body_q.device)), lambda tpl: (
+            torch.as_tensor([s + 3 + k for _, s, _ in _free_roots(tpl) for k in range(3)], dtype=torch.long, device=body_q.device),
+            torch.as_tensor([[float(x) for x in q] for _, _, q in _free_roots(tpl)], dtype=torch.float32, device=body_q.device)))
+        lin = [_q_rot(quats[k].expand(body_qd.shape[:-2] + (4,)), body_qd[..., b, 3:], inverse=True) for k, (b, _, _) in enumerate(free)]
+        jqd = jqd.index_copy(-1, idx, torch.cat(lin, dim=-1))
+    return body_twists(body_q, jqd, env, "generalized")
+
+
 def compute_com(body_q, part_com, part_mass):
     """mass-weighted COM of one articulation (numpy)   dp_utils.py:86-90"""
     from scipy.spatial.transform import Rotation as R

@@ -760,7 +760,7 @@ def _env_table(env, key, build):
 
 
 def _state_op_check(op, kind, width, table, nb, rows, bare=False, name=None, columns=None):
-    """The argument check of the twelve state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    """The argument check of the fourteen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
@@ -1204,6 +1204,52 @@ def generalized_force_vjp(table, nb, rows, g_out):
     _grad_check("generalized_force_vjp", "g_out", g_out, sets, nqd)
     g_b = torch.empty(n, 13, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_GENERALIZED_FORCE, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", sets * nqd),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
+POSE_BODY_TWIST = 17   # (code 16 is not assigned either: include/ppr_diffphys.h)
+_BT_COLUMNS = "(p, q xyzw, r[6])"
+
+
+def joint_rate_slot_index(tpl):
+    """[nb, 6] int64 numpy: the dof behind rate slot k of each body's joint, qd_start + k for k below the joint's dof count (6 FREE,
+    3 COMPOUND, 1 REVOLUTE, 0 FIXED), or nqd -- a column of zeros the caller appends -- for a slot no dof uses."""
+    nb, nqd = int(tpl["nb"]), int(tpl["nqd"])
+    ty = np.asarray(tpl["joint_type"], dtype=np.int64).reshape(nb)
+    qds = np.asarray(tpl["joint_qd_start"], dtype=np.int64).reshape(-1)[:nb]
+    idx = np.full((nb, 6), nqd, np.int64)
+    for b in range(nb):
+        n_dof = _JC_WIDTH.get(int(ty[b]), (0, 0))[1]
+        idx[b, :n_dof] = qds[b] + np.arange(n_dof)
+    return idx
+
+
+def env_joint_rate_slot_index(env, device):
+    """``joint_rate_slot_index`` of a :class:`diffphys_amd.sim.Model` as a flat [6 nb] int64 tensor on ``device``, cached on the model."""
+    return _env_table(env, ("jointrateslots", str(torch.device(device))),
+                      lambda tpl: torch.from_numpy(joint_rate_slot_index(tpl).reshape(-1)).to(device))
+
+
+def body_twists(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_BODY_TWIST: rows [n, 13] = (p, q xyzw, r[6]) per body -- a pose and the rates of that body's joint in six
+    slots (``joint_rate_slot_index``) --, n a multiple of nb (row i is body i % nb of set i // nb), and the joint table of
+    ``joint_coords`` -> [n, 6] = (w, v) per body, world axes, v of the body's centre of mass: the rigid twists those rates give, the
+    articulation's Jacobian applied to them.  The table's mode selects the COMPOUND convention: "measured" or "generalized" rates.
+    Fixed summation order: a set's bits depend neither on the call nor on the other sets."""
+    n, _ = _state_op_check("body_twists", "joint", 13, table, int(nb), rows, name="rows", columns=_BT_COLUMNS)
+    out = torch.empty(n, 6, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_BODY_TWIST, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def body_twists_vjp(table, nb, rows, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_BODY_TWIST: g_out [n, 6] -> g_rows [n, 13], the raw partials with respect to pose and rate slots
+    (quaternion entries not projected; zero in a slot no dof uses)."""
+    n, _ = _state_op_check("body_twists_vjp", "joint", 13, table, int(nb), rows, name="rows", columns=_BT_COLUMNS)
+    _grad_check("body_twists_vjp", "g_out", g_out, n, 6)
+    g_b = torch.empty(n, 13, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_BODY_TWIST, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", n * 6),
                                 None, _ptr(g_b, "g_b"), _stream()))
     return g_b
 

@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import robots, sim
 from .dataloader import mocap_tensors, bullet2gl, parse_amp
 from .dp_model import ForwardKinematics, ForwardWarp, ForwardWarpTrajLossFK, convert_ppr_warp
-from .dp_utils import (compose_delta, contact_state, penetration_loss, project_bodies, reduce_loss, reduce_loss_masked, reproj_loss,
+from .dp_utils import (compose_delta, contact_state, penetration_loss, project_bodies, reduce_loss, reduce_loss_masked, reproj_loss, rigid_twists,
                        rotate_frame, rotate_frame_vel, se3_loss, skate_loss)
 from .geom_utils import fid_reindex
 from .grad_guard import GradHistory
@@ -521,7 +521,12 @@ class phys_model(nn.Module):
         # reg_pen / reg_skate (opt-in, off at weight 0: nothing of them is evaluated, no key enters loss_dict): ground penetration and
         # foot skate of the KINEMATIC states, like reg_foot -- the FK poses and twists in the rollouts' (w, v) order, as FK returns them
         wt_pen, wt_skate = (float(self.opts.get(k, 0.0) or 0.0) for k in ("reg_pen_wt", "reg_skate_wt"))
-        contact = contact_state(queried_position, queried_velocity, self.env) if (wt_pen > 0 or wt_skate > 0) else None
+        # rigid_twists (opt-in): FK's linear velocities lack the levers of the ancestors' angular velocities; when
+        # on, the contact state sees the rigid twists of the same joint rates instead.  Off: nothing of it is evaluated
+        contact = None
+        if wt_pen > 0 or wt_skate > 0:
+            contact_velocity = rigid_twists(queried_position, queried_velocity, self.env) if self.opts.get("rigid_twists") else queried_velocity
+            contact = contact_state(queried_position, contact_velocity, self.env)
         sim_velocity = convert_ppr_warp(sim_velocity)
         queried_velocity = convert_ppr_warp(queried_velocity)
         foot_height = self.get_foot_height(queried_position)

@@ -48,6 +48,8 @@ def get_opts(argv=None):
                     "(dp_utils.penetration_loss: mean squared summed depth of every body's touching contact candidates)")
     ap.add_argument("--reg_skate_wt", type=float, default=0.0, help="weight of the foot-skate term on the kinematic states "
                     "(dp_utils.skate_loss: horizontal speed of every body's lowest contact candidate, within 2 cm of the ground)")
+    ap.add_argument("--rigid_twists", action="store_true", help="reg_pen / reg_skate see the rigid-body twists of the kinematic joint rates "
+                    "(dp_utils.rigid_twists) instead of forward kinematics' velocities, which lack the ancestors' levers")
     ap.add_argument("--traj_2d_wt", type=float, default=0.0, help="weight of the 2D keypoint reprojection term (needs --cameras)")
     ap.add_argument("--cameras", default=None, help=".npz with rtk [frames, 4, 4] (rows 0-2 [R|t], row 3 fx fy cx cy) and optionally "
                     "target_2d [frames, bodies, 2]: the cameras / observed keypoints of the 2D term (phys_model.set_cameras)")
