@@ -538,16 +538,51 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * A table whose nb is not the call's a_broadcast is not read beyond its first float: out / g_b are then written as zeros.  A parent
  * index or a coordinate range outside the set is handled as for PD_POSE_JOINT_COORDS.
  *
+ * Body accelerations of a state -- J qdd + Jdot qd of the articulation, the second-order term next to PD_POSE_BODY_TWIST (DESIGN.md
+ * section 8):
+ *   PD_POSE_BODY_ACCEL     b = rows [n][19] = (p, q xyzw, w, v, s_0..s_5): a state row as for PD_POSE_JOINT_COORDS (w the world angular
+ *                          velocity, v the velocity of the body's centre of mass) followed by the TIME DERIVATIVES of the rate slots of
+ *                          THIS body's joint, in PD_POSE_BODY_TWIST's slot layout (slot k = dof qd_start + k below the joint's dof
+ *                          count; a further slot never enters arithmetic and its gradient is written as 0).  a_broadcast = nb and
+ *                          a = ONE joint table of PD_POSE_JOINT_COORDS as above; its mode float [3] says in which convention the
+ *                          COMPOUND slots are read (1 generalized, 0 measured) -> out [n][6] = (alpha, a) per body, world axes, a the
+ *                          acceleration of the body's centre of mass x_b = p_b + R(q_b) com_b.  State-based: every velocity-dependent
+ *                          term comes from the row's own twist and its parent's; no joint rates are passed.  With pi the parent of
+ *                          joint i (w_pi = v_pi = 0 and a constant frame without one), o0 the origin of the set's body 0, d_b = x_b - o0:
+ *                            every joint  om_i = w_i - w_pi
+ *                            REVOLUTE  omd_i = (R_wj axis) s_0 + w_pi x om_i      ud_i = 0     o_i = p_wj,
+ *                                      od_i = v_pi + w_pi x (p_wj - x_pi)  (0 without a parent)
+ *                            COMPOUND  ah_k = R_wj R_off a_k, m_k = ah_k . om_i, rho = G^-1 m (the Gram solve of PD_POSE_JOINT_COORDS'
+ *                                      generalized rates, s = a_0 . a_2, in EITHER mode);  mode 1: rhod = s_0..2;  mode 0:
+ *                                      rhod = G^-1 (s_0 - sd rho_2, s_1, s_2 - sd rho_0), sd = rho_1 a_0 . (a_1 x a_2)
+ *                                      omd_i = sum_k ah_k rhod_k + w_pi x om_i + rho_0 rho_1 ah_0 x ah_1 + rho_0 rho_2 ah_0 x ah_2
+ *                                              + rho_1 rho_2 ah_1 x ah_2;   ud_i = 0, o_i and od_i as REVOLUTE
+ *                            FREE      u_i = v_i - v_pi - w_pi x (x_i - x_pi)
+ *                                      omd_i = R_wj s_0..2 + w_pi x om_i    ud_i = R_wj s_3..5 + w_pi x u_i    o_i = x_i, od_i = v_i
+ *                            FIXED     omd_i = w_pi x om_i, ud_i = 0, anchor as REVOLUTE  (om_i is 0 on a rigid state)
+ *                            e_i = ud_i - omd_i x (o_i - o0) - om_i x od_i
+ *                          alpha_b = sum omd_i and a_b = sum e_i + alpha_b x d_b + w_b x v_b, the sums over the joints of b and of
+ *                          its ancestors.  On a rigid state (twists = PD_POSE_BODY_TWIST of its joint rates) this is the exact time
+ *                          derivative of PD_POSE_BODY_TWIST's output along the motion whose slot rates change at s; on any other
+ *                          state it is this formula.  Every lever is a difference about o0.  Mapping, sweeps and the bit guarantees
+ *                          are PD_POSE_BODY_TWIST's.
+ *                          VJP: g_out [n][6] -> g_b [n][19], the raw partials with respect to the whole row (quaternion entries not
+ *                          projected): the ancestor sum again, subtree sums of the accelerations' adjoints, the joint's adjoint, and
+ *                          the parent-side adjoint -- a whole state row, 13 floats: the parent's pose and twist both enter -- gathered
+ *                          in the table's child order.  The table has no gradient: a non-NULL g_a is refused, at every n.
+ * A table of another nb, a parent index or a coordinate range outside the set: as for PD_POSE_BODY_TWIST.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
  * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE,
- * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE and PD_POSE_BODY_TWIST are new op codes of the two entries: no symbol or signature
- * changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14 and 16 are not assigned and are refused as "unknown op" --
- * callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal op took 9, of 10 since the contact state took
- * 11, of 12 since the joint wrench took 13, of 14 since the generalised force took 15, of 16 since the body twist took 17), so the six
- * stay free for as long as the version is 9. */
+ * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE, PD_POSE_BODY_TWIST and PD_POSE_BODY_ACCEL are new op codes of the two entries: no
+ * symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14, 16 and 18 are not assigned and are
+ * refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal op took 9, of 10
+ * since the contact state took 11, of 12 since the joint wrench took 13, of 14 since the generalised force took 15, of 16 since the
+ * body twist took 17, of 18 since the body acceleration took 19), so the seven stay free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
        PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11,
-       PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15, PD_POSE_BODY_TWIST = 17 };
+       PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15, PD_POSE_BODY_TWIST = 17,
+       PD_POSE_BODY_ACCEL = 19 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

@@ -1580,6 +1580,250 @@ __global__ __launch_bounds__(256) void k_body_twist_vjp(int nsets, int nb, const
   for (int k = 0; k < 6; ++k) dst[7 + k] = gr[k];
 }
 
+// ---- PD_POSE_BODY_ACCEL: the accelerations of the bodies of a state -- J qdd + Jdot qd of the articulation -- from rows
+// (p, q xyzw, w, v, s_0..s_5): a state row and the time derivatives of the rate slots of the body's joint, and its vector-Jacobian
+// product with respect to the whole row.  State-based: every velocity-dependent term comes from the row's own twist and its parent's.
+// Per joint i with parent pi (w_pi = v_pi = 0 and a constant frame without one), on jc_joint's frames and jc_compound's angles and axes:
+//   every joint  om_i = w_i - w_pi (jc_joint's w_err);  omd_i = (the joint's term) + w_pi x om_i
+//   REVOLUTE     term (R_wj axis) s_0                       ud_i = 0     anchor o_i = p_wj,  od_i = v_pi + w_pi x (p_wj - x_pi)
+//   COMPOUND     rho = G^-1 m of jc_compound (always the Gram solve);  mode 1: rhod = s_0..2;  mode 0: rhod = G^-1 (s_0 - sd rho_2, s_1,
+//                s_2 - sd rho_0), sd = rho_1 a_0 . (a_1 x a_2);  term sum_k ah_k rhod_k + sum_{k<l} rho_k rho_l ah_k x ah_l, ah_k = R_wj R_off a_k
+//                ud_i = 0, anchor as REVOLUTE
+//   FREE         u_i = v_i - v_pi - w_pi x (x_i - x_pi);  term R_wj s_0..2;  ud_i = R_wj s_3..5 + w_pi x u_i;  o_i = x_i, od_i = v_i
+//   FIXED        no term, anchor as REVOLUTE
+//   e_i = ud_i - omd_i x (o_i - o0) - om_i x od_i
+//   alpha_b = sum omd_i,  a_b = sum e_i + alpha_b x d_b + w_b x v_b,  the sums over b and its ancestors, d_b = x_b - o0
+// Mapping and sweeps are the body twist's: forward one ancestor sum (gf_down); VJP the ancestor sum again (adj d needs alpha_b), subtree
+// sums of (adj E, adj alpha) = (g_a, g_alpha + d x g_a) through gf_up, the joint's adjoint -- the s adjoints are the body twist's
+// projections, the rho adjoints flow into w_i - w_pi through the m_k --, and the parent-side adjoint, now a whole state row (pose AND
+// twist of the parent enter), handed over in an LDS slot of 13 floats as k_joint_coords_vjp does.  No atomics; one writing lane per float.
+enum { BA_ROW = 19 };
+struct BaBody { BodyState s; JcJoint J; v3 d, ro, od, l, com_p, sa, sv; };  // (sa, sv) = s_0..2, s_3..5; ro = o_i - o0; l = p_wj - x_pi (FREE: x_i - x_pi), 0 without a parent
+__device__ __forceinline__ void ba_load(const float *tab, int nb, int body, const float *set_rows, BaBody &B) {
+  const v3 o0 = ld3(set_rows);
+  const float *r = set_rows + (size_t)body * BA_ROW;
+  B.s = load_row<BA_ROW>(set_rows, (size_t)body);
+  B.sa = ld3(r + 13); B.sv = ld3(r + 16);
+  B.J = jc_joint<BA_ROW>(tab, nb, (int)tab[1], (int)tab[2], body, B.s, set_rows);
+  const JcJoint &J = B.J;
+  B.d = (B.s.p - o0) + qrot(B.s.r, J.com);
+  const bool fr = J.type == PD_JOINT_FREE, hp = J.parent >= 0;
+  v3 com_p = V3(0, 0, 0);
+  if (hp) com_p = ld3(tab + JC_HEAD + JC_BODY * J.parent + 18);
+  // (without a parent jc_joint leaves pp = 0, qp = 1, w_p = v_p = 0: the anchor is p_pj - o0 and od vanishes by the same lines)
+  v3 l = fr ? B.d - ((J.pp - o0) + qrot(J.qp, com_p)) : qrot(J.qp, J.p_pj - com_p);
+  if (!hp) l = V3(0, 0, 0);
+  B.com_p = com_p; B.l = l;
+  B.ro = fr ? B.d : (J.pp - o0) + qrot(J.qp, J.p_pj);
+  B.od = fr ? B.s.v : J.v_p + cross(J.w_p, l);
+}
+// omd_i, ud_i and what the adjoint needs of them.  COMPOUND: eps = sum_k a_k rhod_k in the offset frame, ah_k = R_wj R_off a_k (the
+// products ah_k x ah_l are formed from the ROTATED axes, as the definition states them: the raw partials with respect to a quaternion
+// that leaves the unit sphere see the difference to R (a_k x a_l)), t = the right-hand side of the mode-0 Gram solve,
+// sd = d(a_0 . a_2) / dt, trip = a_0 . (a_1 x a_2)
+struct BaJoint { v3 omd, ud, u, eps, ah0, ah1, ah2; JcCompound C; v3 rho, rhod, t; float sd, trip; };
+__device__ __forceinline__ void ba_joint(const BaBody &B, bool generalized, BaJoint &Q) {
+  const JcJoint &J = B.J;
+  const v3 bias = cross(J.w_p, J.w_err);
+  Q.omd = bias; Q.ud = V3(0, 0, 0); Q.u = Q.ud; Q.eps = Q.ud;
+  if (J.type == PD_JOINT_FREE) {
+    Q.u = (B.s.v - J.v_p) - cross(J.w_p, B.l);
+    Q.omd = qrot(J.q_wj, B.sa) + bias;
+    Q.ud = qrot(J.q_wj, B.sv) + cross(J.w_p, Q.u);
+  } else if (J.type == PD_JOINT_REVOLUTE) {
+    Q.omd = qrot(J.q_wj, J.axis) * B.sa.x + bias;
+  } else if (J.type == PD_JOINT_COMPOUND) {
+    JcCompound &C = Q.C;
+    jc_compound(J, false, C);
+    C.id = 1.0f / (1.0f - C.s * C.s);  // rho = G^-1 m in either mode
+    Q.rho = V3((C.m[0] - C.s * C.m[2]) * C.id, C.m[1], (C.m[2] - C.s * C.m[0]) * C.id);
+    Q.rhod = B.sa; Q.t = B.sa;
+    Q.trip = cross(C.a1, C.a2).x; Q.sd = Q.rho.y * Q.trip;
+    if (!generalized) {
+      Q.t.x = B.sa.x - Q.sd * Q.rho.z; Q.t.z = B.sa.z - Q.sd * Q.rho.x;
+      Q.rhod.x = (Q.t.x - C.s * Q.t.z) * C.id; Q.rhod.z = (Q.t.z - C.s * Q.t.x) * C.id;
+    }
+    Q.eps = V3(Q.rhod.x, 0, 0) + C.a1 * Q.rhod.y + C.a2 * Q.rhod.z;
+    Q.ah0 = qrot(C.q_w, V3(1, 0, 0)); Q.ah1 = qrot(C.q_w, C.a1); Q.ah2 = qrot(C.q_w, C.a2);
+    Q.omd = qrot(C.q_w, Q.eps) + bias + cross(Q.ah0, Q.ah1) * (Q.rho.x * Q.rho.y) + cross(Q.ah0, Q.ah2) * (Q.rho.x * Q.rho.z) +
+            cross(Q.ah1, Q.ah2) * (Q.rho.y * Q.rho.z);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_body_accel_fwd(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                        float *__restrict__ out) {
+  __shared__ float down[256 * GF_S];
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *o = out + ((size_t)L.set * nb + L.body) * 6;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
+    if (L.active)
+      for (int k = 0; k < 6; ++k) o[k] = 0.0f;
+    return;
+  }
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  BaBody B;
+  v3 A = V3(0, 0, 0), E = A;
+  if (L.active) {
+    ba_load(tab, nb, L.body, rows + (size_t)L.set * nb * BA_ROW, B);
+    BaJoint Q;
+    ba_joint(B, generalized, Q);
+    A = Q.omd; E = Q.ud - cross(Q.omd, B.ro) - cross(B.J.w_err, B.od);
+  }
+  gf_down(down, T, L, nb, A, E);
+  if (!L.active) return;
+  const v3 a = E + cross(A, B.d) + cross(B.s.w, B.s.v);
+  o[0] = A.x; o[1] = A.y; o[2] = A.z; o[3] = a.x; o[4] = a.y; o[5] = a.z;
+}
+
+// g_b [n][19]: the raw partials of <g_out, out> with respect to (p, q, w, v, s_0..s_5) of every body; a slot past the joint's dofs gets zero.
+__global__ __launch_bounds__(256) void k_body_accel_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                        const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float slot[256 * GF_S], down[256 * GF_S], pslot[256 * PD_ADJ];  // subtree sums / ancestor sums / the parent-side adjoint (odd strides)
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *dst = g_b + ((size_t)L.set * nb + L.body) * BA_ROW;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {
+    if (L.active)
+      for (int k = 0; k < BA_ROW; ++k) dst[k] = 0.0f;
+    return;
+  }
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  BaBody B;
+  BaJoint Q;
+  v3 A = V3(0, 0, 0), E = A;
+  if (L.active) {
+    ba_load(tab, nb, L.body, rows + (size_t)L.set * nb * BA_ROW, B);
+    ba_joint(B, generalized, Q);
+    A = Q.omd; E = Q.ud - cross(Q.omd, B.ro) - cross(B.J.w_err, B.od);
+  }
+  gf_down(down, T, L, nb, A, E);
+  // the body's own share: alpha_b = A, a_b = E + A x d + w x v
+  BodyAdj own = adj_zero(), par = adj_zero();
+  v3 F = V3(0, 0, 0), M = F, adj_d = F;
+  if (L.active) {
+    const float *g = g_out + ((size_t)L.set * nb + L.body) * 6;
+    F = ld3(g + 3); M = ld3(g);
+    adj_cross(A, B.d, M, adj_d, F);
+    adj_cross(B.s.w, B.s.v, own.w, own.v, F);
+  }
+  gf_up(slot, T, L, nb, F, M);  // (adj e_i, adj omd_i before e_i's share) of the joint's subtree
+  float gs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (L.active) {
+    const JcJoint &J = B.J;
+    const bool has_par = J.parent >= 0;
+    // e_i = ud_i - omd_i x ro - om_i x od_i
+    v3 N = M, adj_ro = V3(0, 0, 0), adj_om = adj_ro, adj_od = adj_ro, adj_wp = adj_ro, adj_l = adj_ro;
+    adj_cross(Q.omd, B.ro, N, adj_ro, -F);
+    adj_cross(J.w_err, B.od, adj_om, adj_od, -F);
+    adj_cross(J.w_p, J.w_err, adj_wp, adj_om, N);  // omd_i = term + w_pi x om_i
+    qt adj_q_wj = Q4(0, 0, 0, 0);
+    if (J.type == PD_JOINT_FREE) {
+      const v3 a = qrot_inv(J.q_wj, N), l = qrot_inv(J.q_wj, F);
+      gs[0] = a.x; gs[1] = a.y; gs[2] = a.z; gs[3] = l.x; gs[4] = l.y; gs[5] = l.z;
+      adj_qrot_q(J.q_wj, B.sa, adj_q_wj, N);
+      adj_qrot_q(J.q_wj, B.sv, adj_q_wj, F);
+      v3 adj_u = V3(0, 0, 0);
+      adj_cross(J.w_p, Q.u, adj_wp, adj_u, F);  // ud_i = R_wj s_3..5 + w_pi x u_i
+      own.v += adj_u; par.v -= adj_u;           // u_i = v_i - v_pi - w_pi x l
+      adj_cross(J.w_p, B.l, adj_wp, adj_l, -adj_u);
+      own.v += adj_od;                          // od_i = v_i, ro = d
+      adj_d += adj_ro;
+      if (has_par) {                            // l = d - ((p_pi - o0) + R(q_pi) com_pi)
+        adj_d += adj_l;
+        par.p -= adj_l;
+        adj_qrot_q(J.qp, B.com_p, par.r, -adj_l);
+      }
+    } else {
+      if (has_par) {  // ro = (p_pi - o0) + R(q_pi) p_pj, od_i = v_pi + w_pi x l, l = R(q_pi) (p_pj - com_pi)
+        par.p += adj_ro;
+        adj_qrot_q(J.qp, J.p_pj, par.r, adj_ro);
+        par.v += adj_od;
+        adj_cross(J.w_p, B.l, adj_wp, adj_l, adj_od);
+        adj_qrot_q(J.qp, J.p_pj - B.com_p, par.r, adj_l);
+      }
+      if (J.type == PD_JOINT_REVOLUTE) {
+        gs[0] = dot(qrot(J.q_wj, J.axis), N);
+        adj_qrot_q(J.q_wj, J.axis, adj_q_wj, N * B.sa.x);
+      } else if (J.type == PD_JOINT_COMPOUND) {
+        const JcCompound &K = Q.C;
+        const v3 ae = qrot_inv(K.q_w, N);  // adj eps
+        float grd[3] = {ae.x, dot(K.a1, ae), dot(K.a2, ae)}, g_s = 0.0f;  // adj rhod
+        const float p01 = dot(cross(Q.ah0, Q.ah1), N), p02 = dot(cross(Q.ah0, Q.ah2), N), p12 = dot(cross(Q.ah1, Q.ah2), N);
+        float grho[3] = {Q.rho.y * p01 + Q.rho.z * p02, Q.rho.x * p01 + Q.rho.z * p12, Q.rho.x * p02 + Q.rho.y * p12};
+        v3 adj_a1 = ae * Q.rhod.y, adj_a2 = ae * Q.rhod.z, adj_c12 = V3(0, 0, 0);
+        qt adj_q_w = Q4(0, 0, 0, 0), adj_r_err = adj_q_w;
+        {  // the products of the rotated axes, ah_k = R(q_w) a_k
+          v3 adj_h0 = V3(0, 0, 0), adj_h1 = adj_h0, adj_h2 = adj_h0;
+          adj_cross(Q.ah0, Q.ah1, adj_h0, adj_h1, N * (Q.rho.x * Q.rho.y));
+          adj_cross(Q.ah0, Q.ah2, adj_h0, adj_h2, N * (Q.rho.x * Q.rho.z));
+          adj_cross(Q.ah1, Q.ah2, adj_h1, adj_h2, N * (Q.rho.y * Q.rho.z));
+          adj_qrot_q(K.q_w, V3(1, 0, 0), adj_q_w, adj_h0);
+          adj_qrot(K.q_w, K.a1, adj_q_w, adj_a1, adj_h1);
+          adj_qrot(K.q_w, K.a2, adj_q_w, adj_a2, adj_h2);
+        }
+        gs[0] = grd[0]; gs[1] = grd[1]; gs[2] = grd[2];
+        if (!generalized) {  // rhod_0 = (t_0 - s t_2) id, rhod_2 = (t_2 - s t_0) id; t_0 = s_0 - sd rho_2, t_2 = s_2 - sd rho_0; sd = rho_1 trip
+          g_s = (grd[0] * (2.0f * K.s * Q.rhod.x - Q.t.z) + grd[2] * (2.0f * K.s * Q.rhod.z - Q.t.x)) * K.id;
+          gs[0] = (grd[0] - K.s * grd[2]) * K.id;
+          gs[2] = (grd[2] - K.s * grd[0]) * K.id;
+          const float g_sd = -(gs[0] * Q.rho.z + gs[2] * Q.rho.x);
+          grho[2] -= gs[0] * Q.sd; grho[0] -= gs[2] * Q.sd;
+          grho[1] += g_sd * Q.trip;
+          adj_c12.x += g_sd * Q.rho.y;
+        }
+        adj_cross(K.a1, K.a2, adj_a1, adj_a2, adj_c12);
+        // rho = G^-1 m, m_k = a_k . u, u = R_w^T om_i
+        g_s += (grho[0] * (2.0f * K.s * Q.rho.x - K.m[2]) + grho[2] * (2.0f * K.s * Q.rho.z - K.m[0])) * K.id;
+        const float gm0 = (grho[0] - K.s * grho[2]) * K.id, gm2 = (grho[2] - K.s * grho[0]) * K.id, gm1 = grho[1];
+        const v3 adj_u = V3(gm0, 0, 0) + K.a1 * gm1 + K.a2 * gm2;
+        adj_a1 += K.u * gm1; adj_a2 += K.u * gm2;
+        adj_a2.x += g_s;
+        adj_qrot_q(K.q_w, Q.eps, adj_q_w, N);
+        adj_qrot_inv(K.q_w, J.w_err, adj_q_w, adj_om, adj_u);
+        adj_qmul_a(J.q_off, adj_q_wj, adj_q_w);
+        // the axis chain and the decomposition, as k_body_twist_vjp
+        float adj_ang[3] = {0.f, 0.f, 0.f};
+        qt adj_q10 = Q4(0, 0, 0, 0), adj_q_1 = adj_q10, adj_q_0 = adj_q10;
+        adj_qrot_q(K.q10, V3(0, 0, 1), adj_q10, adj_a2);
+        adj_qmul(K.q_1, K.q_0, adj_q_1, adj_q_0, adj_q10);
+        adj_q_axis_angle(K.a1, K.ang[1], adj_a1, adj_ang[1], adj_q_1);
+        adj_qrot_q(K.q_0, V3(0, 1, 0), adj_q_0, adj_a1);
+        adj_q_axis_angle_ang(V3(1, 0, 0), K.ang[0], adj_ang[0], adj_q_0);
+        qt adj_q_pc = Q4(0, 0, 0, 0), adj_qa = adj_q_pc;
+        quat_decompose_adj(K.q_pc, K.c0, K.c1, K.c2, adj_ang, adj_q_pc);
+        adj_qmul_a(J.q_off, adj_qa, adj_q_pc);
+        adj_qmul_b(qconj(J.q_off), adj_r_err, adj_qa);
+        qt adj_cq = Q4(0, 0, 0, 0);
+        adj_qmul(qconj(J.q_wj), B.s.r, adj_cq, own.r, adj_r_err);  // r_err = conj(q_wj) q_c
+        adj_q_wj += qconj(adj_cq);
+      }
+    }
+    own.w += adj_om;  // om_i = w_i - w_pi
+    if (has_par) {
+      par.w += adj_wp - adj_om;
+      adj_qmul_a(J.q_pj, par.r, adj_q_wj);  // q_wj = q_pi q_pj
+    }
+    own.p += adj_d;  // d = (p_b - o0) + R(q_b) com_b
+    adj_qrot_q(B.s.r, J.com, own.r, adj_d);
+  }
+  adj_store(pslot + threadIdx.x * PD_ADJ, par);
+  __syncthreads();
+  if (!L.active) return;
+  for (int k = 0; k < T.nch; ++k) {
+    const int c = (int)T.ch[k];
+    if (c >= 0 && c < nb) adj_add_from(own, pslot + (L.set_l * nb + c) * PD_ADJ);
+  }
+  float o[PD_ADJ];
+  adj_store(o, own);
+#pragma unroll
+  for (int k = 0; k < PD_ADJ; ++k) dst[k] = o[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) dst[PD_ADJ + k] = gs[k];
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -1603,6 +1847,7 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 //   joint wrench       b / g_b [n][25] = (state, the joint's controls), out / g_out [n][6]; the joint-force table, no g_a
 //   generalized force  b / g_b [n][13] = (pose, wrench), out / g_out [n / nb][nqd]; the joint table, no g_a
 //   body twist         b / g_b [n][13] = (pose, the joint's rates in six slots), out / g_out [n][6]; the joint table, no g_a
+//   body acceleration  b / g_b [n][19] = (state, the derivatives of the joint's rate slots), out / g_out [n][6]; the joint table, no g_a
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
 struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
 constexpr TabledOp TABLED[] = {
@@ -1613,6 +1858,7 @@ constexpr TabledOp TABLED[] = {
     {PD_POSE_JOINT_WRENCH, "PD_POSE_JOINT_WRENCH", "jointforce", JC_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_GENERALIZED_FORCE, "PD_POSE_GENERALIZED_FORCE", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_BODY_TWIST, "PD_POSE_BODY_TWIST", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
+    {PD_POSE_BODY_ACCEL, "PD_POSE_BODY_ACCEL", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
 };
 
 template <class... A>
@@ -1662,6 +1908,10 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
       if (out) hipLaunchKernelGGL(k_body_twist_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_body_twist_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
       break;
+    case PD_POSE_BODY_ACCEL:
+      if (out) hipLaunchKernelGGL(k_body_accel_fwd, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_body_accel_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
     default:
       if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
@@ -1673,7 +1923,7 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
 
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
   if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH &&
-                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST))  // (codes 7, 8, 10, 12, 14 and 16 are not assigned: include/ppr_diffphys.h)
+                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST && op != PD_POSE_BODY_ACCEL))  // (codes 7, 8, 10, 12, 14, 16 and 18 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
     if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);

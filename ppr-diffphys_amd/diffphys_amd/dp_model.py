@@ -317,6 +317,42 @@ class BodyTwists(torch.autograd.Function):
                 g_r[:, 7:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None, None, None)
 
 
+class BodyAccelerations(torch.autograd.Function):
+    """body_q (..., nb, 7), body_qd (..., nb, 6) twists (w, v of the centre of mass), acc6 (..., nb, 6) = the time derivatives of the
+    rates of each body's joint in six slots (``hip_backend.joint_rate_slot_index``; a slot no dof uses may hold anything and gets a zero
+    gradient), env, rates -> (..., nb, 6) = (alpha, a) per body in world axes, a of the body's centre of mass: J qdd + Jdot qd of the
+    articulation on that state (``pd_pose_op`` PD_POSE_BODY_ACCEL on the env's joint table, one launch forward and one for the
+    vector-Jacobian product).  rates="generalized" or "measured": the COMPOUND convention the slots are read in, that of
+    ``joint_coords``.  Gathering the slots from the joint_qd layout is the caller's (``dp_utils.body_accelerations`` does it).  float32
+    GPU tensors, or an error: no CPU fallback.  The gradients are the raw partials (quaternion entries not projected)."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_qd, acc6, env, rates="generalized"):
+        nb = int(env.nb)
+        _need_gpu("BodyAccelerations", body_q, body_qd, acc6)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_qd.shape) == lead + (nb, 6)
+                and tuple(acc6.shape) == lead + (nb, 6)):
+            raise ValueError("BodyAccelerations: body_q (..., %d, 7), body_qd and acc6 (..., %d, 6) with equal leading shapes; got %s, %s and %s" % (
+                nb, nb, tuple(body_q.shape), tuple(body_qd.shape), tuple(acc6.shape)))
+        table = hip_backend.env_joint_table(env, body_q.device, rates)
+        rows = torch.cat([t.detach().reshape(-1, w) for t, w in ((body_q, 7), (body_qd, 6), (acc6, 6))], dim=1)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows)
+        return hip_backend.body_accelerations(table, nb, rows).view(lead + (nb, 6))
+
+    @staticmethod
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None, None
+        lead, nb = ctx.lead, ctx.nb
+        g_r = hip_backend.body_accelerations_vjp(ctx.table, nb, rows, g.to(torch.float32).reshape(-1, 6).contiguous())
+        return (g_r[:, :7].reshape(lead + (nb, 7)) if ctx.needs_input_grad[0] else None,
+                g_r[:, 7:13].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None,
+                g_r[:, 13:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[2] else None, None, None)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

@@ -511,12 +511,19 @@ def body_twists(body_q, joint_qd, env, rates="generalized"):
     if not ok:
         raise ValueError("body_twists: joint_qd must broadcast to %s; got %s" % (lead + (nqd,), tuple(joint_qd.shape)))
     hip_backend._jc_rate_mode(rates)
-    # slot k of body b <- dof qd_start[b] + k, or the appended zero column
-    t = joint_qd.expand(joint_qd.shape[:-1] + (nqd,))
+    return BodyTwists.apply(body_q, _rate_slots(joint_qd, lead, env, body_q.device), env, rates)
+
+
+def _rate_slots(t, lead, env, device):
+    """(..., nqd) in the joint_qd layout, broadcastable to lead + (nqd,) -> lead + (nb, 6): slot k of body b <- dof qd_start[b] + k, or
+    the appended zero column.  Plain torch indexing, so autograd sums the gradient of a shared entry."""
+    from . import hip_backend
+
+    nb, nqd = int(env.nb), int(env.template()["nqd"])
+    t = t.expand(t.shape[:-1] + (nqd,))
     t = torch.cat([t, t.new_zeros(t.shape[:-1] + (1,))], dim=-1)
-    idx = hip_backend.env_joint_rate_slot_index(env, body_q.device)
-    rates6 = t.index_select(-1, idx).reshape(t.shape[:-1] + (nb, 6)).expand(lead + (nb, 6))
-    return BodyTwists.apply(body_q, rates6, env, rates)
+    idx = hip_backend.env_joint_rate_slot_index(env, device)
+    return t.index_select(-1, idx).reshape(t.shape[:-1] + (nb, 6)).expand(lead + (nb, 6))
 
 
 def jacobian(body_q, env, rates="generalized"):
@@ -588,6 +595,100 @@ def rigid_twists(body_q, body_qd, env):
         lin = [_q_rot(quats[k].expand(body_qd.shape[:-2] + (4,)), body_qd[..., b, 3:], inverse=True) for k, (b, _, _) in enumerate(free)]
         jqd = jqd.index_copy(-1, idx, torch.cat(lin, dim=-1))
     return body_twists(body_q, jqd, env, "generalized")
+
+
+EFFORTS_OF = {"generalized": "generalized", "measured": "actuator"}   # rate convention -> the conjugate efforts of generalized_force
+
+
+def body_accelerations(body_q, body_qd, joint_qdd, env, rates="generalized"):
+    """The accelerations of the bodies of a state -- J qdd + Jdot qd of the articulation, the second-order term next to ``body_twists``:
+    body_q (..., nb, 7) poses, body_qd (..., nb, 6) twists (w, v of the centre of mass; a rollout's states as they are, or
+    ``body_twists`` of joint rates) and joint_qdd broadcastable to (..., nqd), the time derivatives of the joint rates in the joint_qd
+    layout -> (..., nb, 6) = (alpha, a) in world axes, a the acceleration of the body's centre of mass.  joint_qdd=None means zeros:
+    the bias acceleration Jdot qd.  Every velocity-dependent term comes from the twists themselves (a body's and its parent's): no joint
+    rates are passed, and on a state whose twists are not rigid the result is the op's formula (include/ppr_diffphys.h), not a time
+    derivative of anything.  rates: the convention joint_qdd's COMPOUND entries are read in, as for ``body_twists``.  A FREE joint's six
+    entries are the derivatives of ``body_twists``' FREE slots.  One HIP launch (``dp_model.BodyAccelerations``), differentiable in all
+    three tensors (raw partials; quaternions are taken as they are).  joint_qdd is gathered into the op's per-body slots HERE, outside
+    the Function, so autograd sums the gradient of a shared entry.  float32 GPU tensors only."""
+    from . import hip_backend
+    from .dp_model import BodyAccelerations
+
+    _need_gpu("body_accelerations", body_q, body_qd, *(() if joint_qdd is None else (joint_qdd,)))
+    nb, nqd = int(env.nb), int(env.template()["nqd"])
+    lead = _check_states("body_accelerations", body_q, body_qd, nb)
+    if joint_qdd is None:
+        acc6 = body_q.new_zeros(lead + (nb, 6))
+    else:
+        try:
+            ok = joint_qdd.dim() >= 1 and tuple(torch.broadcast_shapes(tuple(joint_qdd.shape), lead + (nqd,))) == lead + (nqd,)
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError("body_accelerations: joint_qdd must broadcast to %s; got %s" % (lead + (nqd,), tuple(joint_qdd.shape)))
+    hip_backend._jc_rate_mode(rates)
+    if joint_qdd is not None:
+        acc6 = _rate_slots(joint_qdd, lead, env, body_q.device)
+    return BodyAccelerations.apply(body_q, body_qd, acc6, env, rates)
+
+
+def newton_euler_wrench(body_q, body_qd, body_acc, body_mass, body_inertia, env):
+    """The total body_f (..., nb, 6) = (torque, force) that gives the bodies of a state the accelerations body_acc (..., nb, 6) =
+    (alpha, a of the centre of mass) -- Newton and Euler per body:
+        t = R (I R^T alpha + R^T w x I R^T w),   R = R(q)          f = m (a - gravity [m != 0])
+    The continuous counterpart of ``inertial_wrench`` (which solves the rollouts' discrete step, with its (1 - 0.1 dt) angular damping,
+    for the force): no time step and no damping here.  body_mass broadcastable to (..., nb), body_inertia (body frame, about the centre
+    of mass) to (..., nb, 3, 3); gravity is the env's; a body without mass gets force 0.  Plain torch on the tensors' device and
+    dtype, differentiable by autograd in every tensor argument."""
+    nb = int(env.nb)
+    _check_states("newton_euler_wrench", body_q, body_qd, nb)
+    _check_states("newton_euler_wrench", body_q, body_acc, nb)
+    gravity = torch.as_tensor([float(g) for g in env.template()["gravity"]], dtype=body_q.dtype, device=body_q.device)
+    r0 = body_q[..., 3:]
+    mass = torch.as_tensor(body_mass, dtype=body_q.dtype, device=body_q.device)[..., None]
+    inertia = torch.as_tensor(body_inertia, dtype=body_q.dtype, device=body_q.device)
+    f = mass * (body_acc[..., 3:] - gravity * (mass != 0).to(body_q.dtype))
+    wb = _q_rot(r0, body_qd[..., :3], inverse=True)
+    ab = _q_rot(r0, body_acc[..., :3], inverse=True)
+    Iwb = (inertia @ wb[..., None])[..., 0]
+    Iab = (inertia @ ab[..., None])[..., 0]
+    t = _q_rot(r0, Iab + torch.cross(wb, Iwb, dim=-1))
+    return torch.cat([t, f.expand(t.shape)], -1)
+
+
+def rnea(body_q, joint_qd, joint_qdd, body_mass, body_inertia, env, external=None, rates="generalized"):
+    """Inverse dynamics of a joint-space trajectory point (q as poses, qd, qdd) -- the recursive Newton-Euler algorithm on the state ops:
+    ``body_twists(body_q, joint_qd)``, ``body_accelerations`` of those twists and joint_qdd, ``newton_euler_wrench`` - ``external``, and
+    ``generalized_force`` with the efforts conjugate to ``rates`` (generalized <-> generalized, measured <-> actuator) -> (..., nqd) =
+    H qdd + C(q, qd) qd + g - J^T external.  joint_qd and joint_qdd broadcastable to (..., nqd); joint_qdd=None means zeros.
+    ``external`` (..., nb, 6): the wrenches something other than the joints supplies, as for ``inverse_dynamics``, whose SIGN convention
+    this keeps: the entries are what the bodies RECEIVE, read in joint space.  Three HIP launches forward and three for the gradient;
+    differentiable in every tensor argument.  float32 GPU tensors only."""
+    from . import hip_backend
+
+    hip_backend._jc_rate_mode(rates)
+    tw = body_twists(body_q, joint_qd, env, rates)
+    acc = body_accelerations(body_q, tw, joint_qdd, env, rates)
+    need = newton_euler_wrench(body_q, tw, acc, body_mass, body_inertia, env)
+    if external is not None:
+        need = need - external
+    return generalized_force(body_q, need.contiguous(), env, EFFORTS_OF[rates])
+
+
+def bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external=None, rates="generalized"):
+    """C(q, qd) qd + g - J^T external: ``rnea`` with joint_qdd=None -> (..., nqd)."""
+    return rnea(body_q, joint_qd, None, body_mass, body_inertia, env, external, rates)
+
+
+def forward_dynamics(body_q, joint_qd, tau, body_mass, body_inertia, env, external=None):
+    """The joint accelerations the joint-space forces tau (..., nqd) produce, in ``rnea``'s sign convention and the generalized rates:
+    solve(``mass_matrix``, tau - ``bias_forces``) -> (..., nqd), so ``forward_dynamics(rnea(qdd)) = qdd``.  Plain torch (a dense solve)
+    on ``mass_matrix`` -- S * nqd * nb rows through ``body_twists`` -- and ``bias_forces``: like ``mass_matrix`` it is meant for a few
+    state sets, not for a batch of thousands, and it is not an articulated-body kernel.  Differentiable in every tensor argument.
+    float32 GPU tensors only."""
+    H = mass_matrix(body_q, body_mass, body_inertia, env)
+    rhs = tau - bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external, "generalized")
+    return torch.linalg.solve(H, rhs[..., None])[..., 0]
 
 
 def compute_com(body_q, part_com, part_mass):

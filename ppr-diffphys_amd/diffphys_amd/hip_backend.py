@@ -729,7 +729,7 @@ def pose_op_vjp(op, a, b, g_out, need_a=True, need_b=True):
 
 # ---- The tabled state ops (ground wrench, joint coordinates, centroidal, contact state, joint wrench): each takes a device table compiled from a template.  They share
 # one tag on the table tensor, one per-model cache, one argument check and one gradient check; what differs is passed in.
-_ROWS = {13: ("state", "(p, q xyzw, w, v)"), 23: ("rows", "(p, q xyzw, w, v, m, I row-major)"),
+_ROWS = {13: ("state", "(p, q xyzw, w, v)"), 19: ("rows", "(p, q xyzw, w, v, s[6])"), 23: ("rows", "(p, q xyzw, w, v, m, I row-major)"),
          25: ("rows", "(p, q xyzw, w, v, act[3], target[3], ke[3], kd[3])")}   # operand row width -> its name, its columns
 
 
@@ -760,7 +760,7 @@ def _env_table(env, key, build):
 
 
 def _state_op_check(op, kind, width, table, nb, rows, bare=False, name=None, columns=None):
-    """The argument check of the fourteen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    """The argument check of the sixteen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
@@ -1250,6 +1250,33 @@ def body_twists_vjp(table, nb, rows, g_out):
     _grad_check("body_twists_vjp", "g_out", g_out, n, 6)
     g_b = torch.empty(n, 13, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op_vjp(POSE_BODY_TWIST, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", n * 6),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
+
+
+POSE_BODY_ACCEL = 19   # (code 18 is not assigned either: include/ppr_diffphys.h)
+
+
+def body_accelerations(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_BODY_ACCEL: rows [n, 19] = (p, q xyzw, w, v, s[6]) per body -- a state row and the time derivatives of the
+    rates of that body's joint in six slots (``joint_rate_slot_index``) --, n a multiple of nb (row i is body i % nb of set i // nb), and
+    the joint table of ``joint_coords`` -> [n, 6] = (alpha, a) per body, world axes, a of the body's centre of mass: J qdd + Jdot qd of
+    the articulation, every velocity-dependent term taken from the rows' own twists.  The table's mode says in which convention the
+    COMPOUND slots are read: "measured" or "generalized".  Fixed summation order: a set's bits depend neither on the call nor on the
+    other sets."""
+    n, _ = _state_op_check("body_accelerations", "joint", 19, table, int(nb), rows)
+    out = torch.empty(n, 6, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_BODY_ACCEL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def body_accelerations_vjp(table, nb, rows, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_BODY_ACCEL: g_out [n, 6] -> g_rows [n, 19], the raw partials with respect to the whole row (quaternion
+    entries not projected; zero in a slot no dof uses)."""
+    n, _ = _state_op_check("body_accelerations_vjp", "joint", 19, table, int(nb), rows)
+    _grad_check("body_accelerations_vjp", "g_out", g_out, n, 6)
+    g_b = torch.empty(n, 19, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_BODY_ACCEL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", n * 6),
                                 None, _ptr(g_b, "g_b"), _stream()))
     return g_b
 
