@@ -572,17 +572,49 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  *                          in the table's child order.  The table has no gradient: a non-NULL g_a is refused, at every n.
  * A table of another nb, a parent index or a coordinate range outside the set: as for PD_POSE_BODY_TWIST.
  *
+ * The inverse of the mass matrix of a state, applied to a joint-space vector -- the articulated-body recursion:
+ *   PD_POSE_MASS_INVERSE   b = rows [n][23] = (p, q xyzw, m, I row-major 3x3, r_0..r_5): the body's pose, its mass, its body-frame
+ *                          inertia about the centre of mass (as in PD_POSE_CENTROIDAL's rows; its symmetric part enters) and the
+ *                          joint-space force entries of THIS body's joint in PD_POSE_BODY_TWIST's slot layout -- the efforts
+ *                          conjugate to the table's rate mode; a further slot never enters arithmetic.  a_broadcast = nb (at most 256)
+ *                          and a = ONE joint table of PD_POSE_JOINT_COORDS as above, its mode float [3] included -> out [n][6] =
+ *                          the solution x in the same slots, 0 in a slot no dof uses:
+ *                            J = PD_POSE_BODY_TWIST's Jacobian in the table's mode,  M_b = diag(R_b I_b R_b^T, m_b 1),
+ *                            H = sum_b J_b^T M_b J_b,   out = H^-1 r   per state set.
+ *                          In mode 1 (generalized) H is the mass matrix of the generalised rates; in mode 0 (measured) the COMPOUND
+ *                          columns are Ah G^-1, exactly as PD_POSE_BODY_TWIST reads its rates.  Recursion, in world axes about o0 = the
+ *                          origin of the set's body 0, spatial vectors (angular, linear at o0), d_b = x_b - o0, r_i = the joint's
+ *                          anchor - o0:  spatial inertia [[Ibar - m [d]x[d]x, m [d]x], [-m [d]x, m 1]], Ibar = R sym(I) R^T;  motion
+ *                          subspace S_i = REVOLUTE (ah, -ah x r_i), COMPOUND three such columns, FREE (R_wj e_k, -R_wj e_k x d_b) and
+ *                          (0, R_wj e_k), FIXED none.  Up, deepest level first: IA = I_b + sum Ia_c, pA = sum pa_c, U = IA S,
+ *                          D = S^T U = L diag(dd) L^T, W = L^-1 U^T, z = L^-1 (r_b - S^T pA); the body hands up
+ *                          Ia = IA - W^T dd^-1 W (exactly 0 behind a 6-dof joint) and pa = pA + W^T dd^-1 z; a body without a dof
+ *                          hands IA, pA up unchanged.  Down, from the roots: x_b = L^-T dd^-1 (z - W a_pi), a_b = a_pi + S x_b.
+ *                          D is factored, never inverted.  A pivot that is not positive (a massless body on a joint with dofs: a
+ *                          singular H) gives inf / NaN; a massless body on a FIXED joint is fine.  O(nb) per set, one launch, no
+ *                          atomics: a set's bits depend neither on the run nor on n nor on its place in the launch.
+ *                          GRADIENT: there is no VJP kernel.  pd_pose_op_vjp refuses this code at every n, after the shared checks
+ *                          (n % g, the cap, g_a), and says so in pd_last_error; nothing is launched or written.  H is symmetric, so the
+ *                          op is self-adjoint in its slots and the caller composes the gradient: with lam = pd_pose_op(21) of
+ *                          g_out in place of r, the gradient in r is lam, and the gradient in poses, masses and inertias is that of
+ *                            - sum_b tlam_b . M_b(q_b, m_b, I_b) . tx_b,   tx = PD_POSE_BODY_TWIST(pose, x),  tlam = PD_POSE_BODY_TWIST(pose, lam)
+ *                          in the table's mode with x and lam held constant: one more launch of this op, one PD_POSE_BODY_TWIST on
+ *                          the 2 S stacked sets, its VJP, and M_b's own partials (dp_model.MassInverse does exactly that).
+ * A table of another nb: out is written as zeros, no row of the table is read.  A parent index or a coordinate range outside the set:
+ * as for PD_POSE_BODY_TWIST -- a malformed table never indexes outside the set.
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
  * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE,
- * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE, PD_POSE_BODY_TWIST and PD_POSE_BODY_ACCEL are new op codes of the two entries: no
- * symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14, 16 and 18 are not assigned and are
- * refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal op took 9, of 10
- * since the contact state took 11, of 12 since the joint wrench took 13, of 14 since the generalised force took 15, of 16 since the
- * body twist took 17, of 18 since the body acceleration took 19), so the seven stay free for as long as the version is 9. */
+ * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE, PD_POSE_BODY_TWIST, PD_POSE_BODY_ACCEL and PD_POSE_MASS_INVERSE are new op codes of
+ * the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14, 16, 18 and 20 are
+ * not assigned and are refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal
+ * op took 9, of 10 since the contact state took 11, of 12 since the joint wrench took 13, of 14 since the generalised force took 15,
+ * of 16 since the body twist took 17, of 18 since the body acceleration took 19, of 20 since the mass inverse took 21), so the eight
+ * stay free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
        PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11,
        PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15, PD_POSE_BODY_TWIST = 17,
-       PD_POSE_BODY_ACCEL = 19 };
+       PD_POSE_BODY_ACCEL = 19, PD_POSE_MASS_INVERSE = 21 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

@@ -1824,6 +1824,256 @@ __global__ __launch_bounds__(256) void k_body_accel_vjp(int nsets, int nb, const
   for (int k = 0; k < 6; ++k) dst[PD_ADJ + k] = gs[k];
 }
 
+// ---- PD_POSE_MASS_INVERSE: H^-1 applied to a joint-space vector, H = sum_b J_b^T diag(R_b I_b R_b^T, m_b) J_b the mass matrix of the
+// articulation (J = PD_POSE_BODY_TWIST's Jacobian in the table's mode), by the articulated-body recursion, from rows
+// (p, q xyzw, m, I row-major, r_0..r_5): the pose, the body's mass and body-frame inertia about its centre of mass (its symmetric part
+// enters) and the joint-space force entries of the body's joint in the body twist's slot layout -> the solution in the same slots.
+// Everything in world axes about o0 = the origin of the set's body 0, spatial vectors (angular, linear at o0): children's quantities add
+// without a transform, like gf_up's (F, M).  Per body, d = x_b - o0, Ibar = R sym(I) R^T, r_i = the joint's anchor - o0 as gf_load forms it:
+//   spatial inertia  [[Ibar - m [d]x[d]x, m [d]x], [-m [d]x, m 1]]   (symmetric: 21 floats, mi_ix)
+//   motion subspace  REVOLUTE (ah, -ah x r_i);  COMPOUND three such columns from Ah = R_wj R_off (a_0 a_1 a_2) (mode 1) or Ah G^-1 (mode 0,
+//                    as bt_joint reads its rates);  FREE (R_wj e_k, -R_wj e_k x d_b) and (0, R_wj e_k);  FIXED none
+// Up, deepest level first:  IA = I_b + sum Ia_c, pA = sum pa_c (the table's child order), U = IA S, D = S^T U = L diag(dd) L^T,
+//   W = L^-1 U^T, z = L^-1 (r_b - S^T pA);  the body hands up Ia = IA - W^T dd^-1 W and pa = pA + W^T dd^-1 z through an LDS slot of 27
+//   floats (odd stride: distinct banks); behind a 6-dof joint Ia is exactly 0, not the rounding residue; a body without a dof hands
+//   IA, pA up unchanged.  Down, from the roots:  x_b = L^-T dd^-1 (z - W a_pi),  a_b = a_pi + S x_b, six floats per body.
+// D (1x1, 3x3, 6x6) is never inverted: the LDL^T factor is applied by substitution (the explicit inverse loses 6e-3 of max |x| on the
+// human in fp32).  A pivot that is not positive gives inf / NaN, as a singular H does in a dense solve; not guarded.
+// Precision: rows, frames, motion subspaces, the 27 + 6 floats handed over and the kept factor are fp32; the body's own spatial inertia,
+// the sums over children, the factor and the substitutions are evaluated in double (an fp32 recursion is 1e-5 .. 4e-5 off on the human,
+// almost all of it from the recursion's own roundings; this form 2e-6: DESIGN.md section 8).
+// The factor of every joint size is the same unrolled template: every array index is a constant, nothing is indexed by the dof count.
+// Mapping: a lane per body, whole state sets per workgroup (set_lane), depths from gf_tree; every barrier in workgroup-uniform control
+// flow (trip counts are table data); no atomics, one writing lane per float.  A table of another nb: zeros, no row of it is read.
+// The op is self-adjoint in its slots (H is symmetric); its gradient is composed on the host side (include/ppr_diffphys.h): no VJP kernel.
+enum { MI_ROW = 23, MI_S = 27 };
+__device__ __forceinline__ constexpr int mi_ix(int i, int j) {  // the upper triangle of a symmetric 6 x 6, row by row
+  return i <= j ? i * 6 - i * (i - 1) / 2 + (j - i) : j * 6 - j * (j - 1) / 2 + (i - j);
+}
+__device__ __forceinline__ constexpr int mi_lx(int i, int j) { return i * (i - 1) / 2 + j; }  // the strict lower triangle, j < i
+struct MiJoint { float S[36], W[36], L[15], di[6], z[6]; };  // column k of S and row k of W at [6 k ..]; di = 1 / the pivots dd
+__device__ __forceinline__ void mi_col(float *c, v3 w, v3 l) { c[0] = w.x; c[1] = w.y; c[2] = w.z; c[3] = l.x; c[4] = l.y; c[5] = l.z; }
+// The joint's factor from (IA, pA) and its force entries r; (IA, pA) leave as what the body hands up.  The arithmetic is double, what is
+// kept (Q) and handed over is float: H of a long or branched chain is ill-conditioned (human: 4e4), and the roundings of an fp32
+// recursion -- not those of its fp32 inputs -- are what the solution loses digits to (measured: DESIGN.md section 8).
+template <int K>
+__device__ __forceinline__ void mi_factor(double *IA, double *pA, const float *r, MiJoint &Q) {
+  double W[6 * K], L[K * (K - 1) / 2 + 1], dd[K], di[K], z[K];  // W starts as U = IA S and is reduced in place
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double t = IA[mi_ix(i, 0)] * (double)Q.S[6 * k];
+#pragma unroll
+      for (int j = 1; j < 6; ++j) t += IA[mi_ix(i, j)] * (double)Q.S[6 * k + j];
+      W[6 * k + i] = t;
+    }
+#pragma unroll
+  for (int j = 0; j < K; ++j) {  // D(i, j) = S_i . U_j, formed where it is used (U_j is still whole: rows are reduced below)
+    double t = 0.0;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) t += (double)Q.S[6 * j + e] * W[6 * j + e];
+#pragma unroll
+    for (int p = 0; p < j; ++p) t -= L[mi_lx(j, p)] * L[mi_lx(j, p)] * dd[p];
+    dd[j] = t;
+    di[j] = 1.0 / t;
+#pragma unroll
+    for (int i = j + 1; i < K; ++i) {
+      double u = 0.0;
+#pragma unroll
+      for (int e = 0; e < 6; ++e) u += (double)Q.S[6 * i + e] * W[6 * j + e];
+#pragma unroll
+      for (int p = 0; p < j; ++p) u -= L[mi_lx(i, p)] * L[mi_lx(j, p)] * dd[p];
+      L[mi_lx(i, j)] = u * di[j];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double zk = (double)r[k];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) zk -= (double)Q.S[6 * k + e] * pA[e];
+#pragma unroll
+    for (int p = 0; p < k; ++p) zk -= L[mi_lx(k, p)] * z[p];
+    z[k] = zk;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double w = W[6 * k + i];
+#pragma unroll
+      for (int p = 0; p < k; ++p) w -= L[mi_lx(k, p)] * W[6 * p + i];
+      W[6 * k + i] = w;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double zd = z[k] * di[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      pA[i] += W[6 * k + i] * zd;
+      const double wd = W[6 * k + i] * di[k];
+#pragma unroll
+      for (int j = i; j < 6; ++j) IA[mi_ix(i, j)] -= wd * W[6 * k + j];
+    }
+  }
+  if constexpr (K == 6) {
+#pragma unroll
+    for (int e = 0; e < 21; ++e) IA[e] = 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    Q.di[k] = (float)di[k]; Q.z[k] = (float)z[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Q.W[6 * k + i] = (float)W[6 * k + i];
+#pragma unroll
+    for (int p = 0; p < k; ++p) Q.L[mi_lx(k, p)] = (float)L[mi_lx(k, p)];
+  }
+}
+// a: the parent's acceleration in, the body's out; x: the joint's solution.  Double arithmetic on the kept floats.
+template <int K>
+__device__ __forceinline__ void mi_solve(const MiJoint &Q, double *a, double *x) {
+#pragma unroll
+  for (int k = K - 1; k >= 0; --k) {
+    double t = (double)Q.z[k];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) t -= (double)Q.W[6 * k + e] * a[e];
+    x[k] = t * (double)Q.di[k];
+  }
+#pragma unroll
+  for (int k = K - 1; k >= 0; --k)
+#pragma unroll
+    for (int i = k + 1; i < K; ++i) x[k] -= (double)Q.L[mi_lx(i, k)] * x[i];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) a[i] += (double)Q.S[6 * k + i] * x[k];
+}
+
+__global__ __launch_bounds__(256) void k_mass_inverse(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                      float *__restrict__ out) {
+  __shared__ float slot[256 * MI_S], down[256 * GF_S];  // what a body hands up: Ia (21), pa (6) / its acceleration (6)
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *o = out + ((size_t)L.set * nb + L.body) * 6;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
+    if (L.active)
+      for (int k = 0; k < 6; ++k) o[k] = 0.0f;
+    return;
+  }
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  MiJoint Q;
+  double IA[21], pA[6];
+  float r[6];
+  int type = PD_JOINT_FIXED;
+#pragma unroll
+  for (int e = 0; e < 21; ++e) IA[e] = 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) { pA[e] = 0.0; r[e] = 0.0f; }
+  if (L.active) {
+    const float *set_rows = rows + (size_t)L.set * nb * MI_ROW, *row = set_rows + (size_t)L.body * MI_ROW;
+    const v3 o0 = ld3(set_rows);
+    BodyState s;
+    s.p = ld3(row); s.r = ld4(row + 3); s.w = V3(0, 0, 0); s.v = s.w;
+    const JcJoint J = jc_joint<MI_ROW>(tab, nb, (int)tab[1], (int)tab[2], L.body, s, set_rows);
+    type = J.type;
+    const v3 d = (s.p - o0) + qrot(s.r, J.com);
+    const v3 ra = type == PD_JOINT_FREE ? d : J.parent >= 0 ? (J.pp - o0) + qrot(J.qp, J.p_pj) : J.p_pj - o0;
+    // the body's own spatial inertia in double from the fp32 row (rotm's polynomial, as qrot's): the shift to o0 adds m |d|^2 to an
+    // inertia that may be 1e-4 of it
+    const double m = (double)row[7], qx = s.r.x, qy = s.r.y, qz = s.r.z, qw = s.r.w, sq = 2.0 * qw * qw - 1.0;
+    const double R[9] = {sq + 2.0 * qx * qx, 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy),
+                         2.0 * (qx * qy + qw * qz), sq + 2.0 * qy * qy, 2.0 * (qy * qz - qw * qx),
+                         2.0 * (qx * qz - qw * qy), 2.0 * (qy * qz + qw * qx), sq + 2.0 * qz * qz};
+    double Is[9], RI[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Is[3 * i + j] = 0.5 * ((double)row[8 + 3 * i + j] + (double)row[8 + 3 * j + i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) RI[3 * i + j] = R[3 * i] * Is[j] + R[3 * i + 1] * Is[3 + j] + R[3 * i + 2] * Is[6 + j];
+    const double dv[3] = {d.x, d.y, d.z}, d2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = i; j < 3; ++j)
+        IA[mi_ix(i, j)] = (RI[3 * i] * R[3 * j] + RI[3 * i + 1] * R[3 * j + 1] + RI[3 * i + 2] * R[3 * j + 2]) +
+                          m * ((i == j ? d2 : 0.0) - dv[i] * dv[j]);
+    IA[mi_ix(0, 4)] = -m * dv[2]; IA[mi_ix(0, 5)] = m * dv[1];  // m [d]x
+    IA[mi_ix(1, 3)] = m * dv[2]; IA[mi_ix(1, 5)] = -m * dv[0];
+    IA[mi_ix(2, 3)] = -m * dv[1]; IA[mi_ix(2, 4)] = m * dv[0];
+    IA[mi_ix(3, 3)] = m; IA[mi_ix(4, 4)] = m; IA[mi_ix(5, 5)] = m;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r[k] = row[17 + k];
+    if (type == PD_JOINT_FREE) {
+      const v3 e0 = qrot(J.q_wj, V3(1, 0, 0)), e1 = qrot(J.q_wj, V3(0, 1, 0)), e2 = qrot(J.q_wj, V3(0, 0, 1)), zero = V3(0, 0, 0);
+      mi_col(Q.S, e0, -cross(e0, ra)); mi_col(Q.S + 6, e1, -cross(e1, ra)); mi_col(Q.S + 12, e2, -cross(e2, ra));
+      mi_col(Q.S + 18, zero, e0); mi_col(Q.S + 24, zero, e1); mi_col(Q.S + 30, zero, e2);
+    } else if (type == PD_JOINT_REVOLUTE) {
+      const v3 ah = qrot(J.q_wj, J.axis);
+      mi_col(Q.S, ah, -cross(ah, ra));
+    } else if (type == PD_JOINT_COMPOUND) {
+      JcCompound C;
+      jc_compound(J, false, C);
+      v3 c0 = V3(1, 0, 0), c2 = C.a2;
+      if (!generalized) {  // the columns of A G^-1
+        const float id = 1.0f / (1.0f - C.s * C.s);
+        c0 = (V3(1, 0, 0) - C.a2 * C.s) * id; c2 = (C.a2 - V3(C.s, 0, 0)) * id;
+      }
+      const v3 h0 = qrot(C.q_w, c0), h1 = qrot(C.q_w, C.a1), h2 = qrot(C.q_w, c2);
+      mi_col(Q.S, h0, -cross(h0, ra)); mi_col(Q.S + 6, h1, -cross(h1, ra)); mi_col(Q.S + 12, h2, -cross(h2, ra));
+    }
+  }
+  float *mine = slot + threadIdx.x * MI_S, *dn = down + threadIdx.x * GF_S;
+#pragma unroll
+  for (int e = 0; e < MI_S; ++e) mine[e] = 0.0f;  // (a malformed table may name a child that publishes later: it reads zeros)
+#pragma unroll
+  for (int e = 0; e < 6; ++e) dn[e] = 0.0f;
+  for (int lev = T.maxd; lev >= 0; --lev) {
+    __syncthreads();
+    if (L.active && T.dep == lev) {
+      for (int k = 0; k < T.nch; ++k) {
+        const int c = (int)T.ch[k];
+        if (c >= 0 && c < nb) {
+          const float *cs = slot + (L.set_l * nb + c) * MI_S;
+#pragma unroll
+          for (int e = 0; e < 21; ++e) IA[e] += (double)cs[e];
+#pragma unroll
+          for (int e = 0; e < 6; ++e) pA[e] += (double)cs[21 + e];
+        }
+      }
+      if (type == PD_JOINT_FREE) mi_factor<6>(IA, pA, r, Q);
+      else if (type == PD_JOINT_COMPOUND) mi_factor<3>(IA, pA, r, Q);
+      else if (type == PD_JOINT_REVOLUTE) mi_factor<1>(IA, pA, r, Q);
+#pragma unroll
+      for (int e = 0; e < 21; ++e) mine[e] = (float)IA[e];
+#pragma unroll
+      for (int e = 0; e < 6; ++e) mine[21 + e] = (float)pA[e];
+    }
+  }
+  double a[6], x[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) { a[e] = 0.0; x[e] = 0.0; }
+  for (int lev = 0; lev <= T.maxd; ++lev) {
+    __syncthreads();
+    if (L.active && T.dep == lev) {
+      if (T.parent >= 0) {
+        const float *pp = down + (L.set_l * nb + T.parent) * GF_S;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) a[e] = (double)pp[e];
+      }
+      if (type == PD_JOINT_FREE) mi_solve<6>(Q, a, x);
+      else if (type == PD_JOINT_COMPOUND) mi_solve<3>(Q, a, x);
+      else if (type == PD_JOINT_REVOLUTE) mi_solve<1>(Q, a, x);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) dn[e] = (float)a[e];
+    }
+  }
+  if (!L.active) return;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[k] = (float)x[k];
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -1848,8 +2098,10 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 //   generalized force  b / g_b [n][13] = (pose, wrench), out / g_out [n / nb][nqd]; the joint table, no g_a
 //   body twist         b / g_b [n][13] = (pose, the joint's rates in six slots), out / g_out [n][6]; the joint table, no g_a
 //   body acceleration  b / g_b [n][19] = (state, the derivatives of the joint's rate slots), out / g_out [n][6]; the joint table, no g_a
+//   mass inverse       b [n][23] = (pose, mass, inertia, the joint's force slots), out [n][6]; the joint table; forward only -- the
+//                      gradient is composed by the caller from this op and the body twist, pd_pose_op_vjp refuses the code by name
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
-struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; };  // max_nb 0: no cap (GEO_SETS needs one <= 256)
+struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; const char *composed = nullptr; };  // max_nb 0: no cap (GEO_SETS needs one <= 256); composed: no VJP kernel, and from what the gradient is put together
 constexpr TabledOp TABLED[] = {
     {PD_POSE_GROUND_WRENCH, "PD_POSE_GROUND_WRENCH", "contact", 0, true, GEO_WAVE, GEO_WAVE},
     {PD_POSE_JOINT_COORDS, "PD_POSE_JOINT_COORDS", "joint", JC_MAXNB, false, GEO_LANE, GEO_SETS},
@@ -1859,6 +2111,8 @@ constexpr TabledOp TABLED[] = {
     {PD_POSE_GENERALIZED_FORCE, "PD_POSE_GENERALIZED_FORCE", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_BODY_TWIST, "PD_POSE_BODY_TWIST", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_BODY_ACCEL, "PD_POSE_BODY_ACCEL", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
+    {PD_POSE_MASS_INVERSE, "PD_POSE_MASS_INVERSE", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS,
+     "the gradient is composed from pd_pose_op(21) and PD_POSE_BODY_TWIST (17)"},
 };
 
 template <class... A>
@@ -1869,12 +2123,13 @@ int refuse(const char *fmt, A... args) {  // pd_set_error of a formatted message
 }
 
 int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const float *rows, float *out, const float *g_out, float *g_a,
-                  float *g_b, hipStream_t st) {
+                  float *g_b, hipStream_t st, bool vjp) {
   if (nb <= 0 || n % nb != 0)  // before the n == 0 return, like the projection ops: a bad group size is refused at every n
     return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the bodies per state set, a_broadcast = nb >= 1");
   if (T.max_nb && nb > T.max_nb) return refuse("pd_pose_op: %s serves at most %d bodies per state set", T.name, T.max_nb);
   if (g_a && !T.has_g_a)  // before the n == 0 return, too
     return refuse("pd_pose_op_vjp: %s has no gradient for its %s table -- g_a_dev must be NULL", T.name, T.table);
+  if (vjp && T.composed) return refuse("pd_pose_op_vjp: %s has no VJP kernel -- %s", T.name, T.composed);  // at every n, before any launch
   if (n == 0) return 0;
   if (!tab || !rows) return pd_set_error("pd_pose_op: a NULL operand");
   if ((size_t)tab & 15) return refuse("pd_pose_op: the %s table a_dev must be 16-byte aligned", T.table);
@@ -1912,6 +2167,9 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
       if (out) hipLaunchKernelGGL(k_body_accel_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_body_accel_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
       break;
+    case PD_POSE_MASS_INVERSE:  // (forward only: the VJP was refused above)
+      hipLaunchKernelGGL(k_mass_inverse, grid, block, 0, st, count, nb, tab, rows, out);
+      break;
     default:
       if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
@@ -1921,12 +2179,13 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
   return 2;
 }
 
-int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream) {
+int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream,
+                  bool vjp) {  // vjp: which entry calls (at n = 0 every pointer may be NULL)
   if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH &&
-                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST && op != PD_POSE_BODY_ACCEL))  // (codes 7, 8, 10, 12, 14, 16 and 18 are not assigned: include/ppr_diffphys.h)
+                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST && op != PD_POSE_BODY_ACCEL && op != PD_POSE_MASS_INVERSE))  // (codes 7, 8, 10, 12, 14, 16, 18 and 20 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
-    if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream);
+    if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream, vjp);
   const bool project = op >= PD_POSE_PROJECT;
   if (project && (a_bcast < 0 || (a_bcast > 0 && n % a_bcast != 0)))  // before the n == 0 return: a bad group size is refused at every n
     return pd_set_error("pd_pose_op: n % g != 0 -- the element count must be a multiple of the camera group size a_broadcast");
@@ -2003,13 +2262,13 @@ extern "C" int pd_colsum(int n, int k, const float *x_dev, float *out_dev, float
 
 extern "C" int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream) {
   if (n > 0 && !out_dev) return pd_set_error("pd_pose_op: out_dev is NULL");
-  return pose_dispatch(op, n, a_dev, a_broadcast, b_dev, out_dev, nullptr, nullptr, nullptr, stream);
+  return pose_dispatch(op, n, a_dev, a_broadcast, b_dev, out_dev, nullptr, nullptr, nullptr, stream, false);
 }
 
 extern "C" int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev, float *g_a_dev,
                               float *g_b_dev, void *stream) {
   if (n > 0 && (!g_out_dev || (!g_a_dev && !g_b_dev))) return pd_set_error("pd_pose_op_vjp: g_out_dev is NULL, or both g_a_dev and g_b_dev");
-  return pose_dispatch(op, n, a_dev, a_broadcast, b_dev, nullptr, g_out_dev, g_a_dev, g_b_dev, stream);
+  return pose_dispatch(op, n, a_dev, a_broadcast, b_dev, nullptr, g_out_dev, g_a_dev, g_b_dev, stream, true);
 }
 
 extern "C" int pd_foot_height(int n, int nb, int nc, const float *body_q_dev, const int *c_body_dev, const float *c_point_dev,

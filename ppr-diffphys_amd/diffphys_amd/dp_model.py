@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import hip_backend
-from .dp_utils import _need_gpu, _state_rows
+from .dp_utils import _need_gpu, _q_rot, _state_rows
 
 
 def convert_ppr_warp(tensor):
@@ -351,6 +351,84 @@ class BodyAccelerations(torch.autograd.Function):
         return (g_r[:, :7].reshape(lead + (nb, 7)) if ctx.needs_input_grad[0] else None,
                 g_r[:, 7:13].reshape(lead + (nb, 6)) if ctx.needs_input_grad[1] else None,
                 g_r[:, 13:].reshape(lead + (nb, 6)) if ctx.needs_input_grad[2] else None, None, None)
+
+
+def _twist_form_partials(q, m, inertia, tx, tl):
+    """The partials of E = -sum_b tl_b . diag(R(q_b) sym(I_b) R(q_b)^T, m_b 1) . tx_b, the pairing of two twist fields [n, 6] = (w, v)
+    through the bodies' inertias, in closed form: q [n, 4] xyzw (raw partials: R is ``_q_rot``'s polynomial), m [n, 1], inertia
+    [n, 3, 3] -> (g_tx [n, 6], g_tl [n, 6], g_q [n, 4], g_m [n, 1], g_inertia [n, 3, 3]).  Plain torch on any device and dtype."""
+    sym = 0.5 * (inertia + inertia.transpose(-1, -2))
+    a, b = _q_rot(q, tl[:, :3], inverse=True), _q_rot(q, tx[:, :3], inverse=True)
+    Ia, Ib = (sym * a[:, None, :]).sum(-1), (sym * b[:, None, :]).sum(-1)   # (elementwise: a batched 3 x 3 matmul costs milliseconds here)
+    g_m = -(tl[:, 3:] * tx[:, 3:]).sum(-1, keepdim=True)
+    g_i = -0.5 * (a[:, :, None] * b[:, None, :] + b[:, :, None] * a[:, None, :])
+    g_tx = -torch.cat([_q_rot(q, Ia), m * tl[:, 3:]], dim=-1)
+    g_tl = -torch.cat([_q_rot(q, Ib), m * tx[:, 3:]], dim=-1)
+    u, w = q[:, :3], q[:, 3:]
+    g_q = 0
+    for v, g in ((tl[:, :3], -Ib), (tx[:, :3], -Ia)):   # the adjoint of R(q)^T v in q: v (2 w^2 - 1) - 2 w (u x v) + 2 u (u . v)
+        uv, gu, gv = (u * v).sum(-1, keepdim=True), (g * u).sum(-1, keepdim=True), (g * v).sum(-1, keepdim=True)
+        g_u = -2.0 * w * torch.cross(v, g, dim=-1) + 2.0 * (uv * g + gu * v)
+        g_w = 4.0 * w * gv - 2.0 * (g * torch.cross(u, v, dim=-1)).sum(-1, keepdim=True)
+        g_q = g_q + torch.cat([g_u, g_w], dim=-1)
+    return g_tx, g_tl, g_q, g_m, g_i
+
+
+class MassInverse(torch.autograd.Function):
+    """body_q (..., nb, 7), body_mass (..., nb), body_inertia (..., nb, 3, 3) (body frame, about the centre of mass; its symmetric part
+    enters), r6 (..., nb, 6) = the joint-space force entries of each body's joint in six slots (``hip_backend.joint_rate_slot_index``;
+    a slot no dof uses may hold anything and gets a zero gradient), env, rates -> (..., nb, 6) = x = H^-1 r in the same slots, 0 where
+    no dof is: H = J^T M J the articulation's mass matrix in the rate convention ``rates`` (``pd_pose_op`` PD_POSE_MASS_INVERSE on the
+    env's joint table: the articulated-body recursion, one launch).  All four tensors carry the full leading shape; gathering the slots
+    and broadcasting masses and inertias is the caller's (``dp_utils.mass_inverse`` does both, so that autograd sums shared ones).
+
+    The gradient is COMPOSED, there is no adjoint kernel: H is symmetric, so with lam = H^-1 g (the same kernel once more) the slot
+    gradient is lam, and the gradient in poses, masses and inertias is that of -sum_b tlam_b . M_b(q_b, m_b, I_b) . tx_b with
+    tx = body_twists(body_q, x), tlam = body_twists(body_q, lam), x and lam held constant: one launch of op 17 on the 2 S stacked sets,
+    one of its VJP, and M_b's partials in closed form in plain torch (``_twist_form_partials``).  When r6 alone needs a gradient only the first launch runs.  ONCE differentiable: backward
+    works on detached tensors, a second derivative is not available.  float32 GPU tensors, or an error: no CPU fallback.  Raw partials
+    (quaternion entries not projected)."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_mass, body_inertia, r6, env, rates="generalized"):
+        nb = int(env.nb)
+        _need_gpu("MassInverse", body_q, body_mass, body_inertia, r6)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_mass.shape) == lead + (nb,)
+                and tuple(body_inertia.shape) == lead + (nb, 3, 3) and tuple(r6.shape) == lead + (nb, 6)):
+            raise ValueError("MassInverse: body_q (..., %d, 7), body_mass (..., %d), body_inertia (..., %d, 3, 3) and r6 (..., %d, 6) with equal "
+                             "leading shapes; got %s, %s, %s and %s" % (nb, nb, nb, nb, tuple(body_q.shape), tuple(body_mass.shape),
+                                                                        tuple(body_inertia.shape), tuple(r6.shape)))
+        table = hip_backend.env_joint_table(env, body_q.device, rates)
+        rows = torch.cat([t.detach().reshape(-1, w) for t, w in ((body_q, 7), (body_mass, 1), (body_inertia, 9), (r6, 6))], dim=1)
+        out = hip_backend.mass_inverse(table, nb, rows)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows, out)
+        return out.view(lead + (nb, 6))
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, x = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:4]):
+            return None, None, None, None, None, None
+        lead, nb, n = ctx.lead, ctx.nb, rows.shape[0]
+        lam = hip_backend.mass_inverse(ctx.table, nb, torch.cat([rows[:, :17], g.to(torch.float32).reshape(-1, 6)], dim=1))
+        g_r = lam.reshape(lead + (nb, 6)) if ctx.needs_input_grad[3] else None
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, g_r, None, None
+        pose = rows[:, :7]
+        rows13 = torch.cat([torch.cat([pose, x], dim=1), torch.cat([pose, lam], dim=1)], dim=0)
+        tw = hip_backend.body_twists(ctx.table, nb, rows13)
+        g_tx, g_tl, g_q, g_m, g_i = _twist_form_partials(rows[:, 3:7], rows[:, 7:8], rows[:, 8:17].reshape(n, 3, 3), tw[:n], tw[n:])
+        g_tw = torch.cat([g_tx, g_tl], dim=0)
+        g_body_q = None
+        if ctx.needs_input_grad[0]:
+            g13 = hip_backend.body_twists_vjp(ctx.table, nb, rows13, g_tw.contiguous())
+            g_pose = g13[:n, :7] + g13[n:, :7]
+            g_pose[:, 3:] += g_q
+            g_body_q = g_pose.reshape(lead + (nb, 7))
+        return (g_body_q, g_m.reshape(lead + (nb,)) if ctx.needs_input_grad[1] else None,
+                g_i.reshape(lead + (nb, 3, 3)) if ctx.needs_input_grad[2] else None, g_r, None, None)
 
 
 def checkpoint_plan(nsteps, frame2step, K):

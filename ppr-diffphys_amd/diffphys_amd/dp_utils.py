@@ -680,15 +680,68 @@ def bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external=None, r
     return rnea(body_q, joint_qd, None, body_mass, body_inertia, env, external, rates)
 
 
-def forward_dynamics(body_q, joint_qd, tau, body_mass, body_inertia, env, external=None):
+def forward_dynamics(body_q, joint_qd, tau, body_mass, body_inertia, env, external=None, method="dense"):
     """The joint accelerations the joint-space forces tau (..., nqd) produce, in ``rnea``'s sign convention and the generalized rates:
-    solve(``mass_matrix``, tau - ``bias_forces``) -> (..., nqd), so ``forward_dynamics(rnea(qdd)) = qdd``.  Plain torch (a dense solve)
-    on ``mass_matrix`` -- S * nqd * nb rows through ``body_twists`` -- and ``bias_forces``: like ``mass_matrix`` it is meant for a few
-    state sets, not for a batch of thousands, and it is not an articulated-body kernel.  Differentiable in every tensor argument.
-    float32 GPU tensors only."""
+    H^-1 (tau - ``bias_forces``) -> (..., nqd), so ``forward_dynamics(rnea(qdd)) = qdd``.
+    method="dense" (the default): solve(``mass_matrix``, .), plain torch (a dense solve) on ``mass_matrix`` -- S * nqd * nb rows through
+    ``body_twists`` --: like ``mass_matrix`` it is meant for a few state sets, not for a batch of thousands, and it is not an
+    articulated-body kernel.  method="articulated": ``mass_inverse`` of the same right-hand side, the articulated-body recursion in one
+    HIP launch behind the three of ``bias_forces``: O(nb) per set, any batch size, once differentiable.  Differentiable in every tensor
+    argument.  float32 GPU tensors only."""
+    if method not in ("dense", "articulated"):
+        raise ValueError("forward_dynamics: method must be \"dense\" or \"articulated\"; got %r" % (method,))
+    if method == "articulated":
+        rhs = tau - bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external, "generalized")
+        return mass_inverse(body_q, rhs, body_mass, body_inertia, env, "generalized")
     H = mass_matrix(body_q, body_mass, body_inertia, env)
     rhs = tau - bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external, "generalized")
     return torch.linalg.solve(H, rhs[..., None])[..., 0]
+
+
+def mass_inverse(body_q, tau, body_mass, body_inertia, env, rates="generalized"):
+    """H^-1 applied to a joint-space vector: body_q (..., nb, 7) poses, tau broadcastable to (..., nqd) in the joint_qd layout (the
+    efforts conjugate to ``rates``), body_mass broadcastable to (..., nb), body_inertia (body frame, about the centre of mass; taken as
+    symmetric) to (..., nb, 3, 3) -> (..., nqd) = the joint accelerations tau produces on the articulation at rest without gravity,
+    H = sum_b J_b^T diag(R_b I_b R_b^T, m_b 1) J_b with J the Jacobian of ``body_twists`` in the same convention (rates="generalized":
+    H is ``mass_matrix``).  The articulated-body recursion as ONE HIP launch (``dp_model.MassInverse``, ``pd_pose_op`` code 21), O(nb)
+    per state set: the primitive of forward dynamics, impulse response and J H^-1 J^T at rollout batch sizes.  Differentiable ONCE in
+    all four tensors; the gradient is composed from the same kernel and ``body_twists`` (three launches).  tau is gathered into the op's
+    per-body slots and masses and inertias are broadcast HERE, outside the Function, so autograd sums the gradient of a shared entry.
+    A singular H (a massless body on a joint with dofs) gives inf / NaN.  float32 GPU tensors only."""
+    from . import hip_backend
+    from .dp_model import MassInverse
+
+    _need_gpu("mass_inverse", body_q, tau, body_mass, body_inertia)
+    nb, nqd = int(env.nb), int(env.template()["nqd"])
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7)):
+        raise ValueError("mass_inverse: body_q must be (..., %d, 7); got %s" % (nb, tuple(body_q.shape)))
+    lead = tuple(body_q.shape[:-2])
+    for name, t, tail in (("tau", tau, (nqd,)), ("body_mass", body_mass, (nb,)), ("body_inertia", body_inertia, (nb, 3, 3))):
+        try:
+            ok = t.dim() >= len(tail) and tuple(torch.broadcast_shapes(tuple(t.shape), lead + tail)) == lead + tail
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError("mass_inverse: %s must broadcast to %s; got %s" % (name, lead + tail, tuple(t.shape)))
+    hip_backend._jc_rate_mode(rates)
+    x6 = MassInverse.apply(body_q, body_mass.expand(lead + (nb,)), body_inertia.expand(lead + (nb, 3, 3)),
+                           _rate_slots(tau, lead, env, body_q.device), env, rates)
+    return x6.reshape(lead + (6 * nb,)).index_select(-1, hip_backend.env_joint_dof_slot_index(env, body_q.device))
+
+
+def mass_matrix_inverse(body_q, body_mass, body_inertia, env):
+    """H^-1 of the generalised rates, (..., nqd, nqd): ``mass_inverse`` on the identity -- nqd right-hand sides per state set, ONE
+    launch of S * nqd * nb rows.  ``mass_matrix_inverse @ mass_matrix`` is the identity to rounding.  Differentiable once.  float32 GPU
+    tensors only."""
+    _need_gpu("mass_matrix_inverse", body_q, body_mass, body_inertia)
+    nb, nqd = int(env.nb), int(env.template()["nqd"])
+    if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7)):
+        raise ValueError("mass_matrix_inverse: body_q must be (..., %d, 7); got %s" % (nb, tuple(body_q.shape)))
+    lead = tuple(body_q.shape[:-2])
+    eye = torch.eye(nqd, dtype=body_q.dtype, device=body_q.device)
+    cols = mass_inverse(body_q.unsqueeze(-3).expand(lead + (nqd, nb, 7)), eye, body_mass.unsqueeze(-2) if body_mass.dim() > 1 else body_mass,
+                        body_inertia.unsqueeze(-4) if body_inertia.dim() > 3 else body_inertia, env, "generalized")   # [..., j, :] = H^-1 e_j
+    return cols.transpose(-1, -2)
 
 
 def compute_com(body_q, part_com, part_mass):

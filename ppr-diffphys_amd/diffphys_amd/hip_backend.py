@@ -760,7 +760,7 @@ def _env_table(env, key, build):
 
 
 def _state_op_check(op, kind, width, table, nb, rows, bare=False, name=None, columns=None):
-    """The argument check of the sixteen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    """The argument check of the seventeen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
@@ -1279,6 +1279,44 @@ def body_accelerations_vjp(table, nb, rows, g_out):
     _check(lib().pd_pose_op_vjp(POSE_BODY_ACCEL, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", n * 6),
                                 None, _ptr(g_b, "g_b"), _stream()))
     return g_b
+
+
+POSE_MASS_INVERSE = 21   # (code 20 is not assigned either: include/ppr_diffphys.h)
+_MI_COLUMNS = "(p, q xyzw, m, I row-major, r[6])"
+
+
+def joint_dof_slot_index(tpl):
+    """[nqd] int64 numpy: the flat slot 6 b + k that holds dof j = qd_start[b] + k -- the inverse of ``joint_rate_slot_index`` on the
+    slots in use; brings a per-body slot tensor [..., 6 nb] back to the joint_qd layout with one index_select."""
+    idx = joint_rate_slot_index(tpl).reshape(-1)
+    nqd = int(tpl["nqd"])
+    used = np.nonzero(idx < nqd)[0]
+    out = np.full(nqd, -1, np.int64)
+    out[idx[used]] = used
+    if (out < 0).any():
+        raise ValueError("joint_dof_slot_index: dof %d belongs to no joint" % int(np.nonzero(out < 0)[0][0]))
+    return out
+
+
+def env_joint_dof_slot_index(env, device):
+    """``joint_dof_slot_index`` of a :class:`diffphys_amd.sim.Model` as an [nqd] int64 tensor on ``device``, cached on the model."""
+    return _env_table(env, ("jointdofslots", str(torch.device(device))),
+                      lambda tpl: torch.from_numpy(joint_dof_slot_index(tpl)).to(device))
+
+
+def mass_inverse(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_MASS_INVERSE: rows [n, 23] = (p, q xyzw, m, I row-major, r[6]) per body -- a pose, the body's mass and
+    body-frame inertia about its centre of mass (its symmetric part enters) and the joint-space force entries of that body's joint in
+    six slots (``joint_rate_slot_index``) --, n a multiple of nb (row i is body i % nb of set i // nb), and the joint table of
+    ``joint_coords`` -> [n, 6]: H^-1 r in the same slots, 0 in a slot no dof uses, H = J^T M J the mass matrix of the articulation in
+    the table's rate mode ("generalized": ``dp_utils.mass_matrix``; "measured": the COMPOUND columns are those of the measured rates).
+    The articulated-body recursion, one launch, O(nb) per set.  The op is self-adjoint in its slots; there is no VJP entry
+    (``pd_pose_op_vjp`` refuses the code): ``dp_model.MassInverse`` composes the gradient from this op and ``body_twists``.  A singular
+    H gives inf / NaN.  Fixed summation order: a set's bits depend neither on the call nor on the other sets."""
+    n, _ = _state_op_check("mass_inverse", "joint", 23, table, int(nb), rows, name="rows", columns=_MI_COLUMNS)
+    out = torch.empty(n, 6, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_MASS_INVERSE, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
 
 
 def _dev_int(t, name):
