@@ -89,7 +89,16 @@ int pd_model_get_segment_width(const pd_model *m);
  * three times the lane-cycles per env) while the batch fits one workgroup per compute unit (<= 4 x CUs envs = 1 024 on MI355X) and the
  * lane-per-body kernels above that; 1: lane per body always; 2: quad-lane wherever the robot is eligible (tests, A/B timing).
  * pd_model_get_kernel_family returns the setting; *eligible (may be NULL) = 1 when the robot has quad-lane kernels at all (whether
- * its contact tables live in LDS or, when they fit at no segment width, in global memory). */
+ * its contact tables live in LDS or, when they fit at no segment width, in global memory).
+ *
+ * Parent-side joint frames (tests, A/B timing; no new entry: the choice rides on `family`).  A revolute-only robot whose joint_X_p
+ * rotations are all bitwise (0, 0, 0, 1) -- Laikago -- qualifies for lane-per-body adjoint kernels compiled without the product
+ * q_p = q_parent (x) q_pj and its adjoint; by default such a robot's adjoint launches take them (not while a per-env joint_X_p is bound:
+ * device data the host has not seen).  family + PD_PFI_GENERAL: the general kernels always; family + PD_PFI_SPECIALISED: refused with an
+ * error unless the robot qualifies; a plain 0 .. 2 is automatic again.  pd_model_get_kernel_family returns what was set, sum included.
+ * pd_last_launch_info(m, PD_LAUNCH_INFO_PARENT_FRAMES, out) tells whether the robot qualifies and what the last adjoint launch ran. */
+#define PD_PFI_GENERAL 4
+#define PD_PFI_SPECIALISED 8
 int pd_model_set_kernel_family(pd_model *m, int family);
 int pd_model_get_kernel_family(const pd_model *m, int *eligible);
 
@@ -652,7 +661,10 @@ int pd_model_set_timing(pd_model *m, int on);
 float pd_last_kernel_ms(const pd_model *m, int kind);
 
 /* Launch geometry of the last rollout launch of `kind` on this model (bench.py reports it beside the roofline):
- * out[0] workgroups, out[1] threads per workgroup, out[2] dynamic LDS bytes per workgroup, out[3] envs per workgroup. */
+ * out[0] workgroups, out[1] threads per workgroup, out[2] dynamic LDS bytes per workgroup, out[3] envs per workgroup.
+ * kind PD_LAUNCH_INFO_PARENT_FRAMES (see pd_model_set_kernel_family): out[0] 1 when the robot qualifies for the adjoint kernels of unrotated
+ * parent-side joint frames, out[1] the setting (0 automatic, 1 general, 2 specialised), out[2] 1 when the last adjoint launch ran them, out[3] 0. */
+#define PD_LAUNCH_INFO_PARENT_FRAMES 2
 int pd_last_launch_info(const pd_model *m, int kind, int out[4]);
 
 #ifdef __cplusplus

@@ -40,6 +40,8 @@ struct PdLaunchCfg {
   int groups;    // env groups (of 64 / segw envs) per workgroup, 1 .. PD_BWAVES
   int nblocks, threads;
   size_t lds;    // dynamic LDS bytes per workgroup
+  int pji;       // adjoint of a revolute-only plain model: 1 = every parent-side joint frame has the identity rotation, and the launch takes the
+                 // kernels compiled for that (k_rollout_bwd PJI) where the family has them; 0 = the general kernels
 };
 // Env groups per workgroup: as many as it takes to cover the batch with one workgroup per compute unit, at most PD_BWAVES.
 // A small batch (512 Laikago envs = 128 groups) then occupies 128 CUs with one group each instead of 32 CUs with four.

@@ -959,14 +959,20 @@ PD_DEV RevCache rev_cache_load(const float *d) {
 }
 
 // pp, qp, w_p: pose and angular velocity of the parent body (ignored for a joint to the world)
-template <bool HP = false>
+// PJI (here, in rev_adjoint_core and in rev_adjoint): the caller promises a PLAIN model whose parent-side joint frames all have the
+// identity rotation, q_pj bitwise (0, 0, 0, 1) -- a property of the model (Laikago's), decided on the host (pd_host.hip
+// parent_frames_identity).  q_p = qp (x) q_pj is then qp for every finite qp, and what the general code spends on the product and on its
+// adjoint is left out; PJI = false is the general code as it was.
+template <bool HP = false, bool PJI = false>
 PD_DEV RevCache rev_forward(const PdDevModel &m, const BodyConst &c, qt q_c, v3 w_c, v3 pp, qt qp, v3 w_p, float tgt, float act, float ke,
                             float kd) {
+  static_assert(!PJI || HP, "PJI: a plain model");
   RevCache R;
   R.x_p = c.p_pj; R.q_p = c.q_pj;
   if (HP || c.parent >= 0) {
     R.x_p = pp + qrot(qp, c.p_pj);
-    R.q_p = qmul(qp, c.q_pj);
+    if constexpr (PJI) R.q_p = qp;
+    else R.q_p = qmul(qp, c.q_pj);
   } else {
     w_p = V3(0, 0, 0);
   }
@@ -981,7 +987,10 @@ PD_DEV RevCache rev_forward(const PdDevModel &m, const BodyConst &c, qt q_c, v3 
 }
 
 // Parent quantities are passed explicitly (pp, qp, w_p, v_p, rc_par = rot(qp, com_par); ignored for a joint to the world).
-template <bool HP = false>
+// PJI (see rev_forward): q_p IS qp, so axis_p = rotm(qp) axis and its adjoint is one more outer product into the matrix adjoint aP that
+// rc_par and x_p already share (9 instructions for adj_qrot_q's ~46); what is left of adj_q_p, the r_err term, is added to par.r as it is
+// (no product with conj(q_pj), ~28); R.q_p is not read (qp of the parent's record has its bits); r_c = -rc_c exactly.
+template <bool HP = false, bool PJI = false>
 PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, v3 pp, qt qp, v3 w_p, v3 v_p, v3 rc_par,
                              const RevCache &R, float tgt, float ke, float kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own, BodyAdj &par,
                              float *aR, float &a_tgt, float &a_act, float &a_ke, float &a_kd) {  // aR: matrix adjoint of rotm(s.r), see integrate_adj2
@@ -992,7 +1001,9 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
   } else {
     pp = V3(0, 0, 0); w_p = pp; v_p = pp; qp = Q4(0, 0, 0, 1);
   }
-  const v3 r_c = s.p - (s.p + rc_c);
+  static_assert(!PJI || HP, "PJI: a plain model");
+  const qt q_p = PJI ? qp : R.q_p;
+  const v3 r_c = PJI ? -rc_c : s.p - (s.p + rc_c);
   const v3 x_err = s.p - R.x_p, v_err = s.v - v_p, w_err = s.w - w_p;
   const v3 f_total = x_err * ake + v_err * akd;
   v3 adj_t = -gc_t, adj_f = -gc_f, adj_r_c = V3(0, 0, 0), adj_r_p = V3(0, 0, 0);
@@ -1016,11 +1027,11 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
   const float adj_da = adj_q * R.dq_dda;
   adj_r_err.x += c.axis.x * adj_da; adj_r_err.y += c.axis.y * adj_da; adj_r_err.z += c.axis.z * adj_da;
   adj_r_err.w += adj_q * R.dq_dw;
-  adj_qrot_q(R.q_p, c.axis, adj_q_p, adj_axis_p);
+  if constexpr (!PJI) adj_qrot_q(q_p, c.axis, adj_q_p, adj_axis_p);  // (PJI: into aP below)
   add_outer(aR, adj_axis_c, c.axis);  // axis_c = rotm(s.r) axis
   {  // r_err = conj(q_p) * q_c
     qt adj_cqp = Q4(0, 0, 0, 0);
-    adj_qmul(qconj(R.q_p), s.r, adj_cqp, adj_q_c, adj_r_err);
+    adj_qmul(qconj(q_p), s.r, adj_cqp, adj_q_c, adj_r_err);
     adj_q_p += qconj(adj_cqp);
   }
   add_outer(aR, -adj_r_c, c.com);     // rc_c = rotm(s.r) com
@@ -1034,13 +1045,15 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
     for (int k = 0; k < 9; ++k) aP[k] = 0.f;
     add_outer(aP, -adj_r_p, c.com_par);
     add_outer(aP, adj_x_p, c.p_pj);
+    if constexpr (PJI) add_outer(aP, adj_axis_p, c.axis);  // axis_p = rotm(qp) axis
     rotm_adj(qp, aP, par.r);
-    adj_qmul_a(c.q_pj, par.r, adj_q_p);
+    if constexpr (PJI) par.r += adj_q_p;                   // q_p = qp
+    else adj_qmul_a(c.q_pj, par.r, adj_q_p);
     par.w = -adj_w_err; par.v = -adj_v_err;
   }
 }
 
-template <bool HP = false>
+template <bool HP = false, bool PJI = false>
 PD_DEV void rev_adjoint(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, const float *rec, const RevCache &R,
                         float tgt, float ke, float kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own, BodyAdj &par, float *aR, float &a_tgt,
                         float &a_act, float &a_ke, float &a_kd) {
@@ -1050,7 +1063,7 @@ PD_DEV void rev_adjoint(const PdDevModel &m, const BodyConst &c, const BodyState
     const float *r = rec + (HP ? c.pidx : c.parent) * PD_REC;  // (pidx: the call may run for a lane without a joint, see the CLONE kernels)
     pp = ld3(r); qp = ld4(r + 3); w_p = ld3(r + 7); v_p = ld3(r + 10); rc_par = ld3(r + 13);
   }
-  rev_adjoint_core<HP>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt, a_act, a_ke, a_kd);
+  rev_adjoint_core<HP, PJI>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt, a_act, a_ke, a_kd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1119,7 +1132,10 @@ PD_DEV void add_outer(LdsAcc9 M, v3 a, v3 b) {
 #pragma unroll
   for (int k = 0; k < 9; ++k) M.p[k] = t[k];
 }
-template <typename ACC, typename F>
+// PURE: the two quaternion products with W = (w1, 0) as qmul_pure (pd_math.h), without the four products with the zero -- rq then has the
+// bits the LEAN forward pass (integrate_bodies) gave it.  Set by the adjoint kernels that are compiled anew anyway (k_rollout_bwd PJI); the
+// others keep their instruction streams.
+template <bool PURE = false, typename ACC, typename F>
 PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodyState &s, const float *Rm, unsigned clamp_mask, v3 t0, v3 f0, float inv_m,
                            const float *I, const float *invI, float dt, const BodyAdj &gn, BodyAdj &a, float *aR, float &g_inv_m, ACC g_I,
                            ACC g_invI, F &&wrench_ready) {
@@ -1132,7 +1148,7 @@ PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodySt
   v3 u = wb + mat_vec(invI, tb) * dt;
   v3 w1 = mat_vec(Rm, u);
   qt W = Q4(w1.x, w1.y, w1.z, 0.f);
-  qt rq = s.r + qmul(W, s.r) * (0.5f * dt);
+  qt rq = s.r + (PURE ? qmul_pure(w1, s.r) : qmul(W, s.r)) * (0.5f * dt);
   qt r1 = qnormalize(rq);
   // ---- reverse, phase 1: the path to the wrench adjoint
   qt adj_r1 = gn.r;
@@ -1156,7 +1172,8 @@ PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodySt
   wrench_ready(adj_t0, adj_f0);
   // ---- phase 2
   qt adj_r0 = adj_rq;
-  adj_qmul_b(W, adj_r0, gW);
+  if constexpr (PURE) adj_r0 += qmul_pure(-w1, gW);  // conj(W) gW
+  else adj_qmul_b(W, adj_r0, gW);
   add_outer(aR, adj_w1, u);    // w1 = Rm u
   add_outer(g_invI, adj_a, tb);
   add_outer(aR, t0, adj_tb);   // Rm^T t0
@@ -1171,8 +1188,9 @@ PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodySt
   a.p = gn.p; a.r = adj_r0; a.w = adj_w0; a.v = adj_v1;
 }
 
+template <bool PURE = false>
 PD_DEV void integrate_adj(const PdDevModel &m, const BodyConst &c, const BodyState &s, const float *Rm, unsigned clamp_mask, v3 t0, v3 f0, float inv_m,
                           const float *I, const float *invI, float dt, const BodyAdj &gn, BodyAdj &a, float *aR, v3 &adj_t0, v3 &adj_f0,
                           float &g_inv_m, float *g_I, float *g_invI) {
-  integrate_adj2(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, dt, gn, a, aR, g_inv_m, g_I, g_invI, [&](v3 t, v3 f) { adj_t0 = t; adj_f0 = f; });
+  integrate_adj2<PURE>(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, dt, gn, a, aR, g_inv_m, g_I, g_invI, [&](v3 t, v3 f) { adj_t0 = t; adj_f0 = f; });
 }

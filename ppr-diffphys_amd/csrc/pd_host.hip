@@ -31,6 +31,12 @@ struct pd_model {
   Quad *quad = nullptr;
   int policy = 0;  // pd_model_set_numeric_policy: PD_NUM_STABLE / PD_NUM_LITERAL (which objects' rollout kernels a launch takes)
   int family = 0;  // pd_model_set_kernel_family: 0 automatic (by batch size), 1 lane per body always, 2 quad-lane wherever eligible
+  // parent_frames_identity: a revolute-only PLAIN model whose jointed bodies' parent-side joint frames all have the rotation bitwise
+  // (0, 0, 0, 1) (build_device) -- its lane-per-body adjoint has kernels without the q_pj algebra (plan_launch, k_rollout_bwd PJI).
+  // pfi_mode (pd_model_set_kernel_family, tests and A/B timing): 0 automatic, 1 the general kernels always, 2 the specialised ones (refused
+  // unless the model qualifies)
+  bool parent_frames_identity = false;
+  int pfi_mode = 0;
   void *blob = nullptr;
   PdDevModel dev{};
   size_t lds_max = 0;  // what the kernels' dynamic-LDS attribute is at least set to
@@ -46,6 +52,7 @@ struct pd_model {
   hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   bool ev_valid[2] = {false, false};
   int last_launch[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  int last_pji = 0;  // the last adjoint launch ran the kernels of unrotated parent frames
 };
 
 // kd-order: recursively split along the longest axis so that runs of `leaf` consecutive points are compact
@@ -307,6 +314,17 @@ static int lds_sizing(PdDevModel &d, int segw, int jt, size_t &lds_tables, int &
   return 0;
 }
 
+// Every jointed body's parent-side joint frame has the rotation (0, 0, 0, 1), bit for bit, in a revolute-only PLAIN model (jt: what
+// chain_topology made of the joint mix): q_p = qp (x) q_pj is then qp itself, and the adjoint has kernels that leave the product and its
+// adjoint out (pd_device.h rev_forward PJI).  A property of the template; a per-env joint_X_p bound later is looked at by plan_launch.
+static bool parent_frames_identity(const pd_model *m, int jt) {
+  if (jt != PD_JT_REVOLUTE) return false;
+  const float one[4] = {0.f, 0.f, 0.f, 1.f};
+  for (int i = 0; i < m->nb; ++i)
+    if (m->jtype[i] != PD_JOINT_FREE && memcmp(&m->X_p[i * 7 + 3], one, sizeof one) != 0) return false;
+  return true;
+}
+
 // Builds the device copy for segment width `segw` into temporaries and commits blob / dev / lds_* / segw / jt only when
 // every check has passed: a failed call leaves the model exactly as it was.
 // global_tables: the contact tables stay in global memory and only the per-env part of a workgroup's LDS has to fit -- for the
@@ -359,6 +377,7 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
   m->blob = blob; m->dev = d;
   m->lds_tables = lds_tables; m->lds_max = (size_t)lds_max;
   m->segw = segw; m->jt = ch.jt; m->contact_order = t.order;
+  m->parent_frames_identity = parent_frames_identity(m, ch.jt);
   return 0;
 }
 
@@ -424,6 +443,9 @@ static LaunchPlan plan_launch(const pd_model *m, int kind, int n_envs, bool loss
   // env groups per workgroup: small batches spread over all CUs (pd_groups_per_wg); the FK kinds always run PD_BWAVES
   c.groups = !rollout ? PD_BWAVES : (g_groups ? g_groups : pd_groups_per_wg(n_groups, d.cu_count));
   if (c.kernel == PD_KV_BWD_QUAD && c.groups > 2) c.groups = 2;  // (three roles: at most 384 threads, two waves per SIMD -- the body wave needs its 256 VGPRs)
+  // the adjoint of a model with unrotated parent-side joint frames: the lane-per-body family has kernels for it (a joint_X_p bound per env
+  // is device data the host has not seen: such a launch keeps the general kernels)
+  c.pji = kind == PD_K_ROLLOUT_BWD && !quad && m->parent_frames_identity && m->pfi_mode != 1 && !m->xp_env ? 1 : 0;
   finish_cfg(c, d, n_groups, epw, d.global_tables ? 0 : (quad ? m->quad->lds_tables : m->lds_tables), 0, 0);
   return LaunchPlan{c, &d, jt, rollout && m->policy == PD_NUM_LITERAL ? 1 : 0, width_index(segw), {c.nblocks, c.threads, (int)c.lds, c.groups * epw}};
 }
@@ -432,6 +454,7 @@ static hipError_t launch(const pd_model *m, int kind, const void *args, int n_en
   const LaunchPlan p = plan_launch(m, kind, n_envs, kind == PD_K_ROLLOUT_FWD && ((const RolloutArgs *)args)->loss_target != nullptr);
   if (p.cfg.nblocks == 0) return hipSuccess;
   if (kind <= PD_K_ROLLOUT_BWD) std::copy(p.info, p.info + 4, const_cast<pd_model *>(m)->last_launch[kind]);
+  if (kind == PD_K_ROLLOUT_BWD) const_cast<pd_model *>(m)->last_pji = p.cfg.pji;
   return g_launch[p.policy][p.wi](kind, p.jt, *p.dev, args, p.cfg, st);
 }
 
@@ -544,15 +567,20 @@ int pd_model_set_segment_width(pd_model *m, int lanes) {
   return 0;
 }
 
+// family: the kernel family (0 .. 2) + PD_PFI_GENERAL / PD_PFI_SPECIALISED (the header); a plain 0 .. 2 puts the parent-frame choice
+// back to automatic
 int pd_model_set_kernel_family(pd_model *m, int family) {
   if (!m) return fail("null model");
-  if (family < 0 || family > 2) return fail("kernel family: 0 automatic, 1 lane per body, 2 quad-lane where eligible");
-  m->family = family;
+  const int fam = family & 3, mode = family >> 2;
+  if (family < 0 || fam > 2 || mode > 2) return fail("kernel family: 0 automatic, 1 lane per body, 2 quad-lane where eligible (+ PD_PFI_GENERAL or PD_PFI_SPECIALISED)");
+  if (mode == 2 && !m->parent_frames_identity)
+    return fail("PD_PFI_SPECIALISED: the model does not qualify (revolute-only plain model whose parent-side joint frames all have the rotation (0, 0, 0, 1))");
+  m->family = fam; m->pfi_mode = mode;
   return 0;
 }
 int pd_model_get_kernel_family(const pd_model *m, int *eligible) {
   if (eligible) *eligible = (m && m->quad) ? 1 : 0;
-  return m ? m->family : 0;
+  return m ? m->family | (m->pfi_mode << 2) : 0;
 }
 int pd_model_set_numeric_policy(pd_model *m, int policy) {
   if (!m) return fail("null model");
@@ -879,7 +907,11 @@ float pd_last_kernel_ms(const pd_model *m, int kind) {
   return ms;
 }
 int pd_last_launch_info(const pd_model *m, int kind, int out[4]) {
-  if (!m || !out || kind < 0 || kind > 1) return fail("bad argument");
+  if (!m || !out || kind < 0 || kind > PD_LAUNCH_INFO_PARENT_FRAMES) return fail("bad argument");
+  if (kind == PD_LAUNCH_INFO_PARENT_FRAMES) {
+    out[0] = m->parent_frames_identity ? 1 : 0; out[1] = m->pfi_mode; out[2] = m->last_pji; out[3] = 0;
+    return 0;
+  }
   for (int k = 0; k < 4; ++k) out[k] = m->last_launch[kind][k];
   return 0;
 }

@@ -1535,9 +1535,12 @@ __device__ __forceinline__ bool grad_wanted(const float *g) {
   else return true;
 }
 
-template <int SEGW, int JT, bool QUAD = false, bool SEL = false>
+// PJI: every parent-side joint frame of the model has the identity rotation (pd_device.h rev_forward; the host's plan says so per launch:
+// PdLaunchCfg::pji).  Lane-per-body family only: the quad-lane body wave keeps the general joint code.
+template <int SEGW, int JT, bool QUAD = false, bool SEL = false, bool PJI = false>
 __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutArgs a) {
   static_assert(JT == PD_JT_REVOLUTE, "the wave-specialised adjoint of revolute-only plain models: every jointed body is a revolute joint on a parent body");
+  static_assert(!(QUAD && PJI), "PJI: lane-per-body family only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
   const int bw = (int)blockDim.x / (QUAD ? 192 : 128);  // env groups per workgroup (host's choice per launch)
@@ -1731,7 +1734,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
         const qt q_c = Q4(pose[0].x, pose[0].y, pose[0].z, pose[0].w), qp = Q4(pose[2].x, pose[2].y, pose[2].z, pose[2].w);
         const v3 w_c = V3(pose[1].x, pose[1].y, pose[1].z), pp = V3(pose[4].x, pose[4].y, pose[4].z), w_p = V3(pose[3].x, pose[3].y, pose[3].z);
         float *dst = jc + (step & 1) * m.env_lds_jc + b * PD_JC;
-        rev_cache_store(dst, rev_forward<true>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
+        rev_cache_store(dst, rev_forward<true, PJI>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
       }
       STAMP(8);
       // request everything the next iteration needs; nothing loaded here is touched before the next PD_WAIT_VMEM
@@ -2156,7 +2159,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
     float aR[9];  // matrix adjoint of Rm, summed over integrate_bodies and the joint; converted after both
 #pragma unroll
     for (int k = 0; k < 9; ++k) aR[k] = 0.f;
-    integrate_adj(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, a.dt, gn, ga, aR, adj_t0, adj_f0, g_inv_m, g_I, g_invI);
+    integrate_adj<PJI>(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, a.dt, gn, ga, aR, adj_t0, adj_f0, g_inv_m, g_I, g_invI);
     if (is_body) {
       float *f = adjf + b * PD_W6;
       f[0] = adj_t0.x; f[1] = adj_t0.y; f[2] = adj_t0.z; f[3] = adj_f0.x; f[4] = adj_f0.y; f[5] = adj_f0.z;
@@ -2181,7 +2184,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       const v3 gp_t = ld3(adjf + c.parent * PD_W6), gp_f = ld3(adjf + c.parent * PD_W6 + 3);  // (plain model: every jointed body hangs on one)
       // the state-only half comes from the contact wave
       const RevCache R = rev_cache_load(jc + (step & 1) * m.env_lds_jc + b * PD_JC);
-      rev_adjoint<true>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
+      rev_adjoint<true, PJI>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
     }
     rotm_adj(s.r, aR, ga.r);
     if (is_body) {
@@ -2803,15 +2806,17 @@ static RolloutKernel select_fwd(int kernel, int roles, bool runsum, bool loss) {
   else return nullptr;
 }
 
-// k_rollout_bwd<SEGW, JT, QUAD, SEL> for revolute-only robots, k_rollout_bwd3<SEGW, JT, GT, SEL> for every other joint mix
+// k_rollout_bwd<SEGW, JT, QUAD, SEL, PJI> for revolute-only robots, k_rollout_bwd3<SEGW, JT, GT, SEL> for every other joint mix
+// pji: the plan's promise that the model's parent-side joint frames are unrotated (PdLaunchCfg::pji) -- the lane-per-body kernel then has a
+// PJI instantiation; the quad-lane kernel and k_rollout_bwd3 are the same kernels either way
 template <int JT, bool GT, bool SEL>
-static RolloutKernel select_bwd(int kernel) {
+static RolloutKernel select_bwd(int kernel, bool pji) {
   if constexpr (pd_split(JT)) {
     if (kernel == PD_KV_BWD_QUAD) {
       if constexpr (PD_SEGW == 64) return k_rollout_bwd<PD_SEGW, JT, true, SEL>;
       else return nullptr;
     }
-    return k_rollout_bwd<PD_SEGW, JT, false, SEL>;
+    return pji ? k_rollout_bwd<PD_SEGW, JT, false, SEL, true> : k_rollout_bwd<PD_SEGW, JT, false, SEL>;
   } else {
     return k_rollout_bwd3<PD_SEGW, JT, GT, SEL>;
   }
@@ -2828,7 +2833,7 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
 }
 template <int JT, bool GT, bool SEL>
 static hipError_t launch_bwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
-  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel), m, a, cfg, st);
+  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel, cfg.pji != 0), m, a, cfg, st);
 }
 
 template <int JT, bool GT>
@@ -2885,7 +2890,8 @@ static hipError_t set_lds_fwd(int bytes) {
 template <int JT, bool GT, bool SEL>
 static hipError_t set_lds_bwd(int bytes) {
   for (const int kernel : kBwdVariants)
-    if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel), bytes)) return e;
+    for (int pji = 0; pji < 2; ++pji)
+      if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel, pji != 0), bytes)) return e;
   return hipSuccess;
 }
 

@@ -61,6 +61,24 @@ def _select_grads(g, want):
     return g if len(want) == len(GRAD_NAMES) else {k: v for k, v in g.items() if k not in GRAD_NAMES or k in want}
 
 
+def parent_frames_identity(tpl):
+    """The library's test (csrc/pd_host.hip parent_frames_identity) on a template dict, without a device: a revolute-only robot whose
+    jointed bodies all hang on a body, with unrotated child joint frames, and whose parent-side joint frames joint_X_p all carry the
+    rotation (0, 0, 0, 1) bit for bit.  Such a robot's lane-per-body adjoint takes the kernels compiled without the q_pj algebra
+    (DeviceModel.set_parent_frame_identity); DeviceModel.parent_frames_identity() is the library's own answer."""
+    nb = int(tpl["nb"])
+    ty = np.asarray(tpl["joint_type"]).reshape(-1)
+    par = np.asarray(tpl["joint_parent"]).reshape(-1)
+    jointed = ty != 4   # (4: FREE)
+    if not (set(int(t) for t in ty[jointed]) == {1} and (par[jointed] >= 0).all()):   # (1: REVOLUTE)
+        return False
+    one = np.asarray([0, 0, 0, 1], np.float32).view(np.uint32)
+    rot = lambda k: np.ascontiguousarray(np.asarray(tpl[k], np.float32).reshape(nb, 7)[:, 3:])
+    if not (rot("joint_X_c") == np.asarray([0, 0, 0, 1], np.float32)).all():   # (a PLAIN model: compared by value, as the library does)
+        return False
+    return bool((rot("joint_X_p").view(np.uint32)[jointed] == one).all())
+
+
 class _Desc(ctypes.Structure):
     _fields_ = [
         ("nb", ctypes.c_int), ("nq", ctypes.c_int), ("nqd", ctypes.c_int), ("nc", ctypes.c_int), ("nmat", ctypes.c_int),
@@ -258,6 +276,7 @@ class DeviceModel:
         self.h = h
         self._xp = None
         self._nc_keep = keep["contact_body"]
+        self._family, self._pfi = 0, 0
 
     def __del__(self):
         try:
@@ -275,7 +294,23 @@ class DeviceModel:
 
     def set_kernel_family(self, family):
         """0 automatic (by batch size), 1 lane per body always, 2 quad-lane (four lanes per body) wherever the robot is eligible."""
-        _check(lib().pd_model_set_kernel_family(self.h, int(family)))
+        _check(lib().pd_model_set_kernel_family(self.h, int(family) + 4 * self._pfi))
+        self._family = int(family)
+
+    def set_parent_frame_identity(self, mode):
+        """Adjoint kernels of a revolute-only robot whose parent-side joint frames (joint_X_p) are all unrotated -- Laikago: 0 automatic (such
+        a robot's lane-per-body adjoint takes the kernels compiled without the q_pj algebra), 1 the general kernels always, 2 the specialised
+        ones (raises unless the robot qualifies).  For tests and A/B timing; rides on ``pd_model_set_kernel_family``."""
+        if int(mode) not in (0, 1, 2):
+            raise ValueError("parent frame identity mode: 0 automatic, 1 general, 2 specialised")
+        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * int(mode)))
+        self._pfi = int(mode)
+
+    def parent_frames_identity(self):
+        """True when the library found every parent-side joint frame of this revolute-only robot unrotated (see set_parent_frame_identity)."""
+        out = (ctypes.c_int * 4)()
+        _check(lib().pd_last_launch_info(self.h, 2, ctypes.byref(out)))
+        return bool(out[0])
 
     def set_numeric_policy(self, policy):
         """NUM_STABLE (default) / NUM_LITERAL: how the revolute twist angle and the FIXED joint's angular error are evaluated by the rollout
@@ -288,7 +323,7 @@ class DeviceModel:
     def kernel_family(self):
         """(setting, eligible): eligible = the robot has quad-lane kernels (revolute-only, at most 16 bodies)."""
         el = ctypes.c_int(0)
-        return int(lib().pd_model_get_kernel_family(self.h, ctypes.byref(el))), bool(el.value)
+        return int(lib().pd_model_get_kernel_family(self.h, ctypes.byref(el))) & 3, bool(el.value)
 
     def workspace_floats(self, bs, nsteps):
         return int(lib().pd_rollout_workspace_floats(self.h, bs, nsteps))
@@ -315,7 +350,11 @@ class DeviceModel:
     def last_launch_info(self, kind):
         out = (ctypes.c_int * 4)()
         _check(lib().pd_last_launch_info(self.h, int(kind), ctypes.byref(out)))
-        return dict(workgroups=out[0], threads_per_wg=out[1], lds_bytes_per_wg=out[2], envs_per_wg=out[3])
+        info = dict(workgroups=out[0], threads_per_wg=out[1], lds_bytes_per_wg=out[2], envs_per_wg=out[3])
+        if int(kind) == 1:  # the adjoint: did it run the kernels of unrotated parent-side joint frames (set_parent_frame_identity)
+            pf = (ctypes.c_int * 4)()
+            info["parent_frame_identity"] = lib().pd_last_launch_info(self.h, 2, ctypes.byref(pf)) == 0 and bool(pf[2])
+        return info
 
     # -- rollout ----------------------------------------------------------------
     def alloc_rollout(self, bs, nsteps, nframes, device, want_forces=True, backward=True, save_trajectory=True):

@@ -48,7 +48,7 @@ with open(os.path.join(dst, tag + "_pmc.csv"), "w") as f:
 def code_object_registers(demangled):
     """VGPRs / spills of a kernel from the code-object metadata of THIS tree's sources (scripts/dump_isa.sh compiles them to ISA):
     rocprofv3's VGPR_Count column is in allocation granules of a wave32 (it printed 80 / 128 for kernels that have 159 / 252), which
-    reads as if four waves fitted a SIMD (VERDICT r3 weak #9).  demangled: e.g. 'void k_rollout_bwd<16, 1, false, false>(...)' (SEGW, JT, QUAD, SEL)."""
+    reads as if four waves fitted a SIMD (VERDICT r3 weak #9).  demangled: e.g. 'void k_rollout_bwd<16, 1, false, false, true>(...)' (SEGW, JT, QUAD, SEL, PJI)."""
     import re
     import subprocess
     m = re.search(r"(k_rollout_\w+)<([^>]*)>", demangled)
