@@ -96,9 +96,15 @@ int pd_model_get_segment_width(const pd_model *m);
  * q_p = q_parent (x) q_pj and its adjoint; by default such a robot's adjoint launches take them (not while a per-env joint_X_p is bound:
  * device data the host has not seen).  family + PD_PFI_GENERAL: the general kernels always; family + PD_PFI_SPECIALISED: refused with an
  * error unless the robot qualifies; a plain 0 .. 2 is automatic again.  pd_model_get_kernel_family returns what was set, sum included.
- * pd_last_launch_info(m, PD_LAUNCH_INFO_PARENT_FRAMES, out) tells whether the robot qualifies and what the last adjoint launch ran. */
+ * pd_last_launch_info(m, PD_LAUNCH_INFO_PARENT_FRAMES, out) tells whether the robot qualifies and what the last adjoint launch ran.
+ *
+ * Model facts.  A qualifying robot that also has no joint limit gains (joint_limit_ke = joint_limit_kd = 0 for the dof of every revolute joint), a FREE root joint
+ * with at least six bodies behind it and no body with more than four children -- Laikago -- takes, by default, the same kernels with these
+ * facts compiled in instead of tested in every step.  + PD_PFI_NO_FACTS (on top of any of the above): keep the kernels that test them.
+ * PD_PFI_GENERAL still forces the fully general kernels. */
 #define PD_PFI_GENERAL 4
 #define PD_PFI_SPECIALISED 8
+#define PD_PFI_NO_FACTS 16
 int pd_model_set_kernel_family(pd_model *m, int family);
 int pd_model_get_kernel_family(const pd_model *m, int *eligible);
 
@@ -663,7 +669,9 @@ float pd_last_kernel_ms(const pd_model *m, int kind);
 /* Launch geometry of the last rollout launch of `kind` on this model (bench.py reports it beside the roofline):
  * out[0] workgroups, out[1] threads per workgroup, out[2] dynamic LDS bytes per workgroup, out[3] envs per workgroup.
  * kind PD_LAUNCH_INFO_PARENT_FRAMES (see pd_model_set_kernel_family): out[0] 1 when the robot qualifies for the adjoint kernels of unrotated
- * parent-side joint frames, out[1] the setting (0 automatic, 1 general, 2 specialised), out[2] 1 when the last adjoint launch ran them, out[3] 0. */
+ * parent-side joint frames, out[1] the setting (0 automatic, 1 general, 2 specialised), out[2] 1 when the last adjoint launch ran them,
+ * out[3] the model facts: 1 when the robot qualifies for having them compiled in + 2 when PD_PFI_NO_FACTS is set + 4 when the last adjoint
+ * launch ran the kernels with the facts compiled in. */
 #define PD_LAUNCH_INFO_PARENT_FRAMES 2
 int pd_last_launch_info(const pd_model *m, int kind, int out[4]);
 

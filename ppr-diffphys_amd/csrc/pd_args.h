@@ -42,7 +42,13 @@ struct PdLaunchCfg {
   size_t lds;    // dynamic LDS bytes per workgroup
   int pji;       // adjoint of a revolute-only plain model: 1 = every parent-side joint frame has the identity rotation, and the launch takes the
                  // kernels compiled for that (k_rollout_bwd PJI) where the family has them; 0 = the general kernels
+  int facts;     // with pji: 1 = the model facts the PJI kernels can have compiled in hold as well (pd_host.hip model_facts), and the launch
+                 // takes the k_rollout_bwd FACTS instantiation
 };
+// PD_PJI_FACTS: the FACTS instantiations exist and qualifying models take them (make EXTRA=-DPD_PJI_FACTS=0 builds them out, for A/B timing)
+#ifndef PD_PJI_FACTS
+#define PD_PJI_FACTS 1
+#endif
 // Env groups per workgroup: as many as it takes to cover the batch with one workgroup per compute unit, at most PD_BWAVES.
 // A small batch (512 Laikago envs = 128 groups) then occupies 128 CUs with one group each instead of 32 CUs with four.
 inline int pd_groups_per_wg(int n_groups, int cu_count) {

@@ -571,18 +571,24 @@ PD_DEV bool contact_point_adj_materials(const float *r, float4 cv, float4 P, flo
 
 // ---------------------------------------------------------------------------------------------
 // Joint PD + attachment forces for joint i == child body i (integrator_euler.py:289-451).
+// NOLIM (here and in joint_force_adj): the caller promises lke = lkd = 0 for every joint the call is made for (pd_host.hip model_facts) --
+// the limit force is identically zero and its tests and products are left out.
+template <bool NOLIM = false>
 PD_DEV float joint_force(float q, float qd, float target, float ke, float kd, float act, float lo, float up, float lke,
                          float lkd) {
+  if constexpr (NOLIM) return ke * (q - target) + kd * qd + act;
   float limit_f = 0.0f;  // :274-281
   if (q < lo) limit_f = lke * (lo - q) - lkd * fminf(qd, 0.0f);
   if (q > up) limit_f = lke * (up - q) - lkd * fmaxf(qd, 0.0f);
   return ke * (q - target) + kd * qd + act - limit_f;  // :284
 }
+template <bool NOLIM = false>
 PD_DEV void joint_force_adj(float q, float qd, float target, float ke, float kd, float lo, float up, float lke, float lkd,
                             float g, float &adj_q, float &adj_qd, float &adj_target, float &adj_ke, float &adj_kd,
                             float &adj_act) {
   adj_ke += g * (q - target); adj_q += g * ke; adj_target += -g * ke;
   adj_kd += g * qd; adj_qd += g * kd; adj_act += g;
+  if constexpr (NOLIM) return;
   // the limit force's adjoint (:274-281) as selects -- the same sums (x + 0 is x), no divergent region: the nested conditionals compiled to
   // two taken branches per dof on a wave whose instruction stream is its run time (round 6)
   const float adj_limit = -g;
@@ -962,8 +968,8 @@ PD_DEV RevCache rev_cache_load(const float *d) {
 // PJI (here, in rev_adjoint_core and in rev_adjoint): the caller promises a PLAIN model whose parent-side joint frames all have the
 // identity rotation, q_pj bitwise (0, 0, 0, 1) -- a property of the model (Laikago's), decided on the host (pd_host.hip
 // parent_frames_identity).  q_p = qp (x) q_pj is then qp for every finite qp, and what the general code spends on the product and on its
-// adjoint is left out; PJI = false is the general code as it was.
-template <bool HP = false, bool PJI = false>
+// adjoint is left out; PJI = false is the general code as it was.  NOLIM: see joint_force.
+template <bool HP = false, bool PJI = false, bool NOLIM = false>
 PD_DEV RevCache rev_forward(const PdDevModel &m, const BodyConst &c, qt q_c, v3 w_c, v3 pp, qt qp, v3 w_p, float tgt, float act, float ke,
                             float kd) {
   static_assert(!PJI || HP, "PJI: a plain model");
@@ -982,7 +988,7 @@ PD_DEV RevCache rev_forward(const PdDevModel &m, const BodyConst &c, qt q_c, v3 
   R.q = twist_angle(dot(qvec(R.r_err), c.axis), R.r_err.w, c.alen, R.dq_dda, R.dq_dw);
   R.qd = dot(w_c - w_p, R.axis_p);
   const JointLimit L = c.lim[0];
-  R.jf = joint_force(R.q, R.qd, tgt, ke, kd, act, L.lo, L.up, L.ke, L.kd);
+  R.jf = joint_force<NOLIM>(R.q, R.qd, tgt, ke, kd, act, L.lo, L.up, L.ke, L.kd);
   return R;
 }
 
@@ -990,7 +996,7 @@ PD_DEV RevCache rev_forward(const PdDevModel &m, const BodyConst &c, qt q_c, v3 
 // PJI (see rev_forward): q_p IS qp, so axis_p = rotm(qp) axis and its adjoint is one more outer product into the matrix adjoint aP that
 // rc_par and x_p already share (9 instructions for adj_qrot_q's ~46); what is left of adj_q_p, the r_err term, is added to par.r as it is
 // (no product with conj(q_pj), ~28); R.q_p is not read (qp of the parent's record has its bits); r_c = -rc_c exactly.
-template <bool HP = false, bool PJI = false>
+template <bool HP = false, bool PJI = false, bool NOLIM = false>
 PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, v3 pp, qt qp, v3 w_p, v3 v_p, v3 rc_par,
                              const RevCache &R, float tgt, float ke, float kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own, BodyAdj &par,
                              float *aR, float &a_tgt, float &a_act, float &a_ke, float &a_kd) {  // aR: matrix adjoint of rotm(s.r), see integrate_adj2
@@ -1022,7 +1028,7 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
   float adj_q = 0.f;
   a_tgt = 0.f; a_act = 0.f; a_ke = 0.f; a_kd = 0.f;
   const JointLimit L = c.lim[0];
-  joint_force_adj(R.q, R.qd, tgt, ke, kd, L.lo, L.up, L.ke, L.kd, adj_jf, adj_q, adj_qd, a_tgt, a_ke, a_kd, a_act);
+  joint_force_adj<NOLIM>(R.q, R.qd, tgt, ke, kd, L.lo, L.up, L.ke, L.kd, adj_jf, adj_q, adj_qd, a_tgt, a_ke, a_kd, a_act);
   adj_w_err += R.axis_p * adj_qd; adj_axis_p += w_err * adj_qd;
   const float adj_da = adj_q * R.dq_dda;
   adj_r_err.x += c.axis.x * adj_da; adj_r_err.y += c.axis.y * adj_da; adj_r_err.z += c.axis.z * adj_da;
@@ -1053,7 +1059,7 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
   }
 }
 
-template <bool HP = false, bool PJI = false>
+template <bool HP = false, bool PJI = false, bool NOLIM = false>
 PD_DEV void rev_adjoint(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, const float *rec, const RevCache &R,
                         float tgt, float ke, float kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own, BodyAdj &par, float *aR, float &a_tgt,
                         float &a_act, float &a_ke, float &a_kd) {
@@ -1063,7 +1069,7 @@ PD_DEV void rev_adjoint(const PdDevModel &m, const BodyConst &c, const BodyState
     const float *r = rec + (HP ? c.pidx : c.parent) * PD_REC;  // (pidx: the call may run for a lane without a joint, see the CLONE kernels)
     pp = ld3(r); qp = ld4(r + 3); w_p = ld3(r + 7); v_p = ld3(r + 10); rc_par = ld3(r + 13);
   }
-  rev_adjoint_core<HP, PJI>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt, a_act, a_ke, a_kd);
+  rev_adjoint_core<HP, PJI, NOLIM>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt, a_act, a_ke, a_kd);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -37,6 +37,11 @@ struct pd_model {
   // unless the model qualifies)
   bool parent_frames_identity = false;
   int pfi_mode = 0;
+  // model_facts: such a model that also has no joint limit gains, a FREE root with at least six bodies behind it and no body with more than
+  // four children (build_device) -- its PJI kernels have these facts compiled in (k_rollout_bwd FACTS).  no_facts
+  // (pd_model_set_kernel_family + PD_PFI_NO_FACTS, tests and A/B timing): keep the PJI kernels that test them at run time
+  bool model_facts = false;
+  bool no_facts = false;
   void *blob = nullptr;
   PdDevModel dev{};
   size_t lds_max = 0;  // what the kernels' dynamic-LDS attribute is at least set to
@@ -53,6 +58,7 @@ struct pd_model {
   bool ev_valid[2] = {false, false};
   int last_launch[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   int last_pji = 0;  // the last adjoint launch ran the kernels of unrotated parent frames
+  int last_facts = 0;  // ... with the model facts compiled in
 };
 
 // kd-order: recursively split along the longest axis so that runs of `leaf` consecutive points are compact
@@ -325,6 +331,18 @@ static bool parent_frames_identity(const pd_model *m, int jt) {
   return true;
 }
 
+// What the PJI kernels test in every step although the model fixes it (k_rollout_bwd FACTS compiles it in): no joint has limit gains, the
+// root is a FREE joint with at least six bodies behind it, no body has more than four children.  Like parent_frames_identity a property
+// of the template; a launch takes the FACTS kernels only where it takes the PJI kernels at all (plan_launch: no per-env joint_X_p).
+// (Limit gains: those of the revolute joints' dofs.  PdDevModel::has_limits looks at every dof, and Laikago's template carries gains on the six
+// dofs of its FREE root, which no kernel reads -- a FREE joint has no joint force.)
+static bool model_facts(const pd_model *m, const PdDevModel &d) {
+  if (!PD_PJI_FACTS || !m->parent_frames_identity || m->jtype[0] != PD_JOINT_FREE || m->nb < 7 || d.max_children > 4) return false;
+  for (int i = 0; i < m->nb; ++i)
+    if (m->jtype[i] == PD_JOINT_REVOLUTE && (m->lim_ke[m->qdstart[i]] != 0.f || m->lim_kd[m->qdstart[i]] != 0.f)) return false;
+  return true;
+}
+
 // Builds the device copy for segment width `segw` into temporaries and commits blob / dev / lds_* / segw / jt only when
 // every check has passed: a failed call leaves the model exactly as it was.
 // global_tables: the contact tables stay in global memory and only the per-env part of a workgroup's LDS has to fit -- for the
@@ -378,6 +396,7 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
   m->lds_tables = lds_tables; m->lds_max = (size_t)lds_max;
   m->segw = segw; m->jt = ch.jt; m->contact_order = t.order;
   m->parent_frames_identity = parent_frames_identity(m, ch.jt);
+  m->model_facts = model_facts(m, d);
   return 0;
 }
 
@@ -446,6 +465,7 @@ static LaunchPlan plan_launch(const pd_model *m, int kind, int n_envs, bool loss
   // the adjoint of a model with unrotated parent-side joint frames: the lane-per-body family has kernels for it (a joint_X_p bound per env
   // is device data the host has not seen: such a launch keeps the general kernels)
   c.pji = kind == PD_K_ROLLOUT_BWD && !quad && m->parent_frames_identity && m->pfi_mode != 1 && !m->xp_env ? 1 : 0;
+  c.facts = c.pji && m->model_facts && !m->no_facts ? 1 : 0;
   finish_cfg(c, d, n_groups, epw, d.global_tables ? 0 : (quad ? m->quad->lds_tables : m->lds_tables), 0, 0);
   return LaunchPlan{c, &d, jt, rollout && m->policy == PD_NUM_LITERAL ? 1 : 0, width_index(segw), {c.nblocks, c.threads, (int)c.lds, c.groups * epw}};
 }
@@ -454,7 +474,7 @@ static hipError_t launch(const pd_model *m, int kind, const void *args, int n_en
   const LaunchPlan p = plan_launch(m, kind, n_envs, kind == PD_K_ROLLOUT_FWD && ((const RolloutArgs *)args)->loss_target != nullptr);
   if (p.cfg.nblocks == 0) return hipSuccess;
   if (kind <= PD_K_ROLLOUT_BWD) std::copy(p.info, p.info + 4, const_cast<pd_model *>(m)->last_launch[kind]);
-  if (kind == PD_K_ROLLOUT_BWD) const_cast<pd_model *>(m)->last_pji = p.cfg.pji;
+  if (kind == PD_K_ROLLOUT_BWD) { const_cast<pd_model *>(m)->last_pji = p.cfg.pji; const_cast<pd_model *>(m)->last_facts = p.cfg.facts; }
   return g_launch[p.policy][p.wi](kind, p.jt, *p.dev, args, p.cfg, st);
 }
 
@@ -568,19 +588,20 @@ int pd_model_set_segment_width(pd_model *m, int lanes) {
 }
 
 // family: the kernel family (0 .. 2) + PD_PFI_GENERAL / PD_PFI_SPECIALISED (the header); a plain 0 .. 2 puts the parent-frame choice
-// back to automatic
+// back to automatic.  + PD_PFI_NO_FACTS: a qualifying model keeps the PJI kernels without its facts compiled in (model_facts)
 int pd_model_set_kernel_family(pd_model *m, int family) {
   if (!m) return fail("null model");
-  const int fam = family & 3, mode = family >> 2;
-  if (family < 0 || fam > 2 || mode > 2) return fail("kernel family: 0 automatic, 1 lane per body, 2 quad-lane where eligible (+ PD_PFI_GENERAL or PD_PFI_SPECIALISED)");
+  const int fam = family & 3, mode = (family >> 2) & 3;
+  if (family < 0 || family >= 2 * PD_PFI_NO_FACTS || fam > 2 || mode > 2)
+    return fail("kernel family: 0 automatic, 1 lane per body, 2 quad-lane where eligible (+ PD_PFI_GENERAL or PD_PFI_SPECIALISED, + PD_PFI_NO_FACTS)");
   if (mode == 2 && !m->parent_frames_identity)
     return fail("PD_PFI_SPECIALISED: the model does not qualify (revolute-only plain model whose parent-side joint frames all have the rotation (0, 0, 0, 1))");
-  m->family = fam; m->pfi_mode = mode;
+  m->family = fam; m->pfi_mode = mode; m->no_facts = (family & PD_PFI_NO_FACTS) != 0;
   return 0;
 }
 int pd_model_get_kernel_family(const pd_model *m, int *eligible) {
   if (eligible) *eligible = (m && m->quad) ? 1 : 0;
-  return m ? m->family | (m->pfi_mode << 2) : 0;
+  return m ? m->family | (m->pfi_mode << 2) | (m->no_facts ? PD_PFI_NO_FACTS : 0) : 0;
 }
 int pd_model_set_numeric_policy(pd_model *m, int policy) {
   if (!m) return fail("null model");
@@ -909,7 +930,8 @@ float pd_last_kernel_ms(const pd_model *m, int kind) {
 int pd_last_launch_info(const pd_model *m, int kind, int out[4]) {
   if (!m || !out || kind < 0 || kind > PD_LAUNCH_INFO_PARENT_FRAMES) return fail("bad argument");
   if (kind == PD_LAUNCH_INFO_PARENT_FRAMES) {
-    out[0] = m->parent_frames_identity ? 1 : 0; out[1] = m->pfi_mode; out[2] = m->last_pji; out[3] = 0;
+    out[0] = m->parent_frames_identity ? 1 : 0; out[1] = m->pfi_mode; out[2] = m->last_pji;
+    out[3] = (m->model_facts ? 1 : 0) | (m->no_facts ? 2 : 0) | (m->last_facts ? 4 : 0);
     return 0;
   }
   for (int k = 0; k < 4; ++k) out[k] = m->last_launch[kind][k];

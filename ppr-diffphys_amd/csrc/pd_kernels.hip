@@ -1537,10 +1537,15 @@ __device__ __forceinline__ bool grad_wanted(const float *g) {
 
 // PJI: every parent-side joint frame of the model has the identity rotation (pd_device.h rev_forward; the host's plan says so per launch:
 // PdLaunchCfg::pji).  Lane-per-body family only: the quad-lane body wave keeps the general joint code.
-template <int SEGW, int JT, bool QUAD = false, bool SEL = false, bool PJI = false>
+// FACTS (with PJI only; PdLaunchCfg::facts, pd_host.hip model_facts): what the step loop otherwise tests at run time although the model fixes
+// it is compiled in -- no revolute joint has limit gains (the limit terms of joint_force and joint_force_adj go, on both waves), the root is a FREE
+// joint with at least six bodies behind it (its six zero control-gradient columns are written by lanes 1 .. 6, the per-lane store block of a
+// FREE body goes), no body has more than four children (the further-children gather goes).
+template <int SEGW, int JT, bool QUAD = false, bool SEL = false, bool PJI = false, bool FACTS = false>
 __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutArgs a) {
   static_assert(JT == PD_JT_REVOLUTE, "the wave-specialised adjoint of revolute-only plain models: every jointed body is a revolute joint on a parent body");
   static_assert(!(QUAD && PJI), "PJI: lane-per-body family only");
+  static_assert(!FACTS || PJI, "FACTS: instantiated together with PJI only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
   const int bw = (int)blockDim.x / (QUAD ? 192 : 128);  // env groups per workgroup (host's choice per launch)
@@ -1734,7 +1739,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
         const qt q_c = Q4(pose[0].x, pose[0].y, pose[0].z, pose[0].w), qp = Q4(pose[2].x, pose[2].y, pose[2].z, pose[2].w);
         const v3 w_c = V3(pose[1].x, pose[1].y, pose[1].z), pp = V3(pose[4].x, pose[4].y, pose[4].z), w_p = V3(pose[3].x, pose[3].y, pose[3].z);
         float *dst = jc + (step & 1) * m.env_lds_jc + b * PD_JC;
-        rev_cache_store(dst, rev_forward<true, PJI>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
+        rev_cache_store(dst, rev_forward<true, PJI, FACTS>(m, c, q_c, w_c, pp, qp, w_p, tgt_c, act_c, ke1, kd1));
       }
       STAMP(8);
       // request everything the next iteration needs; nothing loaded here is touched before the next PD_WAIT_VMEM
@@ -2111,7 +2116,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
 
   // The stored state, wrench and controls of the NEXT iteration (step - 1) are software-prefetched.
   const unsigned boff = (unsigned)idx * 4u, boff_qd = (unsigned)((size_t)ec * m.nqd + c.qdstart) * 4u;  // per-lane byte offsets
-  const bool zero_by_lanes = m.jtype[0] == PD_JOINT_FREE && nb >= 7;  // see the control-gradient stores below
+  const bool zero_by_lanes = FACTS || (m.jtype[0] == PD_JOINT_FREE && nb >= 7);  // see the control-gradient stores below
   const unsigned boff_zero = (unsigned)((size_t)ec * m.nqd + m.qdstart[0] + (b >= 1 && b <= 6 ? b - 1 : 0)) * 4u;
   float4 n_s[PD_TRAJ_G];
   float n_tgt[ND];  // (the applied torque enters this wave's adjoint through the contact wave's hand-over record only)
@@ -2184,7 +2189,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       const v3 gp_t = ld3(adjf + c.parent * PD_W6), gp_f = ld3(adjf + c.parent * PD_W6 + 3);  // (plain model: every jointed body hangs on one)
       // the state-only half comes from the contact wave
       const RevCache R = rev_cache_load(jc + (step & 1) * m.env_lds_jc + b * PD_JC);
-      rev_adjoint<true, PJI>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
+      rev_adjoint<true, PJI, FACTS>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
     }
     rotm_adj(s.r, aR, ga.r);
     if (is_body) {
@@ -2205,7 +2210,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
           if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc, boff_zero, 0.f);
           if (grad_wanted<SEL>(a.g_torques)) stg(a.g_torques + oc, boff_zero, 0.f);
         }
-      } else if (c.type == PD_JOINT_FREE) {
+      } else if (!FACTS && c.type == PD_JOINT_FREE) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
           if (grad_wanted<SEL>(a.g_refs)) stg(a.g_refs + oc + k, boff_qd, 0.f);
@@ -2219,9 +2224,11 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       const float *const src[4] = {cslot + cz[0] * PD_ADJ, cslot + cz[1] * PD_ADJ, cslot + cz[2] * PD_ADJ, cslot + cz[3] * PD_ADJ};
       adj_add_from_n(ga, src);
     }
-    for (int k = 4; k < m.max_children; ++k) {
-      int cid = (int)((c.children >> (8 * k)) & 0xffull);
-      if (is_body && cid != 0xff) adj_add_from(ga, cslot + cid * PD_ADJ);
+    if constexpr (!FACTS) {
+      for (int k = 4; k < m.max_children; ++k) {
+        int cid = (int)((c.children >> (8 * k)) & 0xffull);
+        if (is_body && cid != 0xff) adj_add_from(ga, cslot + cid * PD_ADJ);
+      }
     }
     STAMP(3);
     pair_wait(sig + 2, a.nsteps - step);  // B: contact adjoints are complete
@@ -2809,13 +2816,17 @@ static RolloutKernel select_fwd(int kernel, int roles, bool runsum, bool loss) {
 // k_rollout_bwd<SEGW, JT, QUAD, SEL, PJI> for revolute-only robots, k_rollout_bwd3<SEGW, JT, GT, SEL> for every other joint mix
 // pji: the plan's promise that the model's parent-side joint frames are unrotated (PdLaunchCfg::pji) -- the lane-per-body kernel then has a
 // PJI instantiation; the quad-lane kernel and k_rollout_bwd3 are the same kernels either way
+// facts (with pji only: PdLaunchCfg::facts): the PJI kernel with the model's facts compiled in (k_rollout_bwd FACTS)
 template <int JT, bool GT, bool SEL>
-static RolloutKernel select_bwd(int kernel, bool pji) {
+static RolloutKernel select_bwd(int kernel, bool pji, bool facts) {
   if constexpr (pd_split(JT)) {
     if (kernel == PD_KV_BWD_QUAD) {
       if constexpr (PD_SEGW == 64) return k_rollout_bwd<PD_SEGW, JT, true, SEL>;
       else return nullptr;
     }
+#if PD_PJI_FACTS
+    if (pji && facts) return k_rollout_bwd<PD_SEGW, JT, false, SEL, true, true>;
+#endif
     return pji ? k_rollout_bwd<PD_SEGW, JT, false, SEL, true> : k_rollout_bwd<PD_SEGW, JT, false, SEL>;
   } else {
     return k_rollout_bwd3<PD_SEGW, JT, GT, SEL>;
@@ -2833,7 +2844,7 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
 }
 template <int JT, bool GT, bool SEL>
 static hipError_t launch_bwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
-  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel, cfg.pji != 0), m, a, cfg, st);
+  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel, cfg.pji != 0, cfg.facts != 0), m, a, cfg, st);
 }
 
 template <int JT, bool GT>
@@ -2890,8 +2901,8 @@ static hipError_t set_lds_fwd(int bytes) {
 template <int JT, bool GT, bool SEL>
 static hipError_t set_lds_bwd(int bytes) {
   for (const int kernel : kBwdVariants)
-    for (int pji = 0; pji < 2; ++pji)
-      if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel, pji != 0), bytes)) return e;
+    for (int pji = 0; pji < 3; ++pji)  // (2: PJI with the model facts)
+      if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel, pji != 0, pji == 2), bytes)) return e;
   return hipSuccess;
 }
 

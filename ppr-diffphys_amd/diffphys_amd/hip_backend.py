@@ -79,6 +79,25 @@ def parent_frames_identity(tpl):
     return bool((rot("joint_X_p").view(np.uint32)[jointed] == one).all())
 
 
+def model_facts(tpl):
+    """The library's test (csrc/pd_host.hip model_facts) on a template dict, without a device: a robot that passes parent_frames_identity
+    and also has no joint limit gains, a FREE root joint with at least six bodies behind it and no body with more than four children.
+    Its lane-per-body adjoint takes the kernels with these facts compiled in (DeviceModel.set_model_facts;
+    DeviceModel.model_facts_info() is the library's own answer)."""
+    if not parent_frames_identity(tpl):
+        return False
+    nb = int(tpl["nb"])
+    ty = np.asarray(tpl["joint_type"]).reshape(-1)
+    par = np.asarray(tpl["joint_parent"]).reshape(-1)
+    # limit gains of the revolute joints' dofs (Laikago's template carries gains on the six dofs of its FREE root, which no kernel reads)
+    dofs = np.asarray(tpl["joint_qd_start"]).reshape(-1)[:nb][ty == 1]
+    if (np.asarray(tpl["joint_limit_ke"], np.float32).reshape(-1)[dofs] != 0).any() or (np.asarray(tpl["joint_limit_kd"], np.float32).reshape(-1)[dofs] != 0).any():
+        return False
+    if int(ty[0]) != 4 or nb < 7:   # (4: FREE)
+        return False
+    return int(np.bincount(par[par >= 0], minlength=nb).max()) <= 4
+
+
 class _Desc(ctypes.Structure):
     _fields_ = [
         ("nb", ctypes.c_int), ("nq", ctypes.c_int), ("nqd", ctypes.c_int), ("nc", ctypes.c_int), ("nmat", ctypes.c_int),
@@ -276,7 +295,7 @@ class DeviceModel:
         self.h = h
         self._xp = None
         self._nc_keep = keep["contact_body"]
-        self._family, self._pfi = 0, 0
+        self._family, self._pfi, self._nofacts = 0, 0, 0
 
     def __del__(self):
         try:
@@ -294,7 +313,7 @@ class DeviceModel:
 
     def set_kernel_family(self, family):
         """0 automatic (by batch size), 1 lane per body always, 2 quad-lane (four lanes per body) wherever the robot is eligible."""
-        _check(lib().pd_model_set_kernel_family(self.h, int(family) + 4 * self._pfi))
+        _check(lib().pd_model_set_kernel_family(self.h, int(family) + 4 * self._pfi + 16 * self._nofacts))
         self._family = int(family)
 
     def set_parent_frame_identity(self, mode):
@@ -303,8 +322,23 @@ class DeviceModel:
         ones (raises unless the robot qualifies).  For tests and A/B timing; rides on ``pd_model_set_kernel_family``."""
         if int(mode) not in (0, 1, 2):
             raise ValueError("parent frame identity mode: 0 automatic, 1 general, 2 specialised")
-        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * int(mode)))
+        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * int(mode) + 16 * self._nofacts))
         self._pfi = int(mode)
+
+    def set_model_facts(self, on):
+        """True (default): a robot that qualifies (hip_backend.model_facts -- Laikago) runs its lane-per-body adjoint on the kernels with its
+        facts compiled in (no joint limits, FREE root with six bodies behind it, at most four children).  False: the same kernels with the
+        facts tested at run time (PD_PFI_NO_FACTS).  For tests and A/B timing; rides on ``pd_model_set_kernel_family``."""
+        nofacts = 0 if on else 1
+        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * self._pfi + 16 * nofacts))
+        self._nofacts = nofacts
+
+    def model_facts_info(self):
+        """dict(qualifies, disabled, last_launch): the library's own model_facts answer for this robot, whether set_model_facts(False) holds,
+        and whether the last adjoint launch ran the kernels with the facts compiled in."""
+        out = (ctypes.c_int * 4)()
+        _check(lib().pd_last_launch_info(self.h, 2, ctypes.byref(out)))
+        return dict(qualifies=bool(out[3] & 1), disabled=bool(out[3] & 2), last_launch=bool(out[3] & 4))
 
     def parent_frames_identity(self):
         """True when the library found every parent-side joint frame of this revolute-only robot unrotated (see set_parent_frame_identity)."""

@@ -80,7 +80,7 @@ N_SIMD = 1024  # 256 CUs x 4
 # rate of the v_pk_fma_f32 the SLP vectoriser had made of that microbenchmark, per FMA)
 VALU_CYC = 4.2
 lines = ["# rocprofv3 summary `%s` (bench.py %s, 1x MI355X)\n" % (tag, cmd),
-         "Source: `scripts/profile_gpu.sh %s` on the GPU box; raw csv under `gpurun_out/prof_%s/` (scratch)." % (tag, tag), ""]
+         "Source: `scripts/profile_gpu.sh %s` on an MI355X; raw csv in the run's output directory `prof_%s/` (scratch, not committed)." % (tag, tag), ""]
 for k in ("k_rollout_fwd", "k_rollout_bwd"):
     if k not in avg_ns:
         continue
