@@ -101,10 +101,15 @@ int pd_model_get_segment_width(const pd_model *m);
  * Model facts.  A qualifying robot that also has no joint limit gains (joint_limit_ke = joint_limit_kd = 0 for the dof of every revolute joint), a FREE root joint
  * with at least six bodies behind it and no body with more than four children -- Laikago -- takes, by default, the same kernels with these
  * facts compiled in instead of tested in every step.  + PD_PFI_NO_FACTS (on top of any of the above): keep the kernels that test them.
- * PD_PFI_GENERAL still forces the fully general kernels. */
+ * PD_PFI_GENERAL still forces the fully general kernels.
+ *
+ * Com facts.  A robot with its model facts compiled in whose centres of mass (body_com, as fp32) all have x == 0 and y == 0, and are
+ * (0, 0, 0) for every body whose joint is not FREE -- Laikago again -- takes, by default, kernels that also leave out the products with those
+ * zeros.  + PD_PFI_NO_COM_FACTS: keep the kernels with the general centre-of-mass algebra.  (A non-finite state no longer meets 0 * x there.) */
 #define PD_PFI_GENERAL 4
 #define PD_PFI_SPECIALISED 8
 #define PD_PFI_NO_FACTS 16
+#define PD_PFI_NO_COM_FACTS 32
 int pd_model_set_kernel_family(pd_model *m, int family);
 int pd_model_get_kernel_family(const pd_model *m, int *eligible);
 
@@ -671,7 +676,8 @@ float pd_last_kernel_ms(const pd_model *m, int kind);
  * kind PD_LAUNCH_INFO_PARENT_FRAMES (see pd_model_set_kernel_family): out[0] 1 when the robot qualifies for the adjoint kernels of unrotated
  * parent-side joint frames, out[1] the setting (0 automatic, 1 general, 2 specialised), out[2] 1 when the last adjoint launch ran them,
  * out[3] the model facts: 1 when the robot qualifies for having them compiled in + 2 when PD_PFI_NO_FACTS is set + 4 when the last adjoint
- * launch ran the kernels with the facts compiled in. */
+ * launch ran the kernels with the facts compiled in; the com facts in the same way: + 8 when the robot qualifies, + 16 when
+ * PD_PFI_NO_COM_FACTS is set, + 32 when the last adjoint launch ran the kernels with them compiled in. */
 #define PD_LAUNCH_INFO_PARENT_FRAMES 2
 int pd_last_launch_info(const pd_model *m, int kind, int out[4]);
 

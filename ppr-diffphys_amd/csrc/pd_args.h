@@ -44,10 +44,15 @@ struct PdLaunchCfg {
                  // kernels compiled for that (k_rollout_bwd PJI) where the family has them; 0 = the general kernels
   int facts;     // with pji: 1 = the model facts the PJI kernels can have compiled in hold as well (pd_host.hip model_facts), and the launch
                  // takes the k_rollout_bwd FACTS instantiation
+  int com;       // with facts: 1 = the model's com facts hold too (pd_host.hip com_facts), and the launch takes the k_rollout_bwd COM instantiation
 };
 // PD_PJI_FACTS: the FACTS instantiations exist and qualifying models take them (make EXTRA=-DPD_PJI_FACTS=0 builds them out, for A/B timing)
 #ifndef PD_PJI_FACTS
 #define PD_PJI_FACTS 1
+#endif
+// PD_COM_FACTS: the same for the COM instantiations (make EXTRA=-DPD_COM_FACTS=0)
+#ifndef PD_COM_FACTS
+#define PD_COM_FACTS 1
 #endif
 // Env groups per workgroup: as many as it takes to cover the batch with one workgroup per compute unit, at most PD_BWAVES.
 // A small batch (512 Laikago envs = 128 groups) then occupies 128 CUs with one group each instead of 32 CUs with four.

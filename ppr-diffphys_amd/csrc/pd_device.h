@@ -400,18 +400,23 @@ PD_DEV bool contact_point_fwd(const float *r, float4 cv, float4 P, float4 mat, C
 // (pd_math.h: rotm).  Measured: -2.3 % adjoint time where the contacts run inline on the integrate wave (quad 8192), +3 % on the
 // revolute kernel's contact wave (Laikago 4096) -- so the caller chooses.
 // cv = the body's cull vector as staged (p_y, row 1 of rotm(q)): the height, and with it "touching", is the forward pass's bit for bit.
-template <bool MAT = false>
+// COMZ (quaternion form only): the caller promises that every body's com lies on its z axis (pd_host.hip com_facts) -- only its z component
+// is recovered from the staged rc (x and y ARE zero; the general code recovers them as rounding residue, ~1e-9) and its rotation's adjoint
+// takes the z form (pd_math.h).
+template <bool MAT = false, bool COMZ = false>
 PD_DEV bool contact_point_adj(const float *r, float4 cv, float4 P, float4 mat, v3 g_t, v3 g_f, BodyAdj &out) {
   v3 p = ld3(r), w = ld3(r + 7), v = ld3(r + 10), rc = ld3(r + 13);
   qt q = ld4(r + 3);
   float M[9];
+  static_assert(!(MAT && COMZ), "COMZ: quaternion form only");
   v3 cpt = V3(P.x, P.y, P.z), com, cp;
   if (MAT) {
     rotm(q, M);
     com = matT_vec(M, rc);
     cp = (p + mat_vec(M, cpt)) - V3(0.f, P.w, 0.f);
   } else {
-    com = qrot_inv(q, rc);  // body-frame COM back from the staged rc = rot(q, com): no table read on the hit path
+    if constexpr (COMZ) com = V3(0.f, 0.f, qrot_inv_z(q, rc));
+    else com = qrot_inv(q, rc);  // body-frame COM back from the staged rc = rot(q, com): no table read on the hit path
     cp = (p + qrot(q, cpt)) - V3(0.f, P.w, 0.f);
   }
   cp.y = contact_height(cv, P);  // the height decides "touching": exactly the forward pass's arithmetic
@@ -460,7 +465,8 @@ PD_DEV bool contact_point_adj(const float *r, float4 cv, float4 P, float4 mat, v
     add_outer(aM, adj_cp, cpt);
     rotm_adj(q, aM, adj_q);
   } else {
-    adj_qrot_q(q, com, adj_q, -adj_r);
+    if constexpr (COMZ) adj_qrot_q_z(q, com.z, adj_q, -adj_r);
+    else adj_qrot_q(q, com, adj_q, -adj_r);
     adj_qrot_q(q, cpt, adj_q, adj_cp);
   }
   out.p = adj_cp - adj_r;
@@ -996,7 +1002,10 @@ PD_DEV RevCache rev_forward(const PdDevModel &m, const BodyConst &c, qt q_c, v3 
 // PJI (see rev_forward): q_p IS qp, so axis_p = rotm(qp) axis and its adjoint is one more outer product into the matrix adjoint aP that
 // rc_par and x_p already share (9 instructions for adj_qrot_q's ~46); what is left of adj_q_p, the r_err term, is added to par.r as it is
 // (no product with conj(q_pj), ~28); R.q_p is not read (qp of the parent's record has its bits); r_c = -rc_c exactly.
-template <bool HP = false, bool PJI = false, bool NOLIM = false>
+// COMZ (with PJI; pd_host.hip com_facts): every com lies on its body's z axis and that of a jointed body -- every body this runs for -- is
+// (0, 0, 0).  r_c is then exactly zero: its cross product with f_total adds zeros to adj_f, and adj_r_c, which only ever met com, is not
+// formed; the parent's com (the trunk's, or zero) enters aP through its z component alone.
+template <bool HP = false, bool PJI = false, bool NOLIM = false, bool COMZ = false>
 PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, v3 pp, qt qp, v3 w_p, v3 v_p, v3 rc_par,
                              const RevCache &R, float tgt, float ke, float kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own, BodyAdj &par,
                              float *aR, float &a_tgt, float &a_act, float &a_ke, float &a_kd) {  // aR: matrix adjoint of rotm(s.r), see integrate_adj2
@@ -1008,12 +1017,13 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
     pp = V3(0, 0, 0); w_p = pp; v_p = pp; qp = Q4(0, 0, 0, 1);
   }
   static_assert(!PJI || HP, "PJI: a plain model");
+  static_assert(!COMZ || PJI, "COMZ: with PJI only");
   const qt q_p = PJI ? qp : R.q_p;
   const v3 r_c = PJI ? -rc_c : s.p - (s.p + rc_c);
   const v3 x_err = s.p - R.x_p, v_err = s.v - v_p, w_err = s.w - w_p;
   const v3 f_total = x_err * ake + v_err * akd;
   v3 adj_t = -gc_t, adj_f = -gc_f, adj_r_c = V3(0, 0, 0), adj_r_p = V3(0, 0, 0);
-  adj_cross(r_c, f_total, adj_r_c, adj_f, -gc_t);
+  if constexpr (!COMZ) adj_cross(r_c, f_total, adj_r_c, adj_f, -gc_t);
   if (HP || c.parent >= 0) {
     adj_t += gp_t; adj_f += gp_f;
     adj_cross(r_p, f_total, adj_r_p, adj_f, gp_t);
@@ -1040,7 +1050,7 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
     adj_qmul(qconj(q_p), s.r, adj_cqp, adj_q_c, adj_r_err);
     adj_q_p += qconj(adj_cqp);
   }
-  add_outer(aR, -adj_r_c, c.com);     // rc_c = rotm(s.r) com
+  if constexpr (!COMZ) add_outer(aR, -adj_r_c, c.com);     // rc_c = rotm(s.r) com
   own.p += adj_x_err; own.r += adj_q_c; own.w += adj_w_err; own.v += adj_v_err;
   par = adj_zero();
   if (HP || c.parent >= 0) {
@@ -1049,7 +1059,8 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
     float aP[9];  // matrix adjoint of rotm(qp): rc_par = rotm(qp) com_par, x_p = pp + rotm(qp) p_pj
 #pragma unroll
     for (int k = 0; k < 9; ++k) aP[k] = 0.f;
-    add_outer(aP, -adj_r_p, c.com_par);
+    if constexpr (COMZ) add_outer_z(aP, -adj_r_p, c.com_par.z);
+    else add_outer(aP, -adj_r_p, c.com_par);
     add_outer(aP, adj_x_p, c.p_pj);
     if constexpr (PJI) add_outer(aP, adj_axis_p, c.axis);  // axis_p = rotm(qp) axis
     rotm_adj(qp, aP, par.r);
@@ -1059,7 +1070,7 @@ PD_DEV void rev_adjoint_core(const PdDevModel &m, const BodyConst &c, const Body
   }
 }
 
-template <bool HP = false, bool PJI = false, bool NOLIM = false>
+template <bool HP = false, bool PJI = false, bool NOLIM = false, bool COMZ = false>
 PD_DEV void rev_adjoint(const PdDevModel &m, const BodyConst &c, const BodyState &s, v3 rc_c, const float *rec, const RevCache &R,
                         float tgt, float ke, float kd, v3 gc_t, v3 gc_f, v3 gp_t, v3 gp_f, BodyAdj &own, BodyAdj &par, float *aR, float &a_tgt,
                         float &a_act, float &a_ke, float &a_kd) {
@@ -1069,7 +1080,7 @@ PD_DEV void rev_adjoint(const PdDevModel &m, const BodyConst &c, const BodyState
     const float *r = rec + (HP ? c.pidx : c.parent) * PD_REC;  // (pidx: the call may run for a lane without a joint, see the CLONE kernels)
     pp = ld3(r); qp = ld4(r + 3); w_p = ld3(r + 7); v_p = ld3(r + 10); rc_par = ld3(r + 13);
   }
-  rev_adjoint_core<HP, PJI, NOLIM>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt, a_act, a_ke, a_kd);
+  rev_adjoint_core<HP, PJI, NOLIM, COMZ>(m, c, s, rc_c, pp, qp, w_p, v_p, rc_par, R, tgt, ke, kd, gc_t, gc_f, gp_t, gp_f, own, par, aR, a_tgt, a_act, a_ke, a_kd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1141,7 +1152,9 @@ PD_DEV void add_outer(LdsAcc9 M, v3 a, v3 b) {
 // PURE: the two quaternion products with W = (w1, 0) as qmul_pure (pd_math.h), without the four products with the zero -- rq then has the
 // bits the LEAN forward pass (integrate_bodies) gave it.  Set by the adjoint kernels that are compiled anew anyway (k_rollout_bwd PJI); the
 // others keep their instruction streams.
-template <bool PURE = false, typename ACC, typename F>
+// COMZ (pd_host.hip com_facts): c.com lies on the body's z axis -- the adjoint of rot(r1, com) and the outer product with com take their
+// z forms (pd_math.h).
+template <bool PURE = false, bool COMZ = false, typename ACC, typename F>
 PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodyState &s, const float *Rm, unsigned clamp_mask, v3 t0, v3 f0, float inv_m,
                            const float *I, const float *invI, float dt, const BodyAdj &gn, BodyAdj &a, float *aR, float &g_inv_m, ACC g_I,
                            ACC g_invI, F &&wrench_ready) {
@@ -1158,7 +1171,8 @@ PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodySt
   qt r1 = qnormalize(rq);
   // ---- reverse, phase 1: the path to the wrench adjoint
   qt adj_r1 = gn.r;
-  adj_qrot_q(r1, c.com, adj_r1, -gn.p);
+  if constexpr (COMZ) adj_qrot_q_z(r1, c.com.z, adj_r1, -gn.p);
+  else adj_qrot_q(r1, c.com, adj_r1, -gn.p);
   // clamp adjoints: pass or block exactly as the forward pass clamped (its mask, integrate_fwd)
   v3 adj_v1 = V3((clamp_mask & 8u) ? 0.0f * gn.v.x : gn.v.x, (clamp_mask & 16u) ? 0.0f * gn.v.y : gn.v.y, (clamp_mask & 32u) ? 0.0f * gn.v.z : gn.v.z);
   v3 adj_w1 = V3((clamp_mask & 1u) ? 0.0f * gn.w.x : gn.w.x, (clamp_mask & 2u) ? 0.0f * gn.w.y : gn.w.y, (clamp_mask & 4u) ? 0.0f * gn.w.z : gn.w.z) *
@@ -1190,13 +1204,14 @@ PD_DEV void integrate_adj2(const PdDevModel &m, const BodyConst &c, const BodySt
   const v3 adj_w0 = mat_vec(Rm, adj_wb);
   add_outer(aR, s.w, adj_wb);  // wb = Rm^T w
   g_inv_m += dot(adj_v1, f0) * dt;
-  add_outer(aR, gn.p, c.com);  // x_com = p + Rm com
+  if constexpr (COMZ) add_outer_z(aR, gn.p, c.com.z);
+  else add_outer(aR, gn.p, c.com);  // x_com = p + Rm com
   a.p = gn.p; a.r = adj_r0; a.w = adj_w0; a.v = adj_v1;
 }
 
-template <bool PURE = false>
+template <bool PURE = false, bool COMZ = false>
 PD_DEV void integrate_adj(const PdDevModel &m, const BodyConst &c, const BodyState &s, const float *Rm, unsigned clamp_mask, v3 t0, v3 f0, float inv_m,
                           const float *I, const float *invI, float dt, const BodyAdj &gn, BodyAdj &a, float *aR, v3 &adj_t0, v3 &adj_f0,
                           float &g_inv_m, float *g_I, float *g_invI) {
-  integrate_adj2<PURE>(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, dt, gn, a, aR, g_inv_m, g_I, g_invI, [&](v3 t, v3 f) { adj_t0 = t; adj_f0 = f; });
+  integrate_adj2<PURE, COMZ>(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, dt, gn, a, aR, g_inv_m, g_I, g_invI, [&](v3 t, v3 f) { adj_t0 = t; adj_f0 = f; });
 }

@@ -42,6 +42,10 @@ struct pd_model {
   // (pd_model_set_kernel_family + PD_PFI_NO_FACTS, tests and A/B timing): keep the PJI kernels that test them at run time
   bool model_facts = false;
   bool no_facts = false;
+  // com_facts: such a model whose centres of mass all lie on their bodies' z axes, those of the jointed bodies at the origin (build_device;
+  // k_rollout_bwd COM).  no_com_facts (PD_PFI_NO_COM_FACTS): keep the FACTS kernels with the general com algebra
+  bool com_facts = false;
+  bool no_com_facts = false;
   void *blob = nullptr;
   PdDevModel dev{};
   size_t lds_max = 0;  // what the kernels' dynamic-LDS attribute is at least set to
@@ -59,6 +63,7 @@ struct pd_model {
   int last_launch[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   int last_pji = 0;  // the last adjoint launch ran the kernels of unrotated parent frames
   int last_facts = 0;  // ... with the model facts compiled in
+  int last_com = 0;    // ... and the com facts
 };
 
 // kd-order: recursively split along the longest axis so that runs of `leaf` consecutive points are compact
@@ -343,6 +348,19 @@ static bool model_facts(const pd_model *m, const PdDevModel &d) {
   return true;
 }
 
+// The com facts (k_rollout_bwd COM), on top of model_facts and on the fp32 values the device receives: Z -- every body's com has x == 0 and
+// y == 0; J0 -- the com of every body whose joint is not FREE is (0, 0, 0).  Laikago: (0, 0, 0.0438) for the trunk, zero for its twelve leg
+// bodies.  (-0.0f == 0: a negative zero qualifies, its products are the zeros the kernels leave out.)  com is given with the template and
+// has no setter and no per-env binding: decided here once per build_device, like the others.
+static bool com_facts(const pd_model *m) {
+  if (!PD_COM_FACTS || !m->model_facts) return false;
+  for (int i = 0; i < m->nb; ++i) {
+    const float *c = &m->com[3 * i];
+    if (c[0] != 0.f || c[1] != 0.f || (m->jtype[i] != PD_JOINT_FREE && c[2] != 0.f)) return false;
+  }
+  return true;
+}
+
 // Builds the device copy for segment width `segw` into temporaries and commits blob / dev / lds_* / segw / jt only when
 // every check has passed: a failed call leaves the model exactly as it was.
 // global_tables: the contact tables stay in global memory and only the per-env part of a workgroup's LDS has to fit -- for the
@@ -397,6 +415,7 @@ static int build_device(pd_model *m, int segw, bool global_tables) {
   m->segw = segw; m->jt = ch.jt; m->contact_order = t.order;
   m->parent_frames_identity = parent_frames_identity(m, ch.jt);
   m->model_facts = model_facts(m, d);
+  m->com_facts = com_facts(m);
   return 0;
 }
 
@@ -466,6 +485,7 @@ static LaunchPlan plan_launch(const pd_model *m, int kind, int n_envs, bool loss
   // is device data the host has not seen: such a launch keeps the general kernels)
   c.pji = kind == PD_K_ROLLOUT_BWD && !quad && m->parent_frames_identity && m->pfi_mode != 1 && !m->xp_env ? 1 : 0;
   c.facts = c.pji && m->model_facts && !m->no_facts ? 1 : 0;
+  c.com = c.facts && m->com_facts && !m->no_com_facts ? 1 : 0;
   finish_cfg(c, d, n_groups, epw, d.global_tables ? 0 : (quad ? m->quad->lds_tables : m->lds_tables), 0, 0);
   return LaunchPlan{c, &d, jt, rollout && m->policy == PD_NUM_LITERAL ? 1 : 0, width_index(segw), {c.nblocks, c.threads, (int)c.lds, c.groups * epw}};
 }
@@ -474,7 +494,7 @@ static hipError_t launch(const pd_model *m, int kind, const void *args, int n_en
   const LaunchPlan p = plan_launch(m, kind, n_envs, kind == PD_K_ROLLOUT_FWD && ((const RolloutArgs *)args)->loss_target != nullptr);
   if (p.cfg.nblocks == 0) return hipSuccess;
   if (kind <= PD_K_ROLLOUT_BWD) std::copy(p.info, p.info + 4, const_cast<pd_model *>(m)->last_launch[kind]);
-  if (kind == PD_K_ROLLOUT_BWD) { const_cast<pd_model *>(m)->last_pji = p.cfg.pji; const_cast<pd_model *>(m)->last_facts = p.cfg.facts; }
+  if (kind == PD_K_ROLLOUT_BWD) { const_cast<pd_model *>(m)->last_pji = p.cfg.pji; const_cast<pd_model *>(m)->last_facts = p.cfg.facts; const_cast<pd_model *>(m)->last_com = p.cfg.com; }
   return g_launch[p.policy][p.wi](kind, p.jt, *p.dev, args, p.cfg, st);
 }
 
@@ -588,20 +608,22 @@ int pd_model_set_segment_width(pd_model *m, int lanes) {
 }
 
 // family: the kernel family (0 .. 2) + PD_PFI_GENERAL / PD_PFI_SPECIALISED (the header); a plain 0 .. 2 puts the parent-frame choice
-// back to automatic.  + PD_PFI_NO_FACTS: a qualifying model keeps the PJI kernels without its facts compiled in (model_facts)
+// back to automatic.  + PD_PFI_NO_FACTS: a qualifying model keeps the PJI kernels without its facts compiled in (model_facts);
+// + PD_PFI_NO_COM_FACTS: ... keeps the FACTS kernels without its com facts (com_facts)
 int pd_model_set_kernel_family(pd_model *m, int family) {
   if (!m) return fail("null model");
   const int fam = family & 3, mode = (family >> 2) & 3;
-  if (family < 0 || family >= 2 * PD_PFI_NO_FACTS || fam > 2 || mode > 2)
-    return fail("kernel family: 0 automatic, 1 lane per body, 2 quad-lane where eligible (+ PD_PFI_GENERAL or PD_PFI_SPECIALISED, + PD_PFI_NO_FACTS)");
+  if (family < 0 || family >= 2 * PD_PFI_NO_COM_FACTS || fam > 2 || mode > 2)
+    return fail("kernel family: 0 automatic, 1 lane per body, 2 quad-lane where eligible (+ PD_PFI_GENERAL or PD_PFI_SPECIALISED, + PD_PFI_NO_FACTS, + PD_PFI_NO_COM_FACTS)");
   if (mode == 2 && !m->parent_frames_identity)
     return fail("PD_PFI_SPECIALISED: the model does not qualify (revolute-only plain model whose parent-side joint frames all have the rotation (0, 0, 0, 1))");
   m->family = fam; m->pfi_mode = mode; m->no_facts = (family & PD_PFI_NO_FACTS) != 0;
+  m->no_com_facts = (family & PD_PFI_NO_COM_FACTS) != 0;
   return 0;
 }
 int pd_model_get_kernel_family(const pd_model *m, int *eligible) {
   if (eligible) *eligible = (m && m->quad) ? 1 : 0;
-  return m ? m->family | (m->pfi_mode << 2) | (m->no_facts ? PD_PFI_NO_FACTS : 0) : 0;
+  return m ? m->family | (m->pfi_mode << 2) | (m->no_facts ? PD_PFI_NO_FACTS : 0) | (m->no_com_facts ? PD_PFI_NO_COM_FACTS : 0) : 0;
 }
 int pd_model_set_numeric_policy(pd_model *m, int policy) {
   if (!m) return fail("null model");
@@ -931,7 +953,8 @@ int pd_last_launch_info(const pd_model *m, int kind, int out[4]) {
   if (!m || !out || kind < 0 || kind > PD_LAUNCH_INFO_PARENT_FRAMES) return fail("bad argument");
   if (kind == PD_LAUNCH_INFO_PARENT_FRAMES) {
     out[0] = m->parent_frames_identity ? 1 : 0; out[1] = m->pfi_mode; out[2] = m->last_pji;
-    out[3] = (m->model_facts ? 1 : 0) | (m->no_facts ? 2 : 0) | (m->last_facts ? 4 : 0);
+    out[3] = (m->model_facts ? 1 : 0) | (m->no_facts ? 2 : 0) | (m->last_facts ? 4 : 0) | (m->com_facts ? 8 : 0) | (m->no_com_facts ? 16 : 0) |
+             (m->last_com ? 32 : 0);
     return 0;
   }
   for (int k = 0; k < 4; ++k) out[k] = m->last_launch[kind][k];

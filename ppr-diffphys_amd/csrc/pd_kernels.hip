@@ -1541,11 +1541,16 @@ __device__ __forceinline__ bool grad_wanted(const float *g) {
 // it is compiled in -- no revolute joint has limit gains (the limit terms of joint_force and joint_force_adj go, on both waves), the root is a FREE
 // joint with at least six bodies behind it (its six zero control-gradient columns are written by lanes 1 .. 6, the per-lane store block of a
 // FREE body goes), no body has more than four children (the further-children gather goes).
-template <int SEGW, int JT, bool QUAD = false, bool SEL = false, bool PJI = false, bool FACTS = false>
+// COM (with FACTS only; PdLaunchCfg::com, pd_host.hip com_facts): every body's com lies on its z axis and that of every jointed body is
+// (0, 0, 0) -- Laikago's: (0, 0, 0.0438) for the trunk, zero for the twelve leg bodies.  The rotation of com, its adjoints (integrate_adj2,
+// rev_adjoint_core) and, on the contact wave, its recovery from the staged rc and the adjoint through it (contact_point_adj) take their
+// z forms (pd_math.h); what a jointed body's zero com only multiplies is left out.
+template <int SEGW, int JT, bool QUAD = false, bool SEL = false, bool PJI = false, bool FACTS = false, bool COM = false>
 __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutArgs a) {
   static_assert(JT == PD_JT_REVOLUTE, "the wave-specialised adjoint of revolute-only plain models: every jointed body is a revolute joint on a parent body");
   static_assert(!(QUAD && PJI), "PJI: lane-per-body family only");
   static_assert(!FACTS || PJI, "FACTS: instantiated together with PJI only");
+  static_assert(!COM || FACTS, "COM: instantiated together with FACTS only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EPW = Seg<SEGW>::EPW;
   const int bw = (int)blockDim.x / (QUAD ? 192 : 128);  // env groups per workgroup (host's choice per launch)
@@ -1604,7 +1609,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       contact_pre_barrier(C);
       contact_point_adj_rest(C, P, mat, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
     } else {
-      contact_point_adj(r, cull_s[pb], P, mat, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
+      contact_point_adj<false, COM>(r, cull_s[pb], P, mat, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
     }
     adj_store(out, o);
   };
@@ -2155,7 +2160,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
     load_step(step - 1);
     float Rm[9];
     rotm(s.r, Rm);  // the body's rotation as a matrix: shared by the staging and the adjoint of integrate_bodies
-    const v3 rc = mat_vec(Rm, c.com);
+    const v3 rc = COM ? mat_vec_z(Rm, c.com.z) : mat_vec(Rm, c.com);
     if (is_body) stage_record(rec, cull, b, s, rc, Rm);
     STAMP(0);
     // ---- adjoint of integrate_bodies
@@ -2164,7 +2169,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
     float aR[9];  // matrix adjoint of Rm, summed over integrate_bodies and the joint; converted after both
 #pragma unroll
     for (int k = 0; k < 9; ++k) aR[k] = 0.f;
-    integrate_adj<PJI>(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, a.dt, gn, ga, aR, adj_t0, adj_f0, g_inv_m, g_I, g_invI);
+    integrate_adj<PJI, COM>(m, c, s, Rm, clamp_mask, t0, f0, inv_m, I, invI, a.dt, gn, ga, aR, adj_t0, adj_f0, g_inv_m, g_I, g_invI);
     if (is_body) {
       float *f = adjf + b * PD_W6;
       f[0] = adj_t0.x; f[1] = adj_t0.y; f[2] = adj_t0.z; f[3] = adj_f0.x; f[4] = adj_f0.y; f[5] = adj_f0.z;
@@ -2189,7 +2194,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       const v3 gp_t = ld3(adjf + c.parent * PD_W6), gp_f = ld3(adjf + c.parent * PD_W6 + 3);  // (plain model: every jointed body hangs on one)
       // the state-only half comes from the contact wave
       const RevCache R = rev_cache_load(jc + (step & 1) * m.env_lds_jc + b * PD_JC);
-      rev_adjoint<true, PJI, FACTS>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
+      rev_adjoint<true, PJI, FACTS, COM>(m, c, s, rc, rec, R, tgt[0], ke[0], kd[0], adj_t0, adj_f0, gp_t, gp_f, ga, par, aR, a_tgt[0], a_act[0], a_ke[0], a_kd[0]);
     }
     rotm_adj(s.r, aR, ga.r);
     if (is_body) {
@@ -2817,13 +2822,17 @@ static RolloutKernel select_fwd(int kernel, int roles, bool runsum, bool loss) {
 // pji: the plan's promise that the model's parent-side joint frames are unrotated (PdLaunchCfg::pji) -- the lane-per-body kernel then has a
 // PJI instantiation; the quad-lane kernel and k_rollout_bwd3 are the same kernels either way
 // facts (with pji only: PdLaunchCfg::facts): the PJI kernel with the model's facts compiled in (k_rollout_bwd FACTS)
+// com (with facts only: PdLaunchCfg::com): ... and its com facts (k_rollout_bwd COM)
 template <int JT, bool GT, bool SEL>
-static RolloutKernel select_bwd(int kernel, bool pji, bool facts) {
+static RolloutKernel select_bwd(int kernel, bool pji, bool facts, bool com = false) {
   if constexpr (pd_split(JT)) {
     if (kernel == PD_KV_BWD_QUAD) {
       if constexpr (PD_SEGW == 64) return k_rollout_bwd<PD_SEGW, JT, true, SEL>;
       else return nullptr;
     }
+#if PD_PJI_FACTS && PD_COM_FACTS
+    if (pji && facts && com) return k_rollout_bwd<PD_SEGW, JT, false, SEL, true, true, true>;
+#endif
 #if PD_PJI_FACTS
     if (pji && facts) return k_rollout_bwd<PD_SEGW, JT, false, SEL, true, true>;
 #endif
@@ -2844,7 +2853,7 @@ static hipError_t launch_fwd(const PdDevModel &m, const RolloutArgs &a, const Pd
 }
 template <int JT, bool GT, bool SEL>
 static hipError_t launch_bwd(const PdDevModel &m, const RolloutArgs &a, const PdLaunchCfg &cfg, hipStream_t st) {
-  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel, cfg.pji != 0, cfg.facts != 0), m, a, cfg, st);
+  return launch_rollout(select_bwd<JT, GT, SEL>(cfg.kernel, cfg.pji != 0, cfg.facts != 0, cfg.com != 0), m, a, cfg, st);
 }
 
 template <int JT, bool GT>
@@ -2901,8 +2910,8 @@ static hipError_t set_lds_fwd(int bytes) {
 template <int JT, bool GT, bool SEL>
 static hipError_t set_lds_bwd(int bytes) {
   for (const int kernel : kBwdVariants)
-    for (int pji = 0; pji < 3; ++pji)  // (2: PJI with the model facts)
-      if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel, pji != 0, pji == 2), bytes)) return e;
+    for (int pji = 0; pji < 4; ++pji)  // (2: PJI with the model facts, 3: and the com facts)
+      if (const hipError_t e = set_lds(select_bwd<JT, GT, SEL>(kernel, pji != 0, pji >= 2, pji == 3), bytes)) return e;
   return hipSuccess;
 }
 

@@ -310,3 +310,23 @@ PD_DEV void add_outer(float *M, v3 a, v3 b) {
   M[3] += a.y * b.x; M[4] += a.y * b.y; M[5] += a.y * b.z;
   M[6] += a.z * b.x; M[7] += a.z * b.y; M[8] += a.z * b.z;
 }
+
+// ---- the same for a vector on the body's z axis, v = (0, 0, vz): the centre-of-mass offset of a model whose com facts hold (pd_host.hip
+// com_facts; k_rollout_bwd COM).  Each is its general form above without the products with the two exact zeros -- the same value for every
+// finite operand (the library does not define the sign of a zero, Makefile); a non-finite operand no longer turns 0 * x into NaN (DESIGN.md
+// section 6).
+PD_DEV v3 mat_vec_z(const float *M, float vz) { return V3(M[2] * vz, M[5] * vz, M[8] * vz); }          // mat_vec(M, (0, 0, vz)): column 2
+PD_DEV void add_outer_z(float *M, v3 a, float bz) { M[2] += a.x * bz; M[5] += a.y * bz; M[8] += a.z * bz; }  // add_outer(M, a, (0, 0, bz))
+PD_DEV void adj_qrot_q_z(qt q, float vz, qt &adj_q, v3 g) {                                               // adj_qrot_q(q, (0, 0, vz), adj_q, g)
+  const v3 u = qvec(q);
+  const float uv = u.z * vz, ug = dot(u, g), w2 = 2.0f * q.w;
+  adj_q.x += (-vz * g.y) * w2 + (g.x * uv) * 2.0f;   // cross(v, g) = (-vz g.y, vz g.x, 0)
+  adj_q.y += (vz * g.x) * w2 + (g.y * uv) * 2.0f;
+  adj_q.z += (g.z * uv + vz * ug) * 2.0f;
+  adj_q.w += 4.0f * q.w * (vz * g.z) + 2.0f * ((u.y * vz) * g.x - (u.x * vz) * g.y);  // cross(u, v) = (u.y vz, -u.x vz, 0)
+}
+// z component of qrot_inv(q, v) -- row 2 of rotm(q)^T v: what is left to recover of a com on the z axis from its rotated image
+PD_DEV float qrot_inv_z(qt q, v3 v) {
+  const v3 u = qvec(q);
+  return v.z * (2.0f * q.w * q.w - 1.0f) - (u.x * v.y - u.y * v.x) * (2.0f * q.w) + u.z * (2.0f * dot(u, v));
+}

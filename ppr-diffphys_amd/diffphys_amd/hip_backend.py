@@ -98,6 +98,19 @@ def model_facts(tpl):
     return int(np.bincount(par[par >= 0], minlength=nb).max()) <= 4
 
 
+def com_facts(tpl):
+    """The library's test (csrc/pd_host.hip com_facts) on a template dict, without a device: a robot that passes model_facts whose centres of
+    mass, as the fp32 values the device receives, all have x == 0 and y == 0 and are (0, 0, 0) for every body whose joint is not FREE --
+    Laikago: (0, 0, 0.0438) for the trunk, zero for the twelve leg bodies.  Its lane-per-body adjoint takes the kernels that leave out the
+    products with those zeros (DeviceModel.set_com_facts; DeviceModel.com_facts_info() is the library's own answer)."""
+    if not model_facts(tpl):
+        return False
+    nb = int(tpl["nb"])
+    com = np.asarray(tpl["body_com"], np.float32).reshape(nb, 3)
+    jointed = np.asarray(tpl["joint_type"]).reshape(-1)[:nb] != 4   # (4: FREE)
+    return bool((com[:, :2] == 0).all() and (com[jointed, 2] == 0).all())
+
+
 class _Desc(ctypes.Structure):
     _fields_ = [
         ("nb", ctypes.c_int), ("nq", ctypes.c_int), ("nqd", ctypes.c_int), ("nc", ctypes.c_int), ("nmat", ctypes.c_int),
@@ -295,7 +308,7 @@ class DeviceModel:
         self.h = h
         self._xp = None
         self._nc_keep = keep["contact_body"]
-        self._family, self._pfi, self._nofacts = 0, 0, 0
+        self._family, self._pfi, self._nofacts, self._nocom = 0, 0, 0, 0
 
     def __del__(self):
         try:
@@ -313,7 +326,7 @@ class DeviceModel:
 
     def set_kernel_family(self, family):
         """0 automatic (by batch size), 1 lane per body always, 2 quad-lane (four lanes per body) wherever the robot is eligible."""
-        _check(lib().pd_model_set_kernel_family(self.h, int(family) + 4 * self._pfi + 16 * self._nofacts))
+        _check(lib().pd_model_set_kernel_family(self.h, int(family) + 4 * self._pfi + 16 * self._nofacts + 32 * self._nocom))
         self._family = int(family)
 
     def set_parent_frame_identity(self, mode):
@@ -322,7 +335,7 @@ class DeviceModel:
         ones (raises unless the robot qualifies).  For tests and A/B timing; rides on ``pd_model_set_kernel_family``."""
         if int(mode) not in (0, 1, 2):
             raise ValueError("parent frame identity mode: 0 automatic, 1 general, 2 specialised")
-        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * int(mode) + 16 * self._nofacts))
+        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * int(mode) + 16 * self._nofacts + 32 * self._nocom))
         self._pfi = int(mode)
 
     def set_model_facts(self, on):
@@ -330,8 +343,23 @@ class DeviceModel:
         facts compiled in (no joint limits, FREE root with six bodies behind it, at most four children).  False: the same kernels with the
         facts tested at run time (PD_PFI_NO_FACTS).  For tests and A/B timing; rides on ``pd_model_set_kernel_family``."""
         nofacts = 0 if on else 1
-        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * self._pfi + 16 * nofacts))
+        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * self._pfi + 16 * nofacts + 32 * self._nocom))
         self._nofacts = nofacts
+
+    def set_com_facts(self, on):
+        """True (default): a robot that qualifies (hip_backend.com_facts -- Laikago) runs its lane-per-body adjoint on the kernels that have its
+        com facts compiled in on top of its model facts (every com on its body's z axis, zero for the jointed bodies).  False: the kernels
+        with the general centre-of-mass algebra (PD_PFI_NO_COM_FACTS).  For tests and A/B timing; rides on ``pd_model_set_kernel_family``."""
+        nocom = 0 if on else 1
+        _check(lib().pd_model_set_kernel_family(self.h, self._family + 4 * self._pfi + 16 * self._nofacts + 32 * nocom))
+        self._nocom = nocom
+
+    def com_facts_info(self):
+        """dict(qualifies, disabled, last_launch): the library's own com_facts answer for this robot, whether set_com_facts(False) holds, and
+        whether the last adjoint launch ran the kernels with the com facts compiled in."""
+        out = (ctypes.c_int * 4)()
+        _check(lib().pd_last_launch_info(self.h, 2, ctypes.byref(out)))
+        return dict(qualifies=bool(out[3] & 8), disabled=bool(out[3] & 16), last_launch=bool(out[3] & 32))
 
     def model_facts_info(self):
         """dict(qualifies, disabled, last_launch): the library's own model_facts answer for this robot, whether set_model_facts(False) holds,
