@@ -623,18 +623,41 @@ int pd_reduce_loss(int bs, int nframes, float *table_dev, int clip, float *reduc
  * A table of another nb: out is written as zeros, no row of the table is read.  A parent index or a coordinate range outside the set:
  * as for PD_POSE_BODY_TWIST -- a malformed table never indexes outside the set.
  *
+ * The joint-space mass matrix of a state -- the composite-rigid-body recursion:
+ *   PD_POSE_MASS_MATRIX    b = rows [n][17] = (p, q xyzw, m, I row-major 3x3): pose, mass and body-frame inertia about the centre of
+ *                          mass as in PD_POSE_MASS_INVERSE's rows (the symmetric part of I enters).  a_broadcast = nb (at most 256)
+ *                          and a = ONE joint table of PD_POSE_JOINT_COORDS, byte for byte, its mode float [3] included ->
+ *                          out [n / nb][nqd * nqd], row-major, in the joint_qd layout (the table's dof starts):
+ *                            H = sum_b J_b^T diag(R_b sym(I_b) R_b^T, m_b 1) J_b,   J = PD_POSE_BODY_TWIST's Jacobian in the table's mode
+ *                          -- in mode 1 (generalized) the mass matrix of the generalised rates, in mode 0 (measured) the matrix whose
+ *                          inverse PD_POSE_MASS_INVERSE applies in that mode.  In PD_POSE_MASS_INVERSE's frame, spatial inertias I_b
+ *                          and motion subspaces S_i:  up, deepest level first, Ic_i = I_i + sum_children Ic_c (the table's child
+ *                          order);  F_i = Ic_i S_i;  walking j = i, parent(i), ...: H[dofs_j, dofs_i] = S_j^T F_i and its transpose.
+ *                          An entry between dofs of two bodies neither of which is the other's ancestor is exactly 0.0f; out[a][b]
+ *                          and out[b][a] are the same bits.  One launch, no atomics: a set's bits depend neither on the run nor on
+ *                          n nor on its place in the launch.  fp32 rows, frames and S; inertias, sums and products in double.
+ *                          VJP: g_out [n / nb][nqd * nqd], arbitrary (not assumed symmetric) -> g_b [n][17], the raw partials in
+ *                          pose, mass and inertia (quaternions as they are; the inertia's are those of sym(I)), by a kernel of its
+ *                          own: with Gs = (g_out + g_out^T) / 2, A_i = sum_{j in anc*(i)} S_j Gs_ji,
+ *                          dL/dI_b = sum_{i in anc*(b)} (A_i S_i^T + S_i A_i^T - S_i Gs_ii S_i^T),
+ *                          dL/dS_i = 2 (Ic_i A_i + sum_{k in desc(i)} F_k Gs_ki), chained into the rows; contributions to a parent's
+ *                          row are gathered in the table's child order.  The table has no gradient: a non-NULL g_a is refused, at
+ *                          every n.
+ * A table of another nb: zeros, no row of the table is read; a malformed table never indexes outside the set (a walk over parents is
+ * bounded by nb steps).
+ *
  * No allocation, no synchronisation: capturable in a HIP graph.  n = 0 is legal.  A refused call returns non-zero and
  * leaves its reason in pd_last_error.  PD_POSE_GROUND_WRENCH, PD_POSE_JOINT_COORDS, PD_POSE_CENTROIDAL, PD_POSE_CONTACT_STATE,
- * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE, PD_POSE_BODY_TWIST, PD_POSE_BODY_ACCEL and PD_POSE_MASS_INVERSE are new op codes of
- * the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14, 16, 18 and 20 are
- * not assigned and are refused as "unknown op" -- callers and tests of version 9 rely on that refusal (of 7 and 8 since the centroidal
- * op took 9, of 10 since the contact state took 11, of 12 since the joint wrench took 13, of 14 since the generalised force took 15,
- * of 16 since the body twist took 17, of 18 since the body acceleration took 19, of 20 since the mass inverse took 21), so the eight
- * stay free for as long as the version is 9. */
+ * PD_POSE_JOINT_WRENCH, PD_POSE_GENERALIZED_FORCE, PD_POSE_BODY_TWIST, PD_POSE_BODY_ACCEL, PD_POSE_MASS_INVERSE and PD_POSE_MASS_MATRIX are new op
+ * codes of the two entries: no symbol or signature changed, the version stays 9.  The enum has gaps: codes 7, 8, 10, 12, 14, 16, 18, 20
+ * and 22 are not assigned and are refused as "unknown op", and so is 24, the code after the last -- callers and tests of version 9 rely
+ * on that refusal (of 7 and 8 since the centroidal op took 9, of 10 since the contact state took 11, of 12 since the joint wrench took
+ * 13, of 14 since the generalised force took 15, of 16 since the body twist took 17, of 18 since the body acceleration took 19, of 20
+ * since the mass inverse took 21, of 22 since the mass matrix took 23), so the nine stay free for as long as the version is 9. */
 enum { PD_POSE_COMPOSE_DELTA = 0, PD_POSE_ROTATE_FRAME = 1, PD_POSE_ROTATE_VEL = 2, PD_POSE_PROJECT = 3, PD_POSE_PROJECT_POINT = 4,
        PD_POSE_GROUND_WRENCH = 5, PD_POSE_JOINT_COORDS = 6, PD_POSE_CENTROIDAL = 9, PD_POSE_CONTACT_STATE = 11,
        PD_POSE_JOINT_WRENCH = 13, PD_POSE_GENERALIZED_FORCE = 15, PD_POSE_BODY_TWIST = 17,
-       PD_POSE_BODY_ACCEL = 19, PD_POSE_MASS_INVERSE = 21 };
+       PD_POSE_BODY_ACCEL = 19, PD_POSE_MASS_INVERSE = 21, PD_POSE_MASS_MATRIX = 23 };
 int pd_pose_op(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, float *out_dev, void *stream);
 int pd_pose_op_vjp(int op, int n, const float *a_dev, int a_broadcast, const float *b_dev, const float *g_out_dev,
                    float *g_a_dev, float *g_b_dev, void *stream);

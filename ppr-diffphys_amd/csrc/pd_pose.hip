@@ -2074,6 +2074,453 @@ __global__ __launch_bounds__(256) void k_mass_inverse(int nsets, int nb, const f
   for (int k = 0; k < 6; ++k) o[k] = (float)x[k];
 }
 
+// ---- PD_POSE_MASS_MATRIX: the joint-space mass matrix H = sum_b J_b^T diag(R_b sym(I_b) R_b^T, m_b) J_b of a state (J =
+// PD_POSE_BODY_TWIST's Jacobian in the table's mode: the matrix whose inverse PD_POSE_MASS_INVERSE applies) by the composite-rigid-body
+// recursion, from rows (p, q xyzw, m, I row-major) -> [n / nb][nqd * nqd] row-major in the joint_qd layout, and its vector-Jacobian
+// product with respect to the rows.  The frame, the spatial inertia (mi_ix) and the motion subspace S_i are k_mass_inverse's: world axes
+// about o0, spatial vectors (angular, linear at o0).  (That kernel keeps its own lines: sharing them changes its instruction stream.)
+//   up, deepest level first   Ic_i = I_i + sum_children Ic_c   (the table's child order; 21 doubles handed up per body)
+//   per body i with dofs      F_i = Ic_i S_i                   (6 x K_i)
+//   walk j = i, pi(i), ...    H[dofs_j, dofs_i] = S_j^T F_i and its transpose, both from one computed value
+// Every lane publishes its S (fp32, at most 36 floats) in LDS for its descendants' walks.  The set's lanes zero its nqd^2 floats in a
+// fixed order first; the barriers of the up sweep separate that from the walks' writes, after which every float between related dofs
+// has one writing lane and every other one stays exactly 0.  A walk is bounded by nb steps (a malformed table may hold a cycle) and a
+// joint's dofs lie inside [0, nqd) or it is FIXED (jc_joint): nothing is indexed outside the set.  A table of another nb: zeros.
+// Precision: rows, frames and S are fp32; the body's inertia, the sums over children, F and the products are double and the composite
+// is handed over in double (rounding it to fp32 at each hand-over costs 1e-5 of sqrt(H_aa H_bb) on a long chain: DESIGN.md section 8).
+// VJP of <G, H>, G arbitrary, Gs = (G + G^T) / 2:
+//   A_i = sum_{j in anc*(i)} S_j Gs_ji;   Q_i = A_i S_i^T + S_i A_i^T - S_i Gs_ii S_i^T;   dL/dI_b = P_b = sum_{i in anc*(b)} Q_i
+//   dL/dS_i = Z_i = 2 (Ic_i A_i + sum_{k in desc(i)} F_k Gs_ki)
+// a column of S_i at a time: the ancestor walk, the gather over the set's bodies k (in body order; k is a descendant when walking up
+// depth(k) - depth(i) parents from k ends at i), and the column's share of Q_i and of the adjoints of the joint's axes and anchor.
+// Then P_b by an ancestor sum from the roots down (21 doubles), P_b into (p, q, m, sym I) of the body, Z into the frames S_i depends
+// on -- the body's own pose, the parent's, jc_compound's axes as k_body_twist_vjp differentiates them --, the parent-side pose adjoint
+// handed over as k_joint_coords_vjp does.  o0 is a constant of the adjoint: H does not depend on the reference point.  No atomics.
+enum { MM_ROW = 17, MM_S = 37 };  // floats of a row / of an LDS slot of S or F (36 used; odd stride)
+struct MmBody { BodyState s; JcJoint J; JcCompound C; v3 d, ra, c0, c2; int K; };  // c0, c2: the COMPOUND columns 0 and 2 in the offset frame
+// The body's pose, joint frames and motion subspace (S: 36 floats, zero past the joint's columns)
+__device__ __forceinline__ void mm_load(const float *tab, int nb, int body, const float *set_rows, bool generalized, MmBody &B, float *S) {
+  const float *row = set_rows + (size_t)body * MM_ROW;
+  const v3 o0 = ld3(set_rows);
+  B.s.p = ld3(row); B.s.r = ld4(row + 3); B.s.w = V3(0, 0, 0); B.s.v = B.s.w;
+  B.J = jc_joint<MM_ROW>(tab, nb, (int)tab[1], (int)tab[2], body, B.s, set_rows);
+  const JcJoint &J = B.J;
+  B.d = (B.s.p - o0) + qrot(B.s.r, J.com);
+  B.ra = J.type == PD_JOINT_FREE ? B.d : J.parent >= 0 ? (J.pp - o0) + qrot(J.qp, J.p_pj) : J.p_pj - o0;
+  B.c0 = V3(1, 0, 0); B.c2 = V3(0, 0, 1); B.K = 0;
+  v3 u0 = V3(0, 0, 0), u1 = u0, u2 = u0;  // the joint's axes in world axes
+  if (J.type == PD_JOINT_FREE) {
+    u0 = qrot(J.q_wj, V3(1, 0, 0)); u1 = qrot(J.q_wj, V3(0, 1, 0)); u2 = qrot(J.q_wj, V3(0, 0, 1));
+    B.K = 6;
+  } else if (J.type == PD_JOINT_REVOLUTE) {
+    u0 = qrot(J.q_wj, J.axis);
+    B.K = 1;
+  } else if (J.type == PD_JOINT_COMPOUND) {
+    jc_compound(J, false, B.C);
+    B.c2 = B.C.a2;
+    if (!generalized) {  // the columns of A G^-1
+      const float id = 1.0f / (1.0f - B.C.s * B.C.s);
+      B.c0 = (V3(1, 0, 0) - B.C.a2 * B.C.s) * id; B.c2 = (B.C.a2 - V3(B.C.s, 0, 0)) * id;
+    }
+    u0 = qrot(B.C.q_w, B.c0); u1 = qrot(B.C.q_w, B.C.a1); u2 = qrot(B.C.q_w, B.c2);
+    B.K = 3;
+  }
+  // (every store unconditional, at a constant index: an axis the joint does not have is zero)
+  const v3 zero = V3(0, 0, 0);
+  const bool free = B.K == 6;
+  mi_col(S, u0, -cross(u0, B.ra)); mi_col(S + 6, u1, -cross(u1, B.ra)); mi_col(S + 12, u2, -cross(u2, B.ra));
+  mi_col(S + 18, zero, free ? u0 : zero); mi_col(S + 24, zero, free ? u1 : zero); mi_col(S + 30, zero, free ? u2 : zero);
+}
+__device__ __forceinline__ void mm_rotm(qt q, double *R) {  // rotm's polynomial, as qrot's, in double
+  const double qx = q.x, qy = q.y, qz = q.z, qw = q.w, sq = 2.0 * qw * qw - 1.0;
+  R[0] = sq + 2.0 * qx * qx; R[1] = 2.0 * (qx * qy - qw * qz); R[2] = 2.0 * (qx * qz + qw * qy);
+  R[3] = 2.0 * (qx * qy + qw * qz); R[4] = sq + 2.0 * qy * qy; R[5] = 2.0 * (qy * qz - qw * qx);
+  R[6] = 2.0 * (qx * qz - qw * qy); R[7] = 2.0 * (qy * qz + qw * qx); R[8] = sq + 2.0 * qz * qz;
+}
+__device__ __forceinline__ void mm_sym(const float *row, double *Is) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Is[3 * i + j] = 0.5 * ((double)row[8 + 3 * i + j] + (double)row[8 + 3 * j + i]);
+}
+// The body's own spatial inertia about o0 in double from the fp32 row (the shift adds m |d|^2 to an inertia that may be 1e-4 of it)
+__device__ __forceinline__ void mm_inertia(const float *row, qt q, v3 d, double *IA) {
+  const double m = (double)row[7];
+  double R[9], Is[9], RI[9];
+  mm_rotm(q, R);
+  mm_sym(row, Is);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) RI[3 * i + j] = R[3 * i] * Is[j] + R[3 * i + 1] * Is[3 + j] + R[3 * i + 2] * Is[6 + j];
+  const double dv[3] = {d.x, d.y, d.z}, d2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j)
+      IA[mi_ix(i, j)] = (RI[3 * i] * R[3 * j] + RI[3 * i + 1] * R[3 * j + 1] + RI[3 * i + 2] * R[3 * j + 2]) +
+                        m * ((i == j ? d2 : 0.0) - dv[i] * dv[j]);
+  IA[mi_ix(0, 3)] = 0.0; IA[mi_ix(1, 4)] = 0.0; IA[mi_ix(2, 5)] = 0.0;
+  IA[mi_ix(0, 4)] = -m * dv[2]; IA[mi_ix(0, 5)] = m * dv[1];  // m [d]x
+  IA[mi_ix(1, 3)] = m * dv[2]; IA[mi_ix(1, 5)] = -m * dv[0];
+  IA[mi_ix(2, 3)] = -m * dv[1]; IA[mi_ix(2, 4)] = m * dv[0];
+  IA[mi_ix(3, 3)] = m; IA[mi_ix(4, 4)] = m; IA[mi_ix(5, 5)] = m;
+  IA[mi_ix(3, 4)] = 0.0; IA[mi_ix(3, 5)] = 0.0; IA[mi_ix(4, 5)] = 0.0;
+}
+// Composite inertias: levels deepest first, a body adds its children's 21 doubles in the table's child order and publishes its own.
+__device__ __forceinline__ void mm_up(double *comp, const GfTree &T, const SetLane &L, int nb, double *IA) {
+  double *cm = comp + threadIdx.x * 21;
+#pragma unroll
+  for (int e = 0; e < 21; ++e) cm[e] = 0.0;  // (a malformed table may name a child that publishes later: it reads zeros)
+  for (int lev = T.maxd; lev >= 0; --lev) {
+    __syncthreads();
+    if (L.active && T.dep == lev) {
+      for (int k = 0; k < T.nch; ++k) {
+        const int c = (int)T.ch[k];
+        if (c >= 0 && c < nb) {
+          const double *cs = comp + (L.set_l * nb + c) * 21;
+#pragma unroll
+          for (int e = 0; e < 21; ++e) IA[e] += cs[e];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 21; ++e) cm[e] = IA[e];
+    }
+  }
+}
+template <int K>
+__device__ __forceinline__ void mm_force(const double *IA, const float *S, double *F) {  // F = Ic S, column k at [6 k ..]
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double t = IA[mi_ix(i, 0)] * (double)S[6 * k];
+#pragma unroll
+      for (int j = 1; j < 6; ++j) t += IA[mi_ix(i, j)] * (double)S[6 * k + j];
+      F[6 * k + i] = t;
+    }
+}
+// The blocks of H the body's dofs share with its own and its ancestors' (base: the set's first lane).  Every index is a constant.
+template <int K>
+__device__ __forceinline__ void mm_walk(const double *IA, const float *S, const float *Ssh, const int *s_par, const int *s_k, const int *s_qd,
+                                        int base, int body, int qds, int nb, int nqd, float *o) {
+  double F[6 * K];
+  mm_force<K>(IA, S, F);
+#pragma unroll
+  for (int a = 0; a < K; ++a)
+#pragma unroll
+    for (int b = a; b < K; ++b) {
+      double h = 0.0;
+#pragma unroll
+      for (int e = 0; e < 6; ++e) h += (double)S[6 * a + e] * F[6 * b + e];
+      o[(size_t)(qds + a) * nqd + (qds + b)] = (float)h;
+      o[(size_t)(qds + b) * nqd + (qds + a)] = (float)h;
+    }
+  int j = s_par[base + body];
+  for (int step = 1; j >= 0 && step < nb; ++step) {
+    const int Kj = s_k[base + j], dj = s_qd[base + j];
+    const float *Sj = Ssh + (base + j) * MM_S;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+      if (a < Kj) {
+        double sj[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) sj[e] = (double)Sj[6 * a + e];
+#pragma unroll
+        for (int b = 0; b < K; ++b) {
+          double h = 0.0;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) h += sj[e] * F[6 * b + e];
+          o[(size_t)(dj + a) * nqd + (qds + b)] = (float)h;
+          o[(size_t)(qds + b) * nqd + (dj + a)] = (float)h;
+        }
+      }
+    j = s_par[base + j];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mass_matrix(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                     float *__restrict__ out) {
+  __shared__ float Ssh[256 * MM_S];  // lane -> its motion subspace
+  __shared__ double comp[256 * 21];  // lane -> its composite inertia
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  const int nqd = max((int)tab[2], 0);
+  const size_t nn = (size_t)nqd * nqd;
+  float *o = out + (size_t)L.set * nn;  // (formed, not touched, by an inactive lane)
+  if (L.active)
+    for (size_t k = (size_t)L.body; k < nn; k += (size_t)nb) o[k] = 0.0f;
+  if ((int)tab[0] != nb) return;  // not this call's table (the same for every lane of the launch: no barrier is skipped by some)
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  MmBody B;
+  float S[36];
+  double IA[21];
+#pragma unroll
+  for (int e = 0; e < 36; ++e) S[e] = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 21; ++e) IA[e] = 0.0;
+  B.K = 0; B.J.qds = 0;
+  if (L.active) {
+    const float *set_rows = rows + (size_t)L.set * nb * MM_ROW;
+    mm_load(tab, nb, L.body, set_rows, generalized, B, S);
+    mm_inertia(set_rows + (size_t)L.body * MM_ROW, B.s.r, B.d, IA);
+  }
+  int *s_par = s_anc[0], *s_k = s_anc[1], *s_qd = s_dep[0];  // (gf_tree is done with them: its last barrier is behind every read)
+  s_par[threadIdx.x] = T.parent; s_k[threadIdx.x] = B.K; s_qd[threadIdx.x] = B.J.qds;
+  float *mine = Ssh + threadIdx.x * MM_S;
+#pragma unroll
+  for (int e = 0; e < 36; ++e) mine[e] = S[e];
+  mm_up(comp, T, L, nb, IA);  // (its barriers also stand between the zeros above and the walks' writes, and publish S)
+  if (!L.active) return;
+  const int base = L.set_l * nb;
+  if (B.K == 6) mm_walk<6>(IA, S, Ssh, s_par, s_k, s_qd, base, L.body, B.J.qds, nb, nqd, o);
+  else if (B.K == 3) mm_walk<3>(IA, S, Ssh, s_par, s_k, s_qd, base, L.body, B.J.qds, nb, nqd, o);
+  else if (B.K == 1) mm_walk<1>(IA, S, Ssh, s_par, s_k, s_qd, base, L.body, B.J.qds, nb, nqd, o);
+}
+
+// g_b [n][17]: the raw partials of <g_out, out> with respect to (p, q, m, I) of every body; the inertia's are those of sym(I).
+__global__ __launch_bounds__(256) void k_mass_matrix_vjp(int nsets, int nb, const float *__restrict__ tab, const float *__restrict__ rows,
+                                                         const float *__restrict__ g_out, float *__restrict__ g_b) {
+  __shared__ float Ssh[256 * MM_S], Fsh[256 * MM_S], pslot[256 * GF_S];  // S / F = Ic S / the parent-side pose adjoint
+  __shared__ double comp[256 * 21];                                       // composite inertias up, then the ancestor sums of Q down
+  __shared__ int s_anc[2][256], s_dep[2][256], s_max[4];
+  const SetLane L = set_lane(nsets, nb);
+  float *dst = g_b + ((size_t)L.set * nb + L.body) * MM_ROW;  // (formed, not touched, by an inactive lane)
+  if ((int)tab[0] != nb) {
+    if (L.active)
+      for (int k = 0; k < MM_ROW; ++k) dst[k] = 0.0f;
+    return;
+  }
+  const int nqd = max((int)tab[2], 0);
+  const bool generalized = tab[3] != 0.0f;
+  const GfTree T = gf_tree(tab, nb, L, s_anc, s_dep, s_max);
+  MmBody B;
+  float S[36];
+  double IA[21];
+#pragma unroll
+  for (int e = 0; e < 36; ++e) S[e] = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 21; ++e) IA[e] = 0.0;
+  B.K = 0; B.J.qds = 0;
+  const float *row = rows;
+  if (L.active) {
+    const float *set_rows = rows + (size_t)L.set * nb * MM_ROW;
+    row = set_rows + (size_t)L.body * MM_ROW;
+    mm_load(tab, nb, L.body, set_rows, generalized, B, S);
+    mm_inertia(row, B.s.r, B.d, IA);
+  }
+  int *s_par = s_anc[0], *s_k = s_anc[1], *s_qd = s_dep[0], *s_dp = s_dep[1];  // (gf_tree is done with them)
+  s_par[threadIdx.x] = T.parent; s_k[threadIdx.x] = B.K; s_qd[threadIdx.x] = B.J.qds; s_dp[threadIdx.x] = T.dep;
+  float *mine = Ssh + threadIdx.x * MM_S, *fmine = Fsh + threadIdx.x * MM_S;
+#pragma unroll
+  for (int e = 0; e < 36; ++e) mine[e] = S[e];
+  mm_up(comp, T, L, nb, IA);
+  {
+    double F[36];
+#pragma unroll
+    for (int e = 0; e < 36; ++e) F[e] = 0.0;
+    if (B.K == 6) mm_force<6>(IA, S, F);
+    else if (B.K == 3) mm_force<3>(IA, S, F);
+    else if (B.K == 1) mm_force<1>(IA, S, F);
+#pragma unroll
+    for (int e = 0; e < 36; ++e) fmine[e] = (float)F[e];
+  }
+  __syncthreads();  // F is published; nobody reads a composite any more
+  const int base = L.set_l * nb, K = B.K, qds = B.J.qds;
+  double Q[21];
+#pragma unroll
+  for (int e = 0; e < 21; ++e) Q[e] = 0.0;
+  v3 gu0 = V3(0, 0, 0), gu1 = gu0, gu2 = gu0, adj_ra = gu0;  // the adjoints of the joint's three axes and of its anchor
+  if (L.active) {
+    const float *G = g_out + (size_t)L.set * nqd * nqd;
+    for (int b = 0; b < K; ++b) {
+      const size_t cb = (size_t)(qds + b);
+      const float *sb = mine + 6 * b;
+      double a[6], self[6], z[6];
+#pragma unroll
+      for (int e = 0; e < 6; ++e) self[e] = 0.0;
+      for (int c = 0; c < K; ++c) {
+        const size_t cc = (size_t)(qds + c);
+        const double gs = 0.5 * ((double)G[cc * nqd + cb] + (double)G[cb * nqd + cc]);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) self[e] += (double)mine[6 * c + e] * gs;
+      }
+#pragma unroll
+      for (int e = 0; e < 6; ++e) a[e] = self[e];
+      int j = T.parent;
+      for (int step = 1; j >= 0 && step < nb; ++step) {
+        const int Kj = s_k[base + j], dj = s_qd[base + j];
+        const float *Sj = Ssh + (base + j) * MM_S;
+        for (int c = 0; c < Kj; ++c) {
+          const size_t cc = (size_t)(dj + c);
+          const double gs = 0.5 * ((double)G[cc * nqd + cb] + (double)G[cb * nqd + cc]);
+#pragma unroll
+          for (int e = 0; e < 6; ++e) a[e] += (double)Sj[6 * c + e] * gs;
+        }
+        j = s_par[base + j];
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {  // Q += a' s^T + s a'^T, a' = a - self / 2 (the own block counts once)
+        const double ai = a[i] - 0.5 * self[i], si = (double)sb[i];
+#pragma unroll
+        for (int jj = i; jj < 6; ++jj) Q[mi_ix(i, jj)] += ai * (double)sb[jj] + si * (a[jj] - 0.5 * self[jj]);
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        double t = IA[mi_ix(i, 0)] * a[0];
+#pragma unroll
+        for (int jj = 1; jj < 6; ++jj) t += IA[mi_ix(i, jj)] * a[jj];
+        z[i] = t;
+      }
+      for (int k = 0; k < nb; ++k) {  // the descendants, in body order
+        const int Kk = s_k[base + k], up = s_dp[base + k] - T.dep;
+        if (Kk == 0 || up <= 0) continue;
+        int anc = k;
+        for (int s = 0; s < up && anc >= 0; ++s) anc = s_par[base + anc];
+        if (anc != L.body) continue;
+        const int dk = s_qd[base + k];
+        const float *Fk = Fsh + (base + k) * MM_S;
+        for (int c = 0; c < Kk; ++c) {
+          const size_t cc = (size_t)(dk + c);
+          const double gs = 0.5 * ((double)G[cc * nqd + cb] + (double)G[cb * nqd + cc]);
+#pragma unroll
+          for (int e = 0; e < 6; ++e) z[e] += (double)Fk[6 * c + e] * gs;
+        }
+      }
+      const v3 za = V3((float)(2.0 * z[0]), (float)(2.0 * z[1]), (float)(2.0 * z[2]));
+      const v3 zl = V3((float)(2.0 * z[3]), (float)(2.0 * z[4]), (float)(2.0 * z[5]));
+      const bool lin = K == 6 && b >= 3;  // a FREE joint's column (0, e_k)
+      v3 g = zl;
+      if (!lin) {  // the column (u, ra x u)
+        g = za;
+        adj_cross(B.ra, V3(sb[0], sb[1], sb[2]), adj_ra, g, zl);
+      }
+      const int kk = lin ? b - 3 : b;
+      if (kk == 0) gu0 += g;
+      else if (kk == 1) gu1 += g;
+      else gu2 += g;
+    }
+  }
+  // P_b = the sum of Q over the body and its ancestors: levels from the roots down
+  double *cm = comp + threadIdx.x * 21;
+#pragma unroll
+  for (int e = 0; e < 21; ++e) cm[e] = Q[e];
+  for (int lev = 1; lev <= T.maxd; ++lev) {
+    __syncthreads();
+    if (L.in_set && T.dep == lev && T.parent >= 0) {
+      const double *pp = comp + (base + T.parent) * 21;
+#pragma unroll
+      for (int e = 0; e < 21; ++e) { Q[e] += pp[e]; cm[e] = Q[e]; }
+    }
+  }
+  v3 own_p = V3(0, 0, 0), par_p = own_p;
+  qt own_q = Q4(0, 0, 0, 0), par_q = own_q;
+  float g_m = 0.0f, g_I[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) g_I[e] = 0.0f;
+  if (L.active) {
+    const JcJoint &J = B.J;
+    // the body's own spatial inertia [[R Is R^T + m (|d|^2 1 - d d^T), m [d]x], [-m [d]x, m 1]] against P (a full symmetric matrix)
+    const double m = (double)row[7], dv[3] = {B.d.x, B.d.y, B.d.z}, d2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+    double R[9], Is[9], PR[9], RI[9];
+    mm_rotm(B.s.r, R);
+    mm_sym(row, Is);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        PR[3 * i + j] = Q[mi_ix(i, 0)] * R[j] + Q[mi_ix(i, 1)] * R[3 + j] + Q[mi_ix(i, 2)] * R[6 + j];
+        RI[3 * i + j] = R[3 * i] * Is[j] + R[3 * i + 1] * Is[3 + j] + R[3 * i + 2] * Is[6 + j];
+      }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) g_I[3 * i + j] = (float)(R[i] * PR[j] + R[3 + i] * PR[3 + j] + R[6 + i] * PR[6 + j]);  // R^T P_aa R
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {  // adj R = 2 P_aa R Is; column k of R is qrot(q, e_k)
+      v3 gk;
+      gk.x = (float)(2.0 * (Q[mi_ix(0, 0)] * RI[k] + Q[mi_ix(0, 1)] * RI[3 + k] + Q[mi_ix(0, 2)] * RI[6 + k]));
+      gk.y = (float)(2.0 * (Q[mi_ix(1, 0)] * RI[k] + Q[mi_ix(1, 1)] * RI[3 + k] + Q[mi_ix(1, 2)] * RI[6 + k]));
+      gk.z = (float)(2.0 * (Q[mi_ix(2, 0)] * RI[k] + Q[mi_ix(2, 1)] * RI[3 + k] + Q[mi_ix(2, 2)] * RI[6 + k]));
+      adj_qrot_q(B.s.r, V3(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f), own_q, gk);
+    }
+    const double tr = Q[mi_ix(0, 0)] + Q[mi_ix(1, 1)] + Q[mi_ix(2, 2)];
+    double Pd[3], dPd = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      Pd[i] = Q[mi_ix(i, 0)] * dv[0] + Q[mi_ix(i, 1)] * dv[1] + Q[mi_ix(i, 2)] * dv[2];
+      dPd += dv[i] * Pd[i];
+    }
+    const double vx[3] = {Q[mi_ix(2, 4)] - Q[mi_ix(1, 5)], Q[mi_ix(0, 5)] - Q[mi_ix(2, 3)], Q[mi_ix(1, 3)] - Q[mi_ix(0, 4)]};  // the m [d]x blocks
+    g_m = (float)(tr * d2 - dPd + 2.0 * (dv[0] * vx[0] + dv[1] * vx[1] + dv[2] * vx[2]) + Q[mi_ix(3, 3)] + Q[mi_ix(4, 4)] + Q[mi_ix(5, 5)]);
+    v3 adj_d = V3((float)(2.0 * m * (tr * dv[0] - Pd[0] + vx[0])), (float)(2.0 * m * (tr * dv[1] - Pd[1] + vx[1])),
+                  (float)(2.0 * m * (tr * dv[2] - Pd[2] + vx[2])));
+    // the joint's axes and anchor
+    qt adj_q_wj = Q4(0, 0, 0, 0);
+    if (J.type == PD_JOINT_FREE) {
+      adj_qrot_q(J.q_wj, V3(1, 0, 0), adj_q_wj, gu0);
+      adj_qrot_q(J.q_wj, V3(0, 1, 0), adj_q_wj, gu1);
+      adj_qrot_q(J.q_wj, V3(0, 0, 1), adj_q_wj, gu2);
+      adj_d += adj_ra;  // (a FREE joint's anchor is d)
+    } else if (J.type == PD_JOINT_REVOLUTE) {
+      adj_qrot_q(J.q_wj, J.axis, adj_q_wj, gu0);
+    } else if (J.type == PD_JOINT_COMPOUND) {
+      const JcCompound &C = B.C;
+      qt adj_q_w = Q4(0, 0, 0, 0), adj_r_err = adj_q_w;
+      v3 adj_c0 = V3(0, 0, 0), adj_a1 = adj_c0, adj_c2 = adj_c0;
+      adj_qrot(C.q_w, B.c0, adj_q_w, adj_c0, gu0);
+      adj_qrot(C.q_w, C.a1, adj_q_w, adj_a1, gu1);
+      adj_qrot(C.q_w, B.c2, adj_q_w, adj_c2, gu2);
+      v3 adj_a2 = adj_c2;
+      if (!generalized) {  // c_0 = (e_0 - s a_2) id, c_2 = (a_2 - s e_0) id, s = a_2.x, id = 1 / (1 - s^2)
+        const float id = 1.0f / (1.0f - C.s * C.s);
+        adj_a2 = (adj_c2 - adj_c0 * C.s) * id;
+        adj_a2.x += -id * (dot(C.a2, adj_c0) + adj_c2.x) + (dot(B.c0, adj_c0) + dot(B.c2, adj_c2)) * (2.0f * C.s * id);
+      }
+      adj_qmul_a(J.q_off, adj_q_wj, adj_q_w);
+      // the axis chain and the decomposition, as k_body_twist_vjp
+      float adj_ang[3] = {0.f, 0.f, 0.f};
+      qt adj_q10 = Q4(0, 0, 0, 0), adj_q_1 = adj_q10, adj_q_0 = adj_q10;
+      adj_qrot_q(C.q10, V3(0, 0, 1), adj_q10, adj_a2);
+      adj_qmul(C.q_1, C.q_0, adj_q_1, adj_q_0, adj_q10);
+      adj_q_axis_angle(C.a1, C.ang[1], adj_a1, adj_ang[1], adj_q_1);
+      adj_qrot_q(C.q_0, V3(0, 1, 0), adj_q_0, adj_a1);
+      adj_q_axis_angle_ang(V3(1, 0, 0), C.ang[0], adj_ang[0], adj_q_0);
+      qt adj_q_pc = Q4(0, 0, 0, 0), adj_qa = adj_q_pc;
+      quat_decompose_adj(C.q_pc, C.c0, C.c1, C.c2, adj_ang, adj_q_pc);
+      adj_qmul_a(J.q_off, adj_qa, adj_q_pc);
+      adj_qmul_b(qconj(J.q_off), adj_r_err, adj_qa);
+      qt adj_cq = Q4(0, 0, 0, 0);
+      adj_qmul(qconj(J.q_wj), B.s.r, adj_cq, own_q, adj_r_err);  // r_err = conj(q_wj) q_c
+      adj_q_wj += qconj(adj_cq);
+    }
+    if (J.type != PD_JOINT_FREE && J.parent >= 0) {  // ra = (p_p - o0) + R(q_p) p_pj
+      par_p += adj_ra;
+      adj_qrot_q(J.qp, J.p_pj, par_q, adj_ra);
+    }
+    if (J.parent >= 0) adj_qmul_a(J.q_pj, par_q, adj_q_wj);  // q_wj = q_p q_pj
+    own_p += adj_d;  // d = (p_b - o0) + R(q_b) com_b
+    adj_qrot_q(B.s.r, J.com, own_q, adj_d);
+  }
+  float *ps = pslot + threadIdx.x * GF_S;
+  ps[0] = par_p.x; ps[1] = par_p.y; ps[2] = par_p.z; ps[3] = par_q.x; ps[4] = par_q.y; ps[5] = par_q.z; ps[6] = par_q.w;
+  __syncthreads();
+  if (!L.active) return;
+  for (int k = 0; k < T.nch; ++k) {
+    const int c = (int)T.ch[k];
+    if (c >= 0 && c < nb) {
+      const float *cs = pslot + (base + c) * GF_S;
+      own_p += ld3(cs); own_q += ld4(cs + 3);
+    }
+  }
+  dst[0] = own_p.x; dst[1] = own_p.y; dst[2] = own_p.z;
+  dst[3] = own_q.x; dst[4] = own_q.y; dst[5] = own_q.z; dst[6] = own_q.w;
+  dst[7] = g_m;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) dst[8 + k] = g_I[k];
+}
+
 template <int OP>
 int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, hipStream_t st) {
   const dim3 grid((n + 255) / 256), block(256);
@@ -2100,6 +2547,7 @@ int launch_pose(int n, const float *a, int a_bcast, const float *b, float *out, 
 //   body acceleration  b / g_b [n][19] = (state, the derivatives of the joint's rate slots), out / g_out [n][6]; the joint table, no g_a
 //   mass inverse       b [n][23] = (pose, mass, inertia, the joint's force slots), out [n][6]; the joint table; forward only -- the
 //                      gradient is composed by the caller from this op and the body twist, pd_pose_op_vjp refuses the code by name
+//   mass matrix        b / g_b [n][17] = (pose, mass, inertia), out / g_out [n / nb][nqd * nqd]; the joint table, no g_a
 enum Geometry { GEO_WAVE, GEO_LANE, GEO_SETS };  // a wavefront per element / a lane per element / 256 / nb whole state sets per workgroup
 struct TabledOp { int op; const char *name, *table; int max_nb; bool has_g_a; Geometry fwd, vjp; const char *composed = nullptr; };  // max_nb 0: no cap (GEO_SETS needs one <= 256); composed: no VJP kernel, and from what the gradient is put together
 constexpr TabledOp TABLED[] = {
@@ -2113,6 +2561,7 @@ constexpr TabledOp TABLED[] = {
     {PD_POSE_BODY_ACCEL, "PD_POSE_BODY_ACCEL", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
     {PD_POSE_MASS_INVERSE, "PD_POSE_MASS_INVERSE", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS,
      "the gradient is composed from pd_pose_op(21) and PD_POSE_BODY_TWIST (17)"},
+    {PD_POSE_MASS_MATRIX, "PD_POSE_MASS_MATRIX", "joint", JC_MAXNB, false, GEO_SETS, GEO_SETS},
 };
 
 template <class... A>
@@ -2170,6 +2619,10 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
     case PD_POSE_MASS_INVERSE:  // (forward only: the VJP was refused above)
       hipLaunchKernelGGL(k_mass_inverse, grid, block, 0, st, count, nb, tab, rows, out);
       break;
+    case PD_POSE_MASS_MATRIX:
+      if (out) hipLaunchKernelGGL(k_mass_matrix, grid, block, 0, st, count, nb, tab, rows, out);
+      else hipLaunchKernelGGL(k_mass_matrix_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
+      break;
     default:
       if (out) hipLaunchKernelGGL(k_contact_state_fwd, grid, block, 0, st, count, nb, tab, rows, out);
       else hipLaunchKernelGGL(k_contact_state_vjp, grid, block, 0, st, count, nb, tab, rows, g_out, g_b);
@@ -2182,7 +2635,8 @@ int launch_tabled(const TabledOp &T, int n, const float *tab, int nb, const floa
 int pose_dispatch(int op, int n, const float *a, int a_bcast, const float *b, float *out, const float *g_out, float *g_a, float *g_b, void *stream,
                   bool vjp) {  // vjp: which entry calls (at n = 0 every pointer may be NULL)
   if (n < 0 || op < 0 || (op > PD_POSE_JOINT_COORDS && op != PD_POSE_CENTROIDAL && op != PD_POSE_CONTACT_STATE && op != PD_POSE_JOINT_WRENCH &&
-                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST && op != PD_POSE_BODY_ACCEL && op != PD_POSE_MASS_INVERSE))  // (codes 7, 8, 10, 12, 14, 16, 18 and 20 are not assigned: include/ppr_diffphys.h)
+                         op != PD_POSE_GENERALIZED_FORCE && op != PD_POSE_BODY_TWIST && op != PD_POSE_BODY_ACCEL && op != PD_POSE_MASS_INVERSE &&
+                         op != PD_POSE_MASS_MATRIX))  // (codes 7, 8, 10, 12, 14, 16, 18, 20 and 22 are not assigned: include/ppr_diffphys.h)
     return pd_set_error("pd_pose_op: n < 0 or an unknown op");
   for (const TabledOp &T : TABLED)
     if (op == T.op) return launch_tabled(T, n, a, a_bcast, b, out, g_out, g_a, g_b, (hipStream_t)stream, vjp);

@@ -431,6 +431,44 @@ class MassInverse(torch.autograd.Function):
                 g_i.reshape(lead + (nb, 3, 3)) if ctx.needs_input_grad[2] else None, g_r, None, None)
 
 
+class MassMatrix(torch.autograd.Function):
+    """body_q (..., nb, 7), body_mass (..., nb), body_inertia (..., nb, 3, 3) (body frame, about the centre of mass; its symmetric part
+    enters), env, rates -> (..., nqd, nqd) = H = J^T M J, the joint-space mass matrix of the articulation in the rate convention
+    ``rates``, in the joint_qd layout (``pd_pose_op`` PD_POSE_MASS_MATRIX on the env's joint table: the composite-rigid-body recursion,
+    one launch forward and one for the vector-Jacobian product, a kernel of its own that takes any upstream gradient, symmetric or
+    not).  All three tensors carry the full leading shape; broadcasting masses and inertias is the caller's (``dp_utils.mass_matrix``
+    does it, so that autograd sums shared ones).  ONCE differentiable.  float32 GPU tensors, or an error: no CPU fallback.  Raw
+    partials (quaternion entries not projected; the inertia's are those of its symmetric part)."""
+
+    @staticmethod
+    def forward(ctx, body_q, body_mass, body_inertia, env, rates="generalized"):
+        nb = int(env.nb)
+        _need_gpu("MassMatrix", body_q, body_mass, body_inertia)
+        lead = tuple(body_q.shape[:-2])
+        if not (body_q.dim() >= 2 and tuple(body_q.shape) == lead + (nb, 7) and tuple(body_mass.shape) == lead + (nb,)
+                and tuple(body_inertia.shape) == lead + (nb, 3, 3)):
+            raise ValueError("MassMatrix: body_q (..., %d, 7), body_mass (..., %d) and body_inertia (..., %d, 3, 3) with equal leading "
+                             "shapes; got %s, %s and %s" % (nb, nb, nb, tuple(body_q.shape), tuple(body_mass.shape), tuple(body_inertia.shape)))
+        table = hip_backend.env_joint_table(env, body_q.device, rates)
+        rows = torch.cat([t.detach().reshape(-1, w) for t, w in ((body_q, 7), (body_mass, 1), (body_inertia, 9))], dim=1)
+        out = hip_backend.mass_matrix(table, nb, rows)
+        ctx.table, ctx.nb, ctx.lead = table, nb, lead
+        ctx.save_for_backward(rows)
+        return out.view(lead + tuple(out.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None, None
+        lead, nb = ctx.lead, ctx.nb
+        nqd = int(g.shape[-1])
+        g_r = hip_backend.mass_matrix_vjp(ctx.table, nb, rows, g.to(torch.float32).reshape(-1, nqd, nqd).contiguous())
+        return (g_r[:, :7].reshape(lead + (nb, 7)) if ctx.needs_input_grad[0] else None,
+                g_r[:, 7].reshape(lead + (nb,)) if ctx.needs_input_grad[1] else None,
+                g_r[:, 8:].reshape(lead + (nb, 3, 3)) if ctx.needs_input_grad[2] else None, None, None)
+
+
 def checkpoint_plan(nsteps, frame2step, K):
     """The launches of a checkpointed rollout adjoint: ``nsteps`` steps cut into segments of ``K`` (the last one shorter when K does not
     divide nsteps).  Pure; -> (launch_frames, segments).

@@ -542,11 +542,40 @@ def jacobian(body_q, env, rates="generalized"):
     return tw.permute(tuple(range(len(lead))) + (len(lead) + 1, len(lead) + 2, len(lead)))
 
 
-def mass_matrix(body_q, body_mass, body_inertia, env):
-    """The joint-space mass matrix H = sum_b J_b^T diag(R_b I_b R_b^T, m_b 1) J_b of the generalised rates: body_q (..., nb, 7),
-    body_mass broadcastable to (..., nb), body_inertia (body frame, about the centre of mass) to (..., nb, 3, 3) -> (..., nqd, nqd),
-    with qd^T H qd / 2 the kinetic energy of ``body_twists(body_q, qd, env)``.  Plain torch on ``jacobian(body_q, env, "generalized")``
-    -- its S * nqd * nb rows --, not a composite-rigid-body kernel; differentiable in every tensor argument."""
+def mass_matrix(body_q, body_mass, body_inertia, env, method="jacobian", rates="generalized"):
+    """The joint-space mass matrix H = sum_b J_b^T diag(R_b I_b R_b^T, m_b 1) J_b: body_q (..., nb, 7), body_mass broadcastable to
+    (..., nb), body_inertia (body frame, about the centre of mass) to (..., nb, 3, 3) -> (..., nqd, nqd), with qd^T H qd / 2 the
+    kinetic energy of ``body_twists(body_q, qd, env, rates)``.
+    method="jacobian" (the default): plain torch on ``jacobian(body_q, env, "generalized")`` -- its S * nqd * nb rows, so for a few
+    state sets, not a batch of thousands --, the generalised rates only (rates="measured" raises ValueError); differentiable in every
+    tensor argument.
+    method="crba": the composite-rigid-body recursion as ONE HIP launch (``dp_model.MassMatrix``, ``pd_pose_op`` code 23), any batch
+    size, either rate convention ("measured": the matrix whose inverse ``mass_inverse`` applies in that mode); exactly symmetric, exactly
+    0 between dofs of unrelated bodies; the inertia is taken as symmetric.  Differentiable ONCE in all three tensors by a kernel of its
+    own.  Masses and inertias are broadcast HERE, outside the Function, so autograd sums the gradient of a shared entry.  float32 GPU
+    tensors only."""
+    if method not in ("jacobian", "crba"):
+        raise ValueError("mass_matrix: method must be \"jacobian\" or \"crba\"; got %r" % (method,))
+    if rates not in ("generalized", "measured"):
+        raise ValueError("mass_matrix: rates must be \"generalized\" or \"measured\"; got %r" % (rates,))
+    if method == "crba":
+        from .dp_model import MassMatrix
+
+        _need_gpu("mass_matrix", body_q, body_mass, body_inertia)
+        nb = int(env.nb)
+        if not (body_q.dim() >= 2 and tuple(body_q.shape[-2:]) == (nb, 7)):
+            raise ValueError("mass_matrix: body_q must be (..., %d, 7); got %s" % (nb, tuple(body_q.shape)))
+        lead = tuple(body_q.shape[:-2])
+        for name, t, tail in (("body_mass", body_mass, (nb,)), ("body_inertia", body_inertia, (nb, 3, 3))):
+            try:
+                ok = t.dim() >= len(tail) and tuple(torch.broadcast_shapes(tuple(t.shape), lead + tail)) == lead + tail
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError("mass_matrix: %s must broadcast to %s; got %s" % (name, lead + tail, tuple(t.shape)))
+        return MassMatrix.apply(body_q, body_mass.expand(lead + (nb,)), body_inertia.expand(lead + (nb, 3, 3)), env, rates)
+    if rates != "generalized":
+        raise ValueError("mass_matrix: rates=\"measured\" is served by method=\"crba\" only; method=\"jacobian\" is the generalised rates'")
     J = jacobian(body_q, env, "generalized")
     mass = torch.as_tensor(body_mass, dtype=J.dtype, device=J.device)
     inertia = torch.as_tensor(body_inertia, dtype=J.dtype, device=J.device)
@@ -683,17 +712,25 @@ def bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external=None, r
 def forward_dynamics(body_q, joint_qd, tau, body_mass, body_inertia, env, external=None, method="dense"):
     """The joint accelerations the joint-space forces tau (..., nqd) produce, in ``rnea``'s sign convention and the generalized rates:
     H^-1 (tau - ``bias_forces``) -> (..., nqd), so ``forward_dynamics(rnea(qdd)) = qdd``.
-    method="dense" (the default): solve(``mass_matrix``, .), plain torch (a dense solve) on ``mass_matrix`` -- S * nqd * nb rows through
-    ``body_twists`` --: like ``mass_matrix`` it is meant for a few state sets, not for a batch of thousands, and it is not an
-    articulated-body kernel.  method="articulated": ``mass_inverse`` of the same right-hand side, the articulated-body recursion in one
-    HIP launch behind the three of ``bias_forces``: O(nb) per set, any batch size, once differentiable.  Differentiable in every tensor
-    argument.  float32 GPU tensors only."""
-    if method not in ("dense", "articulated"):
-        raise ValueError("forward_dynamics: method must be \"dense\" or \"articulated\"; got %r" % (method,))
+    method="dense" (the default): solve(``mass_matrix``, .), plain torch (a dense solve) on ``mass_matrix(method="jacobian")`` --
+    S * nqd * nb rows through ``body_twists`` --: it is meant for a few state sets, not for a batch of thousands.
+    method="crba": the same dense solve on ``mass_matrix(method="crba")``, H from one HIP launch at any batch size.
+    method="articulated": ``mass_inverse`` of the same right-hand side, the articulated-body recursion in one HIP launch behind the
+    three of ``bias_forces``: O(nb) per set, any batch size, once differentiable.  Differentiable in every tensor argument.  float32
+    GPU tensors only (method="crba" on anything else: ValueError)."""
+    if method not in ("dense", "articulated", "crba"):
+        raise ValueError("forward_dynamics: method must be \"dense\", \"crba\" or \"articulated\"; got %r" % (method,))
     if method == "articulated":
         rhs = tau - bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external, "generalized")
         return mass_inverse(body_q, rhs, body_mass, body_inertia, env, "generalized")
-    H = mass_matrix(body_q, body_mass, body_inertia, env)
+    if method == "crba":
+        try:
+            _need_gpu("forward_dynamics", body_q, joint_qd, tau, body_mass, body_inertia)
+        except TypeError as e:   # the method is a HIP kernel and nothing else
+            raise ValueError("forward_dynamics: method=\"crba\" is not available for these tensors -- %s" % (e,)) from None
+        H = mass_matrix(body_q, body_mass, body_inertia, env, method="crba")
+    else:
+        H = mass_matrix(body_q, body_mass, body_inertia, env)
     rhs = tau - bias_forces(body_q, joint_qd, body_mass, body_inertia, env, external, "generalized")
     return torch.linalg.solve(H, rhs[..., None])[..., 0]
 

@@ -861,7 +861,7 @@ def _env_table(env, key, build):
 
 
 def _state_op_check(op, kind, width, table, nb, rows, bare=False, name=None, columns=None):
-    """The argument check of the seventeen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
+    """The argument check of the nineteen state-op entries -> (n, the table's dims).  The dimensions travel with tensors the ``kind``_table
     functions made: a table of another kind or another model is refused here, where that can be seen (the library cannot validate a
     device buffer).  bare: a table without a tag is taken on trust (dims None); otherwise it is refused."""
     tag = _table_tag(table)
@@ -1418,6 +1418,38 @@ def mass_inverse(table, nb, rows):
     out = torch.empty(n, 6, device=rows.device, dtype=torch.float32)
     _check(lib().pd_pose_op(POSE_MASS_INVERSE, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
     return out
+
+
+POSE_MASS_MATRIX = 23   # (codes 22 and 24 are not assigned: include/ppr_diffphys.h)
+_MM_COLUMNS = "(p, q xyzw, m, I row-major)"
+
+
+def mass_matrix(table, nb, rows):
+    """``pd_pose_op`` PD_POSE_MASS_MATRIX: rows [n, 17] = (p, q xyzw, m, I row-major) per body -- a pose, the body's mass and body-frame
+    inertia about its centre of mass (its symmetric part enters) --, n a multiple of nb (row i is body i % nb of set i // nb), and the
+    joint table of ``joint_coords`` -> [n / nb, nqd, nqd]: H = J^T M J, the joint-space mass matrix of the articulation in the table's
+    rate mode ("generalized": ``dp_utils.mass_matrix``; "measured": the matrix whose inverse ``mass_inverse`` applies in that mode), in
+    the joint_qd layout.  The composite-rigid-body recursion, one launch.  Exactly symmetric; exactly 0 between dofs of bodies neither
+    of which is the other's ancestor.  Fixed order, no atomics: a set's bits depend neither on the call nor on the other sets."""
+    n, (_, _, nqd) = _state_op_check("mass_matrix", "joint", 17, table, int(nb), rows, name="rows", columns=_MM_COLUMNS)
+    out = torch.empty(n // int(nb), nqd, nqd, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op(POSE_MASS_MATRIX, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(out, "out"), _stream()))
+    return out
+
+
+def mass_matrix_vjp(table, nb, rows, g_out):
+    """``pd_pose_op_vjp`` PD_POSE_MASS_MATRIX: g_out [n / nb, nqd, nqd], arbitrary (not assumed symmetric) -> g_rows [n, 17], the raw
+    partials with respect to pose, mass and inertia (quaternion entries not projected; the inertia's are those of its symmetric part).
+    One launch of a kernel of its own."""
+    n, (_, _, nqd) = _state_op_check("mass_matrix_vjp", "joint", 17, table, int(nb), rows, name="rows", columns=_MM_COLUMNS)
+    sets = n // int(nb)
+    if not torch.is_tensor(g_out) or tuple(g_out.shape) != (sets, nqd, nqd):
+        raise ValueError("mass_matrix_vjp: g_out must be a [%d, %d, %d] tensor; got %s" % (sets, nqd, nqd, tuple(getattr(g_out, "shape", ()))))
+    _grad_check("mass_matrix_vjp", "g_out", g_out.view(sets, nqd * nqd) if g_out.is_contiguous() else g_out.reshape(sets, nqd * nqd), sets, nqd * nqd)
+    g_b = torch.empty(n, 17, device=rows.device, dtype=torch.float32)
+    _check(lib().pd_pose_op_vjp(POSE_MASS_MATRIX, n, _dev(table, "table"), int(nb), _ptr(rows, "rows"), _ptr(g_out, "g_out", sets * nqd * nqd),
+                                None, _ptr(g_b, "g_b"), _stream()))
+    return g_b
 
 
 def _dev_int(t, name):

@@ -753,7 +753,7 @@ class phys_model(nn.Module):
         return st["out"]
 
     @torch.no_grad()
-    def query(self, img_size=None, joint_coords=False, centroidal=False, contacts=False, efforts=False):
+    def query(self, img_size=None, joint_coords=False, centroidal=False, contacts=False, efforts=False, mass_matrix=False):
         """Env 0 of the last forward(), frame by frame, in the reference's keys (dp_model.py:843-902): the simulated, target and
         control-reference robots POSED -- the reference hands trimesh objects to its renderer (articulate_robot_rbrt:
         collision-mesh vertices rotated and translated by each body's pose); here each is the array of those posed vertices
@@ -771,7 +771,9 @@ class phys_model(nn.Module):
         (dp_utils.contact_state: the lowest candidate of every body, and how many of its candidates touch).
         efforts=True adds `sim_joint_efforts` [F, nqd]: `jaf` of each frame read in joint space (dp_utils.generalized_force of
         `sim_poses` and env 0's jaf, actuator efforts, the joint_qd layout) -- how hard every actuator pulled, and the net joint
-        wrench on the floating root."""
+        wrench on the floating root.
+        mass_matrix=True adds `sim_mass_matrix` [F, nqd, nqd]: the joint-space mass matrix of the generalised rates at each frame's
+        `sim_poses` with the LEARNED body_mass and norm_body_inertia x body_mass (dp_utils.mass_matrix(method="crba"): one launch)."""
         sim = np.stack(list(self.sim_trajs), 0).astype(np.float64)
         tgt = np.stack(list(self.target_trajs), 0).astype(np.float64)
         ref = np.stack(list(self.pid_ref), 0).astype(np.float64)
@@ -839,4 +841,11 @@ class phys_model(nn.Module):
             nb = int(self.env.nb)
             jaf0 = torch.stack(self.jafs, 0)[:, :nb].to(self.device, torch.float32).contiguous()   # env 0
             data["sim_joint_efforts"] = _generalized_force(up(self.sim_trajs), jaf0, self.env, efforts="actuator").cpu().numpy()
+        if mass_matrix:
+            from .dp_utils import mass_matrix as _mass_matrix
+
+            up = lambda frames: torch.from_numpy(np.ascontiguousarray(np.stack(list(frames), 0), dtype=np.float32)).to(self.device)
+            mass = self.body_mass.detach().to(self.device, torch.float32)
+            inertia = self.norm_body_inertia.detach().to(self.device, torch.float32) * mass[:, None, None]
+            data["sim_mass_matrix"] = _mass_matrix(up(self.sim_trajs), mass, inertia, self.env, method="crba").cpu().numpy()
         return data
