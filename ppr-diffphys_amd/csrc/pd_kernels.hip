@@ -132,8 +132,54 @@ PD_DEV int seg_slot(bool pred, SegMask sm, int &total) {
 // and entries that contribute exactly 0 may sit anywhere.  The loop runs (longest run of the wave - 1) times, typically 1-3
 // (a foot's few points); the first version walked the lanes one by one, (hits of the env - 1) iterations, and was 11 % of the
 // adjoint kernel at 4096 envs.  2 NV VALU instructions per iteration (v_add_f32_dpp wave_shr:1 + v_cndmask).
+// The NV values travel as RunVals<NV>, a struct of NV floats named by a compile-time index (rv<I>), not as float[NV]: an array that lives
+// across the iterations is promoted to ONE vector value of NV floats, which the loop then carried as a register tuple -- 16 v_mov_b64 per
+// iteration beside the 2 NV, NV more v_mov for a copy x = acc ahead of the loop; a struct is NV scalars from the first pass on.
+// x holds the terms and is left as it was, z takes the sums.  Iteration 1 stands ahead of every branch: it reads x where it is and writes z,
+// a new set (a wave without a run of two pays its 2 NV for nothing; every other wave saves the copy and a branch).  Iteration 2 behind a
+// wave-uniform test and the loop for the rest update z in place: an iteration is its 2 NV instructions, the compare and the branch.
+template <int N> struct RunVals { float v; RunVals<N - 1> r; };
+template <> struct RunVals<0> {};
+template <int I, int N>
+PD_DEV float &rv(RunVals<N> &p) {
+  if constexpr (I == 0) return p.v;
+  else return rv<I - 1>(p.r);
+}
+template <int I, int N>
+PD_DEV float rv(const RunVals<N> &p) {
+  if constexpr (I == 0) return p.v;
+  else return rv<I - 1>(p.r);
+}
+template <int NV, int I = 0>
+PD_DEV void run_sum_trip(RunVals<NV> &z, const RunVals<NV> &zin, const RunVals<NV> &x, bool upd) {
+  if constexpr (I < NV) {
+    const float own = rv<I>(zin);
+    const float prev = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(own), 0x138, 0xf, 0xf, true));
+    const float sum = prev + rv<I>(x);
+    float t = upd ? sum : own;
+    // (no instruction: the sum stays live past the select, so the select cannot share the sum's register and takes own's -- without it
+    // the loop kept z in two sets and copied one to the other in every iteration)
+    asm("" : "+v"(t) : "v"(sum));
+    rv<I>(z) = t;
+    run_sum_trip<NV, I + 1>(z, zin, x, upd);
+  }
+}
+template <int NV, int I = 0>
+PD_DEV void rv_store(float *dst, const RunVals<NV> &src) {
+  if constexpr (I < NV) {
+    dst[I] = rv<I>(src);
+    rv_store<NV, I + 1>(dst, src);
+  }
+}
+template <int NV, int I = 0>
+PD_DEV void rv_load(RunVals<NV> &dst, const float *src) {
+  if constexpr (I < NV) {
+    rv<I>(dst) = src[I];
+    rv_load<NV, I + 1>(dst, src);
+  }
+}
 template <int NV>
-PD_DEV void seg_run_sum(float *acc, int pb, int l, int nh, bool &last) {
+PD_DEV void seg_run_sum(const RunVals<NV> &x, RunVals<NV> &z, int pb, int l, int nh, bool &last) {
   const int pbp = __builtin_amdgcn_update_dpp(-1, pb, 0x138, 0xf, 0xf, false);  // body of the hit one lane down (wave_shr:1)
   const int pbn = __builtin_amdgcn_update_dpp(-1, pb, 0x130, 0xf, 0xf, false);  // ... one lane up (wave_shl:1)
   const bool in = l < nh, start = in && (l == 0 || pbp != pb);
@@ -142,16 +188,10 @@ PD_DEV void seg_run_sum(float *acc, int pb, int l, int nh, bool &last) {
   const int lane = (int)(threadIdx.x & 63);
   const unsigned long long starts = __ballot(start), below = starts & ((2ull << lane) - 1ull);
   const int pos = in ? lane - (63 - __clzll((long long)below)) : -1;
-  float x[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) x[i] = acc[i];
-  for (int it = 1; __ballot(pos >= it) != 0ull; ++it) {
-    const bool upd = pos >= it;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const float prev = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[i]), 0x138, 0xf, 0xf, true));
-      acc[i] = upd ? prev + x[i] : acc[i];
-    }
+  run_sum_trip<NV>(z, x, x, pos >= 1);
+  if (__ballot(pos >= 2) != 0ull) {
+    run_sum_trip<NV>(z, z, x, pos >= 2);
+    for (int it = 3; __ballot(pos >= it) != 0ull; ++it) run_sum_trip<NV>(z, z, x, pos >= it);
   }
 }
 
@@ -722,15 +762,16 @@ __global__ __launch_bounds__(CULLW ? PD_BLOCK3 : (SPLIT ? PD_BLOCK : PD_FK_BLOCK
         // 0.189 ms, 8192 0.388 -> 0.372; at 2 048 envs the run sums lose 3 %, in the quad-lane kernel -- one env's candidates in one 64-lane
         // segment, runs of up to seven -- 37 %)
         if (RUNSUM && !two) {
-          float out[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          const int pbr = l < nh ? (c_e >> 24) & 0x3f : -2;
-          if (l < nh) touching = contact_hit(rec + pbr * PD_REC, c_P, c_M, out);
+          // every lane evaluates: a lane past the env's candidates holds entry 0 (valid data); the run sums read lanes below nh only,
+          // so what such a lane computes goes nowhere and out[] needs no zeros of its own
+          float out[6];
+          const int pbr = (c_e >> 24) & 0x3f;
+          touching = contact_hit(rec + pbr * PD_REC, c_P, c_M, out) && l < nh;
+          RunVals<6> x, sum;
+          rv_load<6>(x, out);
           bool last;
-          seg_run_sum<6>(out, pbr, l, nh, last);
-          if (last) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) facc[pbr * PD_W6 + i] = out[i];
-          }
+          seg_run_sum<6>(x, sum, pbr, l, nh, last);
+          if (last) rv_store<6>(facc + pbr * PD_W6, sum);
         } else if (l < nh) {
           float out[6];
           touching = contact_hit(rec + ((c_e >> 24) & 0x3f) * PD_REC, c_P, c_M, out);
@@ -1767,7 +1808,7 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       // as soon as the state wave has staged the step's records (hand-over S) instead of behind the wrench adjoints (hand-over A): that much
       // less stands between A and B (adjoint 0.177 -> 0.168 ms at 512 envs).  The lane-per-body kernel keeps both halves behind A: with a
       // hand-over R of its body wave right behind the staging, the early half took issue slots from that wave's phase 1 (4096 envs: 0.268 -> 0.273)
-      const int pb = l < nh ? (e_c >> 24) & 0x3f : -2;
+      const int pb = (e_c >> 24) & 0x3f;  // (a lane past the hits holds entry 0, fetch_point: body 0)
       ContactPre cpre;
       cpre.touch = false;
       if constexpr (QUAD) {
@@ -1781,26 +1822,26 @@ __global__ __launch_bounds__(PD_BLOCK) void k_rollout_bwd(PdDevModel m, RolloutA
       __builtin_amdgcn_s_setprio(PD_PRIO_CRITICAL);  // the body wave will wait for these contact adjoints
       STAMP(9);
       if (fast) {
+        // out[] has ONE definition, adj_store of an adjoint that is zero unless the hit touches (it was zeroed here, again inside l < nh and
+        // again inside "touching", and merged behind each).  Lane-per-body kernel: every lane evaluates -- a lane past the env's hits holds
+        // entry 0 (fetch_point), valid data; the run sums read lanes below nh only, so what such a lane computes goes nowhere.
         float out[PD_ADJ];
-#pragma unroll
-        for (int i = 0; i < PD_ADJ; ++i) out[i] = 0.f;
+        BodyAdj o = adj_zero();
         if constexpr (QUAD) {
           if (l < nh) {
-            BodyAdj o = adj_zero();
             contact_pre_barrier(cpre);
             contact_point_adj_rest(cpre, P_c, M_c, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
-            adj_store(out, o);
           }
         } else {
-          if (l < nh) contact_hit(rec_s + pb * PD_REC, P_c, M_c, out);
+          contact_point_adj<false, COM>(rec_s + pb * PD_REC, cull_s[pb], P_c, M_c, ld3(adjf + pb * PD_W6), ld3(adjf + pb * PD_W6 + 3), o);
         }
+        adj_store(out, o);
+        RunVals<PD_ADJ> x, sum;
+        rv_load<PD_ADJ>(x, out);
         STAMP(10);
         bool last;
-        seg_run_sum<PD_ADJ>(out, pb, l, nh, last);
-        if (last) {  // cacc is zero (its owner clears it after reading) and a body has one run
-#pragma unroll
-          for (int i = 0; i < PD_ADJ; ++i) cacc[pb * PD_ADJ + i] = out[i];
-        }
+        seg_run_sum<PD_ADJ>(x, sum, pb, l, nh, last);
+        if (last) rv_store<PD_ADJ>(cacc + pb * PD_ADJ, sum);  // cacc is zero (its owner clears it after reading) and a body has one run
         STAMP(11);
       } else {
         float4 cv = make_float4(0.f, 0.f, 1.f, 0.f);
